@@ -5,9 +5,15 @@ A "step" is one pass of `read2sdbg` (stage 1 + stage 2, k=21, min count 2, no me
 synthetic 150 bp paired-end reads that is already resident in HBM (BASELINE.json configs[1]: 10 M reads
 per GPU).  metric = M (k+1)-mer edge occurrences sorted+counted per second, E = sum(max(0, len-k)).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--reads R] [--no-cpu-baseline] [--no-e2e]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--reads R] [--dump-outputs DIR]
+    python bench.py --full [--no-cpu-baseline] [--no-cpu-full] [--no-e2e] ...
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
+
+A plain run sets up, warms up, times the steps and prints the line (metric, value, ms_per_step, config).
+--full adds what is measured or checked beside it: the files-in -> files-out CLI runs (e2e), per-kernel times with the
+roofline figures, the digest of the outputs against the reference's known answer (parity) and the CPU baseline.
+--dump-outputs DIR writes what the last timed step computed as DIR/<name>.npy (float32/float64, at most 64 MB).
 """
 import argparse
 import json
@@ -30,6 +36,20 @@ def log(*a):
     print(*a, file=sys.stderr, flush=True)
 
 
+def usable_cpus():
+    """CPUs this process may use: its affinity mask, capped by OMP_NUM_THREADS where that is set (a shared host may hand a
+    job fewer cores than os.cpu_count() reports)"""
+    try:
+        n = len(os.sched_getaffinity(0))
+    except (AttributeError, OSError):
+        n = os.cpu_count() or 1
+    try:
+        n = min(n, int(os.environ["OMP_NUM_THREADS"]))
+    except (KeyError, ValueError):
+        pass
+    return max(1, n)
+
+
 def make_reads(n_reads, rank, world):
     """Reads of this rank: PE fragments from ONE genome shared by all ranks (G = 2.5 bp per read in the
     whole job, i.e. ~60x coverage as in SURVEY.md §8d), per-rank read seed.  Returned reversed+packed.
@@ -42,7 +62,7 @@ def make_reads(n_reads, rank, world):
     # blocks of 1 M pairs made by spawned worker processes (a few per rank), stored reversed, as the reference loads them;
     # every chunk is a whole number of words only if n*2*150 % 16 == 0: true for n multiple of 8
     jobs = synth.pe_jobs("reversed", n_reads, G, 1, 1000 * (rank + 1) + 1, read_len=READ_LEN)
-    procs = max(1, min(len(jobs), (os.cpu_count() or 1) // max(1, world)))
+    procs = max(1, min(len(jobs), usable_cpus() // max(1, world)))
     return np.concatenate(list(synth.map_pe_blocks(jobs, procs)))
 
 
@@ -178,7 +198,7 @@ def cpu_baseline(sample_reads, threads=None):
     from megahit_amd import synth
     ref = os.path.join(ROOT, "oracle", "_ref", "ref_core")
     port = os.path.join(ROOT, "oracle", "oracle_core")
-    cores = os.cpu_count() or 1
+    cores = usable_cpus()
     G = max(5000, int(sample_reads * 2.5))
     reads = synth.gen_pe_reads(sample_reads // 2, G, read_len=READ_LEN, frag=400, err=0.005, seed=77)
     E = reads.shape[0] * (READ_LEN - K)
@@ -203,7 +223,7 @@ def cpu_baseline(sample_reads, threads=None):
             subprocess.run(cmd, check=True, stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL)
             tried[1] = time.perf_counter() - t0
     best = min(tried, key=tried.get)
-    out = {"value": round(E / tried[best] / 1e6, 3), "unit": "M edges/s", "cores": best, "kind": kind, "host_cores": cores,
+    out = {"value": round(E / tried[best] / 1e6, 3), "unit": "M edges/s", "cores": best, "kind": kind, "host_cores": os.cpu_count(),
            "threads_tried": {str(t): round(E / dt / 1e6, 3) for t, dt in tried.items()},
            "sample": "read2sdbg k=%d m=%d on %d synthetic %d bp reads (%.1f M edges), best wall %.1f s incl. file I/O"
                      % (K, MIN_COUNT, reads.shape[0], READ_LEN, E / 1e6, tried[best])}
@@ -377,11 +397,130 @@ def output_parity(eng, engine, n_reads, world, res):
             "reference": "oracle/_ref/ref_core (reference sources) on the same reads: tests/golden/fullsize.json"}
 
 
-def main():
+def roofline(stats, steps, with_traffic, torch):
+    """--full: the dominant kernel of the timed steps (per-kernel event times of the library) against the HBM peak, with the
+    counter measurement of this build where one is committed and a device-to-device copy measured now"""
+    # dominant kernel by total time
+    name, ks = max(stats.items(), key=lambda kv: kv[1]["ms"])
+    per_launch_bytes = ks["bytes"] / ks["launches"]
+    per_launch_ms = ks["ms"] / ks["launches"]
+    achieved = per_launch_bytes / per_launch_ms / 1e6  # GB/s
+    traffic, traffic_src = pmc_traffic(name) if with_traffic else (None, None)
+    copy_gbs = copy_bandwidth(torch)
+    roof = {"bound": "hbm", "kernel": name, "achieved": round(achieved, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
+            "frac": round(achieved / HBM_PEAK_GBS, 4), "traffic": traffic, "traffic_source": traffic_src,
+            "copy_kernel_GBs": copy_gbs, "frac_of_copy_kernel": round(achieved / copy_gbs, 4) if copy_gbs else None,
+            "launches_per_step": ks["launches"] // max(1, steps), "avg_launch_ms": round(per_launch_ms, 4),
+            "algo_bytes_per_launch": per_launch_bytes,
+            # every kernel of a step together (counter file of the running build, else null): what the step moves through HBM
+            "traffic_per_step_all_kernels": pmc_traffic_per_step() if with_traffic else None,
+            # the contract's "bound" knows hbm | mfma; the group-by over super-k-mer records is neither: it reads 16 bytes per 3.5 windows and
+            # spends its time on LDS compare-and-swaps and the vector instructions that form the keys (profiles/rNN_pmc_sq.json)
+            "note": ("dominant kernel is the LDS group-by of stage 1 on super-k-mer records: bound by LDS atomics and vector issue, not by HBM — its "
+                     "fraction of the HBM peak says how few bytes it needs, not how well it runs; the HBM-bound kernels of the step are the sort passes "
+                     "(top_kernels)") if name in ("s1_skm_groups", "count_skm_groups") else None,
+            "kernel_ms_per_step": {k2: round(v["ms"] / steps, 3) for k2, v in sorted(stats.items(), key=lambda kv: -kv[1]["ms"])},
+            # the same figure for the three kernels with the largest time per step (they are within a few per cent of each
+            # other, and which of them leads changes from box to box): algorithmic GB/s of one launch and its fraction of the peak
+            "top_kernels": [{"kernel": k2, "ms_per_step": round(v["ms"] / steps, 3), "launches_per_step": v["launches"] // max(1, steps),
+                             "achieved": round(v["bytes"] / v["ms"] / 1e6, 1) if v["ms"] > 0 else None,
+                             "frac": round(v["bytes"] / v["ms"] / 1e6 / HBM_PEAK_GBS, 4) if v["ms"] > 0 else None,
+                             "traffic": pmc_traffic(k2)[0] if with_traffic else None}
+                            for k2, v in sorted(stats.items(), key=lambda kv: -kv[1]["ms"])[:3]]}
+    return roof
+
+
+DUMP_LIMIT_BYTES = 64 << 20  # all files of --dump-outputs together
+DUMP_WHOLE_BYTES = 16 << 20  # an output up to this size (as floats) is written whole ...
+DUMP_SAMPLE = 4 << 20        # ... a larger one as this many sampled elements + its chunk sums
+DUMP_SEED = 20240601
+DUMP_CHUNK = 1 << 20
+
+
+def _float_view(a):
+    """integer output -> float32 (up to 16 bits: exact) or float64 (the counts and words here stay below 2^53: exact)"""
+    import numpy as np
+    return a.astype(np.float32 if a.dtype.itemsize <= 2 else np.float64)
+
+
+def _dump_array(out_dir, name, a, written):
+    """writes `a` as out_dir/<name>.npy in floats; an array larger than DUMP_WHOLE_BYTES is written as a fixed, seeded sample
+    (<name>_sample.npy: sorted positions drawn from np.random.default_rng(DUMP_SEED), the same for the same length) plus
+    <name>_chunk_sums.npy: over every DUMP_CHUNK bytes of it, sum(byte * (position % 251 + 1)) in float64 (exact), so that
+    no byte of the output goes unchecked.  Returns the bytes written so far."""
+    import numpy as np
+    a = np.ascontiguousarray(a).ravel()
+    files = {}
+    if a.size * (4 if a.dtype.itemsize <= 2 else 8) <= DUMP_WHOLE_BYTES:
+        files[name] = _float_view(a)
+    else:
+        idx = np.sort(np.random.default_rng(DUMP_SEED).integers(0, a.size, DUMP_SAMPLE))
+        files[name + "_sample"] = _float_view(a[idx])
+        raw = a.view(np.uint8)
+        n_chunks = (raw.size + DUMP_CHUNK - 1) // DUMP_CHUNK
+        weights = (np.arange(DUMP_CHUNK, dtype=np.float64) % 251) + 1
+        sums = np.empty(n_chunks, dtype=np.float64)
+        for c in range(n_chunks):
+            part = raw[c * DUMP_CHUNK:(c + 1) * DUMP_CHUNK]
+            sums[c] = np.dot(part.astype(np.float64), weights[:part.size])
+        files[name + "_chunk_sums"] = sums
+    for fname, arr in files.items():
+        written += arr.nbytes
+        if written > DUMP_LIMIT_BYTES:
+            raise SystemExit("--dump-outputs: %s would pass the limit of %d bytes" % (fname, DUMP_LIMIT_BYTES))
+        np.save(os.path.join(out_dir, fname + ".npy"), arr)
+    return written
+
+
+def sdbg_compact_bytes(eng):
+    """the SdBG bytes of every non-empty lv1 bucket in bucket order, exactly the ranges a caller gets written to .sdbg files
+    (canon.digest_sdbg_buffers hashes the same ranges; what lies between them in the buffer is not output)"""
+    import numpy as np
+    from megahit_amd import canon, lib
+    data = eng.fetch(lib.BUF_SDBG_BYTES, np.uint8)
+    items, tips = eng.fetch(lib.BUF_BUCKET_COUNT, np.uint64), eng.fetch(lib.BUF_BUCKET_TIPS, np.uint64)
+    large, off = eng.fetch(lib.BUF_BUCKET_LARGE, np.uint64), eng.fetch(lib.BUF_BUCKET_OFFSET, np.uint64)
+    wpt = (K + 15) // 16
+    parts = [data[int(off[b]):int(off[b]) + canon.sdbg_bucket_nbytes(int(items[b]), int(tips[b]), int(large[b]), wpt)]
+             for b in np.nonzero(items)[0]]
+    compact = np.concatenate(parts) if parts else np.zeros(0, dtype=np.uint8)
+    return compact, {"bucket_items": items, "bucket_tips": tips, "bucket_large": large}
+
+
+def dump_outputs(eng, engine, res, out_dir):
+    """--dump-outputs: what the last timed step left for its caller, as DIR/<name>.npy (float32 / float64, DUMP_LIMIT_BYTES in
+    all).  read2sdbg / seq2sdbg: the SdBG (bytes of every bucket + the per-bucket item, tip and large-multiplicity counts);
+    count: the solid (k+1)-mer edges + the per-bucket counts; each also writes `totals` (the record counts the step returned).
+    With several ranks: rank 0's share."""
+    import numpy as np
+    from megahit_amd import lib
+    os.makedirs(out_dir, exist_ok=True)
+    r1, r2 = res
+    arrays = {}
+    if engine == "count":
+        arrays["totals"] = np.array([r1.n_items, r1.n_distinct, r1.n_edges, r1.words_per_edge], dtype=np.uint64)
+        arrays["bucket_count"] = eng.fetch(lib.BUF_BUCKET_COUNT, np.uint64)
+        arrays["edges"] = eng.fetch(lib.BUF_EDGES, np.uint32)
+    else:
+        arrays["totals"] = np.array(([r1.n_items, r1.n_solid] if r1 is not None else []) +
+                                    [r2.n_items, r2.n_sdbg, r2.n_tips, r2.n_large, r2.sdbg_bytes], dtype=np.uint64)
+        compact, tables = sdbg_compact_bytes(eng)
+        arrays.update(tables)
+        arrays["sdbg_bytes"] = compact
+    written = 0
+    for name, a in arrays.items():  # the small ones first: written whole; the large output last, sampled if it does not fit
+        written = _dump_array(out_dir, name, a, written)
+    return written
+
+
+def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=5)
+    ap.add_argument("--steps", type=int, default=5, help="timed steps (>= 1)")
     ap.add_argument("--warmup", type=int, default=1)
+    ap.add_argument("--full", action="store_true", help="also measure and check what lies beside the headline figure: CLI runs (e2e), "
+                    "per-kernel times + roofline, parity with the reference's known answer, CPU baseline (a plain run does none of it)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="after the timed steps, write what the last one computed as DIR/<name>.npy")
     ap.add_argument("--reads", type=float, default=10e6, help="reads per GPU (BASELINE configs[1]: 10 M)")
     ap.add_argument("--cpu-sample-reads", type=float, default=1e6)
     ap.add_argument("--no-e2e", action="store_true", help="skip the files-in -> files-out run of the CLI after the timed region")
@@ -391,7 +530,14 @@ def main():
     ap.add_argument("--force-dist", action="store_true", help="run the multi-GPU code path (RCCL collectives) even with one rank")
     ap.add_argument("--engine", choices=["read2sdbg", "count", "seq2sdbg"], default="read2sdbg",
                     help="sub-program to time; read2sdbg is BASELINE.json's metric, the others are reported beside it (1 GPU)")
-    args = ap.parse_args()
+    args = ap.parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return args
+
+
+def main():
+    args = parse_args()
 
     # stdout carries exactly ONE line, the JSON result of rank 0: libraries that chat on stdout (RCCL's version banner,
     # gloo's connection notes) are sent to stderr by pointing fd 1 there for the whole run
@@ -428,13 +574,13 @@ def main():
     # The reference's CPU path on the WHOLE workload of this run (8 of this host's cores, ~95 s at 10 M reads) runs at the very
     # END, alone: started beside the read synthesis, the CLI runs and the GPU driver threads (round 4) it was timed under
     # host contention, which flattered the GPU/CPU ratio.
-    cpu_full_wanted = rank == 0 and world == 1 and args.cpu_full and not args.no_cpu_baseline and args.engine == "read2sdbg" and \
+    cpu_full_wanted = args.full and rank == 0 and world == 1 and args.cpu_full and not args.no_cpu_baseline and args.engine == "read2sdbg" and \
         os.path.exists(os.path.join(ROOT, "oracle", "_ref", "ref_core"))
     # Files in -> files out through the CLI, measured FIRST: mhx_core is a process of its own and is meant to find the GPU
     # as a caller finds it (measured after the timed steps, next to this process's ~100 GB of freshly released HBM, its
     # allocations alone took 0.2 s longer).  Reported in the JSON line at the end.
     e2e_result = None
-    if world == 1 and not args.no_e2e and args.engine == "read2sdbg":
+    if args.full and world == 1 and not args.no_e2e and args.engine == "read2sdbg":
         try:
             e2e_result = end_to_end(n_reads)
         except Exception as ex:
@@ -510,8 +656,9 @@ def main():
     for _ in range(args.warmup):
         res = step()
     barrier()
-    eng.profile(True)
-    eng.profile_reset()
+    if args.full:  # per-kernel times (events around every launch) for the roofline figures: --full only
+        eng.profile(True)
+        eng.profile_reset()
     if use_dist:
         comm.bytes_sent(reset=True)
     t0 = time.perf_counter()
@@ -520,10 +667,14 @@ def main():
     barrier()
     dt = time.perf_counter() - t0
     sent_per_step = comm.bytes_sent() / max(1, args.steps) if use_dist else None  # payload this rank handed to OTHER ranks (what crosses xGMI)
-    stats = eng.profile_get()
-    eng.profile(False)
+    if args.full:
+        stats = eng.profile_get()
+        eng.profile(False)
 
-    parity = output_parity(eng, args.engine, n_reads, world, res) if rank == 0 and world == 1 else None
+    if args.dump_outputs and rank == 0:
+        log("[rank 0] --dump-outputs: %d bytes written to %s" % (dump_outputs(eng, args.engine, res, args.dump_outputs), args.dump_outputs))
+
+    parity = output_parity(eng, args.engine, n_reads, world, res) if args.full and rank == 0 and world == 1 else None
 
     if use_dist:
         import torch.distributed as dist
@@ -534,33 +685,6 @@ def main():
     if rank == 0:
         ms_step = dt / args.steps * 1e3
         value = E * world * args.steps / dt / 1e6
-        # dominant kernel by total time
-        name, ks = max(stats.items(), key=lambda kv: kv[1]["ms"])
-        per_launch_bytes = ks["bytes"] / ks["launches"]
-        per_launch_ms = ks["ms"] / ks["launches"]
-        achieved = per_launch_bytes / per_launch_ms / 1e6  # GB/s
-        traffic, traffic_src = pmc_traffic(name) if n_reads == 10000000 and args.engine == "read2sdbg" and not use_dist else (None, None)
-        copy_gbs = copy_bandwidth(torch)
-        roof = {"bound": "hbm", "kernel": name, "achieved": round(achieved, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                "frac": round(achieved / HBM_PEAK_GBS, 4), "traffic": traffic, "traffic_source": traffic_src,
-                "copy_kernel_GBs": copy_gbs, "frac_of_copy_kernel": round(achieved / copy_gbs, 4) if copy_gbs else None,
-                "launches_per_step": ks["launches"] // max(1, args.steps), "avg_launch_ms": round(per_launch_ms, 4),
-                "algo_bytes_per_launch": per_launch_bytes,
-                # every kernel of a step together (counter file of the running build, else null): what the step moves through HBM
-                "traffic_per_step_all_kernels": pmc_traffic_per_step() if n_reads == 10000000 and args.engine == "read2sdbg" and not use_dist else None,
-                # the contract's "bound" knows hbm | mfma; the group-by over super-k-mer records is neither: it reads 16 bytes per 3.5 windows and
-                # spends its time on LDS compare-and-swaps and the vector instructions that form the keys (profiles/rNN_pmc_sq.json)
-                "note": ("dominant kernel is the LDS group-by of stage 1 on super-k-mer records: bound by LDS atomics and vector issue, not by HBM — its "
-                         "fraction of the HBM peak says how few bytes it needs, not how well it runs; the HBM-bound kernels of the step are the sort passes "
-                         "(top_kernels)") if name in ("s1_skm_groups", "count_skm_groups") else None,
-                "kernel_ms_per_step": {k2: round(v["ms"] / args.steps, 3) for k2, v in sorted(stats.items(), key=lambda kv: -kv[1]["ms"])},
-                # the same figure for the three kernels with the largest time per step (they are within a few per cent of each
-                # other, and which of them leads changes from box to box): algorithmic GB/s of one launch and its fraction of the peak
-                "top_kernels": [{"kernel": k2, "ms_per_step": round(v["ms"] / args.steps, 3), "launches_per_step": v["launches"] // max(1, args.steps),
-                                 "achieved": round(v["bytes"] / v["ms"] / 1e6, 1) if v["ms"] > 0 else None,
-                                 "frac": round(v["bytes"] / v["ms"] / 1e6 / HBM_PEAK_GBS, 4) if v["ms"] > 0 else None,
-                                 "traffic": pmc_traffic(k2)[0] if n_reads == 10000000 and args.engine == "read2sdbg" and not use_dist else None}
-                                for k2, v in sorted(stats.items(), key=lambda kv: -kv[1]["ms"])[:3]]}
         metric = {"read2sdbg": "M (k+1)-mer edges sorted+counted/sec, sdbg_build k=21",
                   "count": "M (k+1)-mer edges sorted+counted/sec, count k=21 (beside the headline metric)",
                   "seq2sdbg": "M input (k+1)-mer edges/sec, seq2sdbg k=21 (beside the headline metric)"}[args.engine]
@@ -574,9 +698,10 @@ def main():
                           "reads_per_gpu": n_reads, "edges_per_gpu": E, "k": K, "min_count": MIN_COUNT,
                           "s1_plan": eng.last_s1_plan() if args.engine == "read2sdbg" else None,
                           "parallelism": "1 GPU" if not use_dist else
-                          "lv1 buckets over %d GPUs (C++ driver, RCCL ncclSend/ncclRecv all-to-all, marks routed to the read owners)" % world},
-               "roofline": roof,
-               "parity_checked": bool(parity["checked"]) if parity else None, "parity": parity}
+                          "lv1 buckets over %d GPUs (C++ driver, RCCL ncclSend/ncclRecv all-to-all, marks routed to the read owners)" % world}}
+        if args.full:
+            out["roofline"] = roofline(stats, args.steps, n_reads == 10000000 and args.engine == "read2sdbg" and not use_dist, torch)
+            out["parity_checked"], out["parity"] = (bool(parity["checked"]) if parity else None), parity
         if use_dist:
             out["config"]["rank0_bytes_sent_to_other_ranks_per_step"] = int(sent_per_step)
         try:
@@ -599,7 +724,7 @@ def main():
             if r2 is not None:
                 out["config"]["s2_items" if args.engine == "read2sdbg" else "items"] = int(r2.n_items)
                 out["config"]["sdbg_records"] = int(r2.n_sdbg)
-            if not args.no_cpu_baseline and args.engine == "read2sdbg":
+            if args.full and not args.no_cpu_baseline and args.engine == "read2sdbg":
                 try:
                     out["cpu_baseline"] = cpu_baseline(int(args.cpu_sample_reads) // 2 * 2)
                     if cpu_full_wanted:

@@ -1,8 +1,11 @@
 """Run a `megahit_core`-compatible binary on the golden inputs and digest its outputs (test infra)."""
+import contextlib
 import hashlib
 import json
 import os
+import shutil
 import subprocess
+import tempfile
 
 from megahit_amd import canon
 
@@ -11,6 +14,20 @@ GOLD = os.path.join(ROOT, "tests", "golden")
 ORACLE_CORE = os.path.join(ROOT, "oracle", "oracle_core")
 REF_CORE = os.path.join(ROOT, "oracle", "_ref", "ref_core")
 MHX_CORE = os.path.join(ROOT, "megahit_amd", "mhx_core")
+
+
+@contextlib.contextmanager
+def socket_dir():
+    """A fresh directory whose path leaves room for a Unix socket name (sun_path holds 107 bytes; pytest's tmp_path under a
+    long $TMPDIR does not), removed afterwards."""
+    base = tempfile.gettempdir()
+    if len(base) > 40 and os.access("/tmp", os.W_OK):
+        base = "/tmp"
+    d = tempfile.mkdtemp(prefix="mhx", dir=base)
+    try:
+        yield d
+    finally:
+        shutil.rmtree(d, ignore_errors=True)
 
 
 def cases():

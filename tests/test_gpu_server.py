@@ -13,9 +13,15 @@ pytestmark = pytest.mark.gpu
 
 
 @pytest.fixture(scope="module")
-def server(tmp_path_factory):
+def sock_dir():
+    with gu.socket_dir() as d:
+        yield d
+
+
+@pytest.fixture(scope="module")
+def server(tmp_path_factory, sock_dir):
     d = tmp_path_factory.mktemp("srv")
-    sock = str(d / "mhx.sock")
+    sock = os.path.join(sock_dir, "mhx.sock")
     log = open(str(d / "server.log"), "w")
     p = subprocess.Popen([gu.MHX_CORE, "--serve", sock], stdout=subprocess.DEVNULL, stderr=log, env=dict(os.environ, MHX_SERVE_IDLE_S="60"))
     for _ in range(500):
@@ -67,7 +73,7 @@ def test_the_work_really_ran_in_the_server(tmp_path, server, monkeypatch):
     assert "server: totals since its start" in p.stderr
 
 
-def test_under_the_references_name_the_server_is_the_default(tmp_path, monkeypatch):
+def test_under_the_references_name_the_server_is_the_default(tmp_path, monkeypatch, sock_dir):
     """megahit_core -> mhx_core (how an unmodified orchestrator finds us): no environment variable, and the first sub-program starts
     the resident server (one per user and device, in $XDG_RUNTIME_DIR), the second finds it; the outputs stay the reference's;
     a request whose chained-scan sort gives up (test hook) is run again with the classic passes inside the server; MHX_SERVER=off
@@ -76,10 +82,12 @@ def test_under_the_references_name_the_server_is_the_default(tmp_path, monkeypat
     if not os.path.exists(drop_in):
         os.symlink("mhx_core", drop_in)
     monkeypatch.delenv("MHX_SERVER", raising=False)
-    monkeypatch.setenv("XDG_RUNTIME_DIR", str(tmp_path))
+    rt = os.path.join(sock_dir, "rt")
+    os.mkdir(rt)
+    monkeypatch.setenv("XDG_RUNTIME_DIR", rt)
     monkeypatch.setenv("MHX_SERVE_IDLE_S", "60")
     sock = subprocess.run([gu.MHX_CORE, "--default-socket"], stdout=subprocess.PIPE, text=True, check=True).stdout.strip()
-    assert os.path.dirname(sock) == str(tmp_path)
+    assert os.path.dirname(sock) == rt
     ents = [e for e in gu.cases() if e["case"]["k"] == 21 and e["case"].get("lib") == "hc" and not e["case"].get("input")][:3]
     try:
         for i, ent in enumerate(ents + ents[:1]):

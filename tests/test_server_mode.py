@@ -23,8 +23,14 @@ def run(args, env, cwd=None):
 
 
 @pytest.fixture
-def server(tmp_path):
-    sock = str(tmp_path / "mhx.sock")
+def sock_dir():
+    with gu.socket_dir() as d:
+        yield d
+
+
+@pytest.fixture
+def server(tmp_path, sock_dir):
+    sock = os.path.join(sock_dir, "mhx.sock")
     log = open(str(tmp_path / "server.log"), "w")
     p = subprocess.Popen([gu.MHX_CORE, "--serve", sock], stdout=subprocess.DEVNULL, stderr=log, env=dict(os.environ, MHX_SERVE_IDLE_S="30"))
     for _ in range(200):
@@ -82,9 +88,9 @@ def test_stop_and_fallback_without_a_server(tmp_path, server):
     assert p.returncode == 0 and os.path.exists(os.path.join(d, "local.bin"))
 
 
-def test_autostart(tmp_path):
+def test_autostart(tmp_path, sock_dir):
     d = str(tmp_path)
-    sock = os.path.join(d, "auto.sock")
+    sock = os.path.join(sock_dir, "auto.sock")
     lib = write_inputs(d)
     env = {"MHX_BUILDLIB_HOST": "1", "MHX_SERVER": sock, "MHX_SERVER_AUTOSTART": "1", "MHX_SERVE_IDLE_S": "20", "MHX_SERVER_LOG": os.path.join(d, "auto.log")}
     try:
@@ -110,7 +116,7 @@ def default_socket(env):
     return subprocess.run([gu.MHX_CORE, "--default-socket"], env=env, stdout=subprocess.PIPE, text=True, check=True).stdout.strip()
 
 
-def test_the_references_name_starts_a_server_of_its_own_accord(tmp_path):
+def test_the_references_name_starts_a_server_of_its_own_accord(tmp_path, sock_dir):
     """megahit_core -> mhx_core: no MHX_SERVER in the environment, and the sub-program still runs in a resident server — started by
     this very call, listening on $XDG_RUNTIME_DIR/mhx-core-<uid>-dev0.sock, readable and writable by its owner only; the same
     call with MHX_SERVER=off, or under the name mhx_core, starts nothing"""
@@ -119,7 +125,7 @@ def test_the_references_name_starts_a_server_of_its_own_accord(tmp_path):
     link = os.path.join(d, "megahit_core")
     os.symlink(gu.MHX_CORE, link)
     lib = write_inputs(d)
-    rt = os.path.join(d, "rt")
+    rt = os.path.join(sock_dir, "rt")
     os.mkdir(rt)
     env = {k: v for k, v in os.environ.items() if not k.startswith("MHX_SERVER")}
     env.update(XDG_RUNTIME_DIR=rt, MHX_BUILDLIB_HOST="1", MHX_SERVE_IDLE_S="20")

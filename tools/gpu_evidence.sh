@@ -24,9 +24,9 @@ python tools/pmc_to_json.py $O/${TAG}_pmc_fetch $O/${TAG}_pmc_write > $O/${TAG}_
 cp $O/${TAG}_pmc_traffic.json profiles/${TAG}_pmc_traffic.json   # so that the bench line below carries the traffic of this very build
 find $O/${TAG}_trace -name '*kernel_stats.csv' -exec cp {} $O/${TAG}_kernel_stats.csv \;
 find $O/${TAG}_trace $O/${TAG}_pmc_fetch $O/${TAG}_pmc_write -type f ! -name '*stats.csv' -delete 2>/dev/null
-timeout 300 python bench.py --engine count --steps 3 --no-e2e > $O/${TAG}_bench_count.json 2> $O/${TAG}_bench_count.err
-timeout 300 python bench.py --engine seq2sdbg --steps 3 --no-e2e > $O/${TAG}_bench_seq2sdbg.json 2> $O/${TAG}_bench_seq2sdbg.err
-timeout 300 python bench.py --force-dist --steps 5 --warmup 2 --no-cpu-baseline --no-e2e > $O/${TAG}_bench_force_dist.json 2> $O/${TAG}_bench_force_dist.err
+timeout 300 python bench.py --full --engine count --steps 3 --no-e2e > $O/${TAG}_bench_count.json 2> $O/${TAG}_bench_count.err
+timeout 300 python bench.py --full --engine seq2sdbg --steps 3 --no-e2e > $O/${TAG}_bench_seq2sdbg.json 2> $O/${TAG}_bench_seq2sdbg.err
+timeout 300 python bench.py --full --force-dist --steps 5 --warmup 2 --no-cpu-baseline --no-e2e > $O/${TAG}_bench_force_dist.json 2> $O/${TAG}_bench_force_dist.err
 cut -c1-300 $O/${TAG}_bench_count.json $O/${TAG}_bench_seq2sdbg.json $O/${TAG}_bench_force_dist.json
 timeout 300 python tools/mercy_prof.py 10e6 > $O/${TAG}_mercy_stage1.json 2> $O/${TAG}_mercy_stage1.err
 timeout 300 python tools/buildlib_bench.py > $O/${TAG}_buildlib.json 2> $O/${TAG}_buildlib.err
@@ -37,7 +37,7 @@ timeout 1200 python tools/config_bench.py meta > $O/${TAG}_bench_meta.json 2> $O
 tail -3 $O/${TAG}_bench_meta.err
 [ -n "$CPU_PID" ] && wait $CPU_PID && cp $O/${TAG}_cpu_fullsize.json profiles/${TAG}_cpu_fullsize.json
 # the headline line last, on a device that the runs above have left (its e2e part starts a resident server first)
-timeout 900 python bench.py > $O/${TAG}_bench.json 2> $O/${TAG}_bench.err
+timeout 900 python bench.py --full > $O/${TAG}_bench.json 2> $O/${TAG}_bench.err
 cat $O/${TAG}_bench.json | cut -c1-2500
 timeout 600 python tools/e2e_routes.py > $O/${TAG}_e2e_routes.json 2> $O/${TAG}_e2e_routes.err
 # the north-star size (BASELINE configs[2]): 100 M reads on one GPU (memory plan), as eight ranks on this device, and one GPU's

@@ -28,10 +28,10 @@ unset MHX_S1_SKM
 cd $R
 cp $O/${TAG}_pmc_traffic.json profiles/${TAG}_pmc_traffic.json
 # the other sub-programs and the multi-GPU code path with one rank
-timeout 300 python bench.py --engine count --steps 5 --warmup 2 --no-cpu-baseline --no-e2e > $O/${TAG}_bench_count.json 2> $O/${TAG}_bench_count.err; echo "count rc=$?"
-timeout 300 python bench.py --engine seq2sdbg --steps 5 --warmup 2 --no-cpu-baseline --no-e2e > $O/${TAG}_bench_seq2sdbg.json 2> $O/${TAG}_bench_seq2sdbg.err; echo "seq2sdbg rc=$?"
-timeout 300 python bench.py --force-dist --steps 5 --warmup 2 --no-cpu-baseline --no-e2e > $O/${TAG}_bench_force_dist.json 2> $O/${TAG}_bench_force_dist.err; echo "dist rc=$?"
-MHX_DIST_SKM=0 timeout 300 python bench.py --force-dist --steps 5 --warmup 2 --no-cpu-baseline --no-e2e > $O/${TAG}_bench_force_dist_prefix.json 2> $O/${TAG}_bench_force_dist_prefix.err; echo "dist prefix rc=$?"
+timeout 300 python bench.py --full --engine count --steps 5 --warmup 2 --no-cpu-baseline --no-e2e > $O/${TAG}_bench_count.json 2> $O/${TAG}_bench_count.err; echo "count rc=$?"
+timeout 300 python bench.py --full --engine seq2sdbg --steps 5 --warmup 2 --no-cpu-baseline --no-e2e > $O/${TAG}_bench_seq2sdbg.json 2> $O/${TAG}_bench_seq2sdbg.err; echo "seq2sdbg rc=$?"
+timeout 300 python bench.py --full --force-dist --steps 5 --warmup 2 --no-cpu-baseline --no-e2e > $O/${TAG}_bench_force_dist.json 2> $O/${TAG}_bench_force_dist.err; echo "dist rc=$?"
+MHX_DIST_SKM=0 timeout 300 python bench.py --full --force-dist --steps 5 --warmup 2 --no-cpu-baseline --no-e2e > $O/${TAG}_bench_force_dist_prefix.json 2> $O/${TAG}_bench_force_dist_prefix.err; echo "dist prefix rc=$?"
 cut -c1-240 $O/${TAG}_bench_count.json $O/${TAG}_bench_seq2sdbg.json $O/${TAG}_bench_force_dist.json $O/${TAG}_bench_force_dist_prefix.json
 # low-complexity reads on every path, libraries of several read lengths, the A/Bs of the round in one process each
 timeout 600 python tools/lowcomplexity_probe.py > $O/${TAG}_lowcomplexity.json 2> $O/${TAG}_lowcomplexity.err; echo "lowcomplexity rc=$?"
@@ -58,7 +58,7 @@ if [ -z "$1" ]; then
   rm -rf /tmp/c2lib
 fi
 # the headline line last (default flags: CPU baseline sample, the reference on the whole workload alone at the end, end to end)
-timeout 900 python bench.py > $O/${TAG}_bench.json 2> $O/${TAG}_bench.err; echo "bench rc=$?"
+timeout 900 python bench.py --full > $O/${TAG}_bench.json 2> $O/${TAG}_bench.err; echo "bench rc=$?"
 cut -c1-2000 $O/${TAG}_bench.json
 # every JSON of the set carries the ids of this build; they all have to agree
 python tools/stamp_build.py stamp $O/${TAG}_*.json $O/${TAG}_*.jsonl > /dev/null
