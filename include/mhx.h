@@ -228,7 +228,11 @@ enum mhx_buffer {
   MHX_BUF_SDBG_RS_LAST_SEL = 33,/* uint32[last_sel_count] */
   MHX_BUF_SDBG_RS_TIP_L2 = 34,  /* rank-only structure over tip */
   MHX_BUF_SDBG_RS_TIP_L1 = 35,
-  MHX_BUF_LIB_RECORDS = 40      /* uint32[]: read-library records (len + packed words per read) of mhx_fastx_to_records */
+  MHX_BUF_LIB_RECORDS = 40,     /* uint32[]: read-library records (len + packed words per read) of mhx_fastx_to_records */
+  /* the unitig graph of mhx_sdbg_unitigs (below), kept in HBM for the graph-cleaning steps */
+  MHX_BUF_UNITIG_VERTICES = 41, /* mhx_unitig_vertex[n_vertices], the reference's vertex order on one thread */
+  MHX_BUF_UNITIG_SEQ = 42,      /* char[n_bases]: every vertex's contig text ('ACGT', before FoldPalindrome), back to back */
+  MHX_BUF_UNITIG_OFFSET = 43    /* uint64[n_vertices + 1]: where vertex v's text starts in MHX_BUF_UNITIG_SEQ */
 };
 /* bytes currently held in a result buffer (0 if absent) */
 uint64_t mhx_buffer_bytes(const mhx_ctx *, int which);
@@ -322,6 +326,29 @@ int mhx_sdbg_build_index(mhx_ctx *, uint32_t k, mhx_sdbg_index_info *out);
  * mhx_sdbg_build_index left in HBM.  Updates MHX_BUF_SDBG_INVALID in place; *n_removed = tips removed (the number the
  * reference logs).  `assemble` calls it with max_tip_len = 2k by default (main_assemble.cpp:143-156). */
 int mhx_sdbg_remove_tips(mhx_ctx *, const mhx_sdbg_index_info *info, int max_tip_len, uint64_t *n_removed);
+/* The unitig graph: UnitigGraph::UnitigGraph (assembly/unitig_graph.cpp:13-138) on the buffers mhx_sdbg_build_index
+ * (+ mhx_sdbg_remove_tips) left in HBM, and the contig text OutputContigs writes (contig_output.cpp:62-119 over
+ * VertexToDNAString, unitig_graph.cpp:357-394).  Vertices in the order the reference builds them on one thread (chains
+ * ascending by min(tail, rc tail), then loops ascending by the smallest edge of the cycle pair), so vertex v is contig
+ * k<k>_<v>.  The text of a vertex is on the strand ToUniqueFormat picks (the one beginning at min(b, rb)): GetLabel(begin)
+ * + W of every edge, k + length characters; palindromes are not folded (FoldPalindrome stays with the writer).
+ * Fails as the reference does when the vertices reach UnitigGraph::kMaxNumVertices (2^32 - 2). */
+#define MHX_UNITIG_LOOP 1u        /* is_looped */
+#define MHX_UNITIG_PALINDROME 2u  /* is_palindrome: b == rb */
+#define MHX_UNITIG_STANDALONE 4u  /* a loop, or in-degree = out-degree = 0 (contig_output.cpp:83-117) */
+typedef struct {
+  uint64_t b, e, rb, re;  /* begin / end edge of strand 0 and of its reverse complement (UnitigGraphVertex::strand_info) */
+  uint64_t total_depth;   /* sum of EdgeMultiplicity over the unitig (a loop counts its end edge twice, unitig_graph.cpp:96-104) */
+  uint32_t length;        /* edges */
+  uint32_t flags;         /* MHX_UNITIG_* */
+} mhx_unitig_vertex;
+typedef struct {
+  uint64_t n_vertices, n_loops;
+  uint64_t n_palindromes; /* palindromic non-loop vertices: the reference's "Graph size without loops: N, palindrome: P" */
+  uint64_t n_standalone;
+  uint64_t n_bases;       /* size of MHX_BUF_UNITIG_SEQ */
+} mhx_unitig_result;
+int mhx_sdbg_unitigs(mhx_ctx *, const mhx_sdbg_index_info *info, mhx_unitig_result *out);
 /* install an SdBG produced elsewhere (e.g. read back from .sdbg.* files: bucket byte ranges back to back) as the handle's
  * current SdBG; the four tables have 65536 entries (starting byte, items, tips, large multiplicities per bucket) */
 int mhx_sdbg_load_bytes(mhx_ctx *, const uint8_t *bytes, uint64_t n_bytes, const uint64_t *bucket_offset, const uint64_t *bucket_items,

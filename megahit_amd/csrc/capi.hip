@@ -857,6 +857,13 @@ int mhx_sdbg_remove_tips(mhx_ctx *c, const mhx_sdbg_index_info *info, int max_ti
     mhx::sdbg_remove_tips(c, info, max_tip_len, n_removed);
   })
 }
+int mhx_sdbg_unitigs(mhx_ctx *c, const mhx_sdbg_index_info *info, mhx_unitig_result *out) {
+  MHX_TRY({
+    MHX_HIP(hipSetDevice(c->device));
+    if (!info || !out) throw mhx::Error("sdbg_unitigs: bad arguments");
+    mhx::sdbg_unitigs(c, info, out);
+  })
+}
 int mhx_sdbg_load_bytes(mhx_ctx *c, const uint8_t *bytes, uint64_t n_bytes, const uint64_t *bucket_offset, const uint64_t *bucket_items,
                         const uint64_t *bucket_tips, const uint64_t *bucket_large) {
   MHX_TRY({

@@ -12,7 +12,9 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <atomic>
 #include <fstream>
+#include <thread>
 #include <sstream>
 
 namespace mhxio {
@@ -676,6 +678,106 @@ int64_t read_contigs(const std::string &fasta, PackedSeqs *pkg, std::vector<uint
   }
   gzclose(f);
   return n_read;
+}
+
+SdbgFiles read_sdbg(const std::string &prefix) {
+  const int NB = 65536;
+  SdbgFiles r;
+  std::ifstream meta(prefix + ".sdbg_info");
+  if (!meta) fatal("Cannot open %s.sdbg_info", prefix.c_str());
+  std::string key;
+  uint64_t num_buckets = 0, num_files = 0;
+  for (int i = 0; i < 4; ++i) {
+    uint64_t v = 0;
+    if (!(meta >> key >> v)) fatal("%s.sdbg_info: bad header", prefix.c_str());
+    if (key == "k") r.k = (uint32_t)v;
+    else if (key == "words_per_tip_label") r.words_per_tip_label = (uint32_t)v;
+    else if (key == "num_buckets") num_buckets = v;
+    else if (key == "num_files") num_files = v;
+  }
+  if (num_buckets != (uint64_t)NB) fatal("%s.sdbg_info: %llu buckets (expected %d)", prefix.c_str(), (unsigned long long)num_buckets, NB);
+  struct Row {
+    uint64_t bid, fid, off, items, tips, large;
+  };
+  std::vector<Row> rows;
+  Row x{};
+  while (meta >> x.bid >> x.fid >> x.off >> x.items >> x.tips >> x.large)
+    if (x.bid < (uint64_t)NB && x.fid < num_files) rows.push_back(x);
+  std::sort(rows.begin(), rows.end(), [](const Row &a, const Row &b) { return a.bid < b.bid; });
+  r.offset.assign(NB, 0);
+  r.items.assign(NB, 0);
+  r.tips.assign(NB, 0);
+  r.large.assign(NB, 0);
+  uint64_t total = 0;
+  for (const Row &w : rows) total += 2 * (w.items + w.large) + 4ull * r.words_per_tip_label * w.tips;
+  r.bytes.resize(total);
+  std::vector<FILE *> fs(num_files, nullptr);
+  uint64_t pos = 0;
+  for (const Row &w : rows) {
+    const uint64_t nb = 2 * (w.items + w.large) + 4ull * r.words_per_tip_label * w.tips;
+    if (!fs[w.fid]) {
+      const std::string p = prefix + ".sdbg." + std::to_string(w.fid);
+      fs[w.fid] = fopen(p.c_str(), "rb");
+      if (!fs[w.fid]) fatal("Cannot open %s", p.c_str());
+    }
+    if (nb && (fseeko(fs[w.fid], (off_t)w.off, SEEK_SET) != 0 || fread(r.bytes.data() + pos, 1, nb, fs[w.fid]) != nb))
+      fatal("%s.sdbg.%llu: short read", prefix.c_str(), (unsigned long long)w.fid);
+    r.offset[w.bid] = pos;
+    r.items[w.bid] = w.items;
+    r.tips[w.bid] = w.tips;
+    r.large[w.bid] = w.large;
+    pos += nb;
+  }
+  for (FILE *f : fs)
+    if (f) fclose(f);
+  // empty buckets start where the next byte would go (the device parser reads no byte of them)
+  uint64_t next = total;
+  for (int b = NB - 1; b >= 0; --b) {
+    if (r.items[b]) next = r.offset[b];
+    else r.offset[b] = next;
+  }
+  return r;
+}
+
+void write_contigs(const std::string &path, uint32_t k, const std::vector<ContigRecord> &recs, int n_threads) {
+  FILE *f = fopen(path.c_str(), "w");
+  if (!f) fatal("Cannot open %s", path.c_str());
+  // blocks of records formatted side by side, written in order, at most `window` blocks of text in memory at a time
+  const size_t n = recs.size(), block = 1 << 14, window = 256;
+  const size_t n_blocks = (n + block - 1) / block;
+  n_threads = std::max(1, std::min<int>(n_threads, 64));
+  std::vector<std::string> text(std::min(n_blocks, window));
+  for (size_t lo = 0; lo < n_blocks; lo += window) {
+    const size_t hi = std::min(n_blocks, lo + window);
+    std::atomic<size_t> next{lo};
+    auto format = [&] {
+      char head[160];
+      for (size_t bi; (bi = next.fetch_add(1)) < hi;) {
+        std::string &t = text[bi - lo];
+        t.clear();
+        for (size_t i = bi * block; i < std::min(n, (bi + 1) * block); ++i) {
+          const ContigRecord &c = recs[i];
+          const int h = snprintf(head, sizeof head, ">k%u_%llu flag=%d multi=%.4f len=%zu\n", k, (unsigned long long)c.id, c.flag, c.multi, c.len);
+          t.append(head, (size_t)h);
+          t.append(c.seq, c.len);
+          t.push_back('\n');
+        }
+      }
+    };
+    std::vector<std::thread> th;
+    for (int i = 1; i < n_threads && (size_t)i < hi - lo; ++i) th.emplace_back(format);
+    format();
+    for (auto &x : th) x.join();
+    for (size_t bi = lo; bi < hi; ++bi) {
+      const std::string &t = text[bi - lo];
+      if (!t.empty() && fwrite(t.data(), 1, t.size(), f) != t.size()) fatal("write error on %s", path.c_str());
+    }
+  }
+  if (fclose(f) != 0) fatal("write error on %s", path.c_str());
+  FILE *inf = fopen((path + ".info").c_str(), "w");
+  if (!inf) fatal("Cannot open %s.info", path.c_str());
+  fprintf(inf, "%lld %lld\n", (long long)n, (long long)n * 28);
+  if (fclose(inf) != 0) fatal("write error on %s.info", path.c_str());
 }
 
 }  // namespace mhxio

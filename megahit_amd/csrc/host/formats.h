@@ -106,4 +106,26 @@ int64_t read_contigs(const std::string &fasta, PackedSeqs *pkg, std::vector<uint
 // bucket lines, is_sorted 0
 void write_edges_unsorted(const std::string &prefix, uint32_t k, uint32_t words_per_edge, const uint32_t *edges, uint64_t n_edges);
 
+// <prefix>.sdbg_info + <prefix>.sdbg.* (sdbg_meta.cpp, sdbg_raw_content.cpp:18-96) -> the bucket byte ranges back to back
+// in bucket-id order with the four 65536-entry tables mhx_sdbg_load_bytes takes
+struct SdbgFiles {
+  uint32_t k = 0, words_per_tip_label = 0;
+  std::vector<uint8_t> bytes;
+  std::vector<uint64_t> offset, items, tips, large;
+};
+SdbgFiles read_sdbg(const std::string &prefix);
+
+// ContigWriter (sequence/io/contig/contig_writer.h): ">k<k>_<id> flag=<f> multi=<m %.4f> len=<n>" records and, when the
+// writer closes, <file>.info = "<contigs> <bases>" where bases = 28 per contig (the reference's operator precedence:
+// `len + (flag & kLoop) ? 28 : 0`)
+struct ContigRecord {
+  uint64_t id;
+  int flag;
+  double multi;
+  const char *seq;
+  size_t len;
+};
+// the records in order, formatted on n_threads threads
+void write_contigs(const std::string &path, uint32_t k, const std::vector<ContigRecord> &recs, int n_threads);
+
 }  // namespace mhxio

@@ -25,6 +25,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <deque>
 #include <map>
 #include <mutex>
 #include <string>
@@ -1206,6 +1207,154 @@ int main_iterate(int argc, char **argv) {
 
 
 
+// ---------------------------------------------------------------------------
+// assemble (reference src/main_assemble.cpp) when its options ask for nothing beyond tip trimming, the unitig graph and
+// contig output: --bubble_level 0 --prune_level 0 --cleaning_rounds 0 (every other option set goes to the reference).
+// The SdBG files are read back into HBM, indexed (mhx_sdbg_build_index), trimmed (mhx_sdbg_remove_tips), turned into the
+// unitig graph and its contig text (mhx_sdbg_unitigs); the host folds palindromes and writes the ContigWriter files.
+void add_assemble_options(Options &o) {  // main_assemble.cpp:66-101
+  o.add("sdbg_name", "s", false, "");
+  o.add("output_prefix", "o", false, "out");
+  o.add("num_cpu_threads", "t", false, "0");
+  o.add("max_tip_len", "", false, "-1");
+  o.add("min_standalone", "", false, "200");
+  o.add("bubble_level", "", false, "2");
+  o.add("merge_len", "", false, "20");
+  o.add("merge_similar", "", false, "0.98");
+  o.add("prune_level", "", false, "2");
+  o.add("disconnect_ratio", "", false, "0.1");
+  o.add("low_local_ratio", "", false, "0.2");
+  o.add("cleaning_rounds", "", false, "5");
+  o.add("min_depth", "", false, "-1");
+  o.add("is_final_round", "", true, "");
+  o.add("output_standalone", "", true, "");
+  o.add("careful_bubble", "", true, "");
+}
+// decided from argv alone, before anything touches HIP (forwarding is an execv)
+bool assemble_on_gpu(int argc, char **argv) {
+  if (getenv("MHX_ASSEMBLE_REF") && atoi(getenv("MHX_ASSEMBLE_REF")) != 0) return false;
+  Options o;
+  add_assemble_options(o);
+  try {
+    o.parse(argc - 1, argv + 1);
+  } catch (std::string &) {
+    return false;  // the reference reports it
+  }
+  if (o.get("sdbg_name").empty()) return false;
+  return atoi(o.get("bubble_level").c_str()) == 0 && atoi(o.get("prune_level").c_str()) == 0 && atoi(o.get("cleaning_rounds").c_str()) == 0;
+}
+void revcomp_ascii(std::string &s) {  // contig_output.cpp:12-42
+  auto comp = [](char c) { return c == 'A' ? 'T' : c == 'C' ? 'G' : c == 'G' ? 'C' : 'A'; };
+  std::reverse(s.begin(), s.end());
+  for (char &c : s) c = comp(c);
+}
+void fold_palindrome(std::string &s, unsigned k, bool is_loop) {  // contig_output.cpp:43-60
+  if (is_loop) {
+    for (unsigned i = 1; i + k <= s.length(); ++i) {
+      std::string rc = s.substr(i, k);
+      revcomp_ascii(rc);
+      if (rc == s.substr(i - 1, k)) {
+        s = s.substr(i, s.length() / 2);
+        break;
+      }
+    }
+  } else {
+    const long num_edges = (long)s.length() - (long)k;
+    s.resize((size_t)((num_edges - 1) / 2 + k + 1));
+  }
+}
+int main_assemble(int argc, char **argv) {
+  Options o;
+  add_assemble_options(o);
+  try {
+    o.parse(argc, argv);
+    if (o.get("sdbg_name").empty()) throw std::string("no succinct de Bruijn graph name!");
+  } catch (std::string &e) {
+    fprintf(stderr, "%s\nUsage: %s -s sdbg_name -o output_prefix\noptions:\n", e.c_str(), argv[0]);
+    o.usage();
+    quit(1);
+  }
+  const std::string prefix = o.get("output_prefix");
+  const int n_threads = num_threads_or_all(atoi(o.get("num_cpu_threads").c_str()));
+  const int min_standalone = atoi(o.get("min_standalone").c_str());
+  const bool output_standalone = o.get("output_standalone") == "1";
+  Timer t;
+  info("Loading succinct de Bruijn graph: %s", o.get("sdbg_name").c_str());
+  const mhxio::SdbgFiles f = mhxio::read_sdbg(o.get("sdbg_name"));
+  mhx_ctx *c = open_gpu();
+  CK(mhx_sdbg_load_bytes(c, f.bytes.data(), f.bytes.size(), f.offset.data(), f.items.data(), f.tips.data(), f.large.data()));
+  mhx_sdbg_index_info ix{};
+  CK(mhx_sdbg_build_index(c, f.k, &ix));
+  info("Done. Time elapsed: %.4f", t.lap());
+  info("Number of Edges: %llu; K value: %u", (unsigned long long)ix.n_items, f.k);
+  info("Number of CPU threads: %d", n_threads);
+  int max_tip_len = atoi(o.get("max_tip_len").c_str());
+  if (max_tip_len == -1) max_tip_len = (int)f.k * 2;
+  if (max_tip_len > 0) {
+    uint64_t n_tips = 0;
+    CK(mhx_sdbg_remove_tips(c, &ix, max_tip_len, &n_tips));
+    info("Removing tips with length less than %d; Accumulated tips removed: %llu", max_tip_len, (unsigned long long)n_tips);
+    info("Tips removal done! Time elapsed(sec): %.3f", t.lap());
+  }
+  mhx_unitig_result ur{};
+  CK(mhx_sdbg_unitigs(c, &ix, &ur));
+  info("Graph size without loops: %llu, palindrome: %llu", (unsigned long long)(ur.n_vertices - ur.n_loops), (unsigned long long)ur.n_palindromes);
+  info("unitig graph size: %llu, time for building: %.3f", (unsigned long long)ur.n_vertices, t.lap());
+  const std::vector<mhx_unitig_vertex> vtx = fetch<mhx_unitig_vertex>(c, MHX_BUF_UNITIG_VERTICES);
+  const std::vector<char> seq = fetch<char>(c, MHX_BUF_UNITIG_SEQ);
+  const std::vector<uint64_t> off = fetch<uint64_t>(c, MHX_BUF_UNITIG_OFFSET);
+  {  // CalcAndPrintStat (contig_stat.h:15-47): contig lengths = length + k; std::map order of the names
+    std::map<uint64_t, uint64_t> hist;
+    uint64_t total = 0, n_looped = 0, n_isolated = 0;
+    for (const mhx_unitig_vertex &v : vtx) {
+      ++hist[v.length + f.k];
+      total += v.length + f.k;
+      n_looped += (v.flags & MHX_UNITIG_LOOP) != 0;
+      n_isolated += (v.flags & MHX_UNITIG_STANDALONE) != 0;
+    }
+    uint64_t n50 = 0;
+    double acc = 0;
+    for (auto it = hist.rbegin(); it != hist.rend(); ++it) {
+      acc += (double)it->second * (double)it->first;
+      if (acc >= 0.5 * (double)total) {
+        n50 = it->first;
+        break;
+      }
+    }
+    info("Max: %llu, Min: %llu, N50: %llu, number contigs: %llu, number isolated: %llu, number looped: %llu, total size: %llu, ",
+         (unsigned long long)(hist.empty() ? 0 : hist.rbegin()->first), (unsigned long long)(hist.empty() ? 0 : hist.begin()->first),
+         (unsigned long long)n50, (unsigned long long)vtx.size(), (unsigned long long)n_isolated, (unsigned long long)n_looped, (unsigned long long)total);
+  }
+  // OutputContigs (contig_output.cpp:62-119) with ContigWriter's record format
+  std::vector<mhxio::ContigRecord> main_recs, final_recs;
+  std::deque<std::string> folded;
+  for (uint64_t i = 0; i < vtx.size(); ++i) {
+    const mhx_unitig_vertex &v = vtx[i];
+    const double multi = std::min(65535.0, (double)v.total_depth / v.length);  // kMaxMul
+    mhxio::ContigRecord r{i, 0, multi, seq.data() + off[i], (size_t)(off[i + 1] - off[i])};
+    const bool loop = v.flags & MHX_UNITIG_LOOP, pal = v.flags & MHX_UNITIG_PALINDROME;
+    if (loop || (v.flags & MHX_UNITIG_STANDALONE)) {
+      r.flag = loop && !pal ? 3 : 1;  // kLoop | kStandalone, or kStandalone
+      if (pal) {
+        folded.emplace_back(r.seq, r.len);
+        fold_palindrome(folded.back(), f.k, loop);
+        r.seq = folded.back().data();
+        r.len = folded.back().size();
+      }
+      if (output_standalone) {
+        if (r.len >= (size_t)std::max(0, min_standalone)) final_recs.push_back(r);
+        continue;
+      }
+    }
+    main_recs.push_back(r);
+  }
+  mhxio::write_contigs(prefix + ".contigs.fa", f.k, main_recs, n_threads);
+  mhxio::write_contigs(prefix + ".final.contigs.fa", f.k, final_recs, n_threads);
+  mhxio::write_contigs(prefix + ".bubble_seq.fa", f.k, {}, 1);  // no cleaning round: no bubble
+  info("Time to output: %.4f", t.lap());
+  return finish(c);
+}
+
 // route one sub-program (argv[0] = program name, argv[1] = sub-program); only the ones this binary implements
 int dispatch(int argc, char **argv) {
   const std::string sub = argv[1];
@@ -1215,6 +1364,7 @@ int dispatch(int argc, char **argv) {
   if (sub == "seq2sdbg") return main_seq2sdbg(argc - 1, argv + 1);
   if (sub == "buildlib") return main_buildlib(argc - 1, argv + 1);
   if (sub == "iterate") return main_iterate(argc - 1, argv + 1);
+  if (sub == "assemble") return main_assemble(argc - 1, argv + 1);
   fatal("sub-program '%s' is not served", sub.c_str());
 }
 
@@ -1601,7 +1751,7 @@ int main(int argc, char **argv) {
   }
   const std::string sub = argv[1];
   const bool ours = sub == "count" || sub == "read2sdbg" || sub == "seq2sdbg" || (sub == "buildlib" && !getenv("MHX_BUILDLIB_REF")) ||
-                    (sub == "iterate" && !getenv("MHX_ITERATE_REF"));
+                    (sub == "iterate" && !getenv("MHX_ITERATE_REF")) || (sub == "assemble" && assemble_on_gpu(argc, argv));
   if (ours && g_num_gpus == 1) {
     const int st = try_server(argc, argv);
     if (st >= 0) return st;

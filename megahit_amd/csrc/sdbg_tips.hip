@@ -6,186 +6,9 @@
 // updated MHX_BUF_SDBG_INVALID bit vector (+ the number of tips removed) — the first graph-cleaning pass of `assemble`
 // without the graph ever leaving the GPU.  rank / select are answered from the reference-layout tables (l2 + l1 +
 // in-interval popcounts; select = binary search over the intervals between two select samples, then a word scan).
-#include "dev_prims.h"
-#include "mhx_internal.h"
+#include "sdbg_nav.h"
 
 namespace mhx {
-
-struct DevSdbg {
-  const unsigned long long *w, *last, *tip;
-  unsigned long long *invalid;
-  uint64_t n;
-  const long long *w_l2;      // [9][num_l2_w]
-  const uint16_t *w_l1;       // [9][num_l1_w]
-  const uint32_t *w_sel;      // concatenated, offsets w_sel_off[c]
-  const long long *last_l2;
-  const uint16_t *last_l1;
-  const uint32_t *last_sel;
-  uint64_t num_l1_w, num_l2_w, num_l1_b, num_l2_b;
-  uint64_t w_sel_off[10];
-  uint64_t w_count[9], last_count;
-  long long f[6], rank_f[6];
-};
-constexpr uint64_t kNull = ~0ull;
-
-__device__ __forceinline__ unsigned sd_w(const DevSdbg &g, uint64_t x) { return (unsigned)(g.w[x >> 4] >> (4 * (x & 15))) & 15u; }
-__device__ __forceinline__ bool sd_bit(const unsigned long long *v, uint64_t x) { return (v[x >> 6] >> (x & 63)) & 1ull; }
-__device__ __forceinline__ bool sd_last_or_tip(const DevSdbg &g, uint64_t x) { return ((g.last[x >> 6] | g.tip[x >> 6]) >> (x & 63)) & 1ull; }
-__device__ __forceinline__ bool sd_valid(const DevSdbg &g, uint64_t x) { return !sd_bit(g.invalid, x); }
-
-__device__ __forceinline__ unsigned nib_count(unsigned long long x, unsigned c) {  // nibbles of x equal to c
-  unsigned long long y = x ^ ~(0x1111111111111111ull * (unsigned long long)c);
-  y &= y >> 2;
-  y &= y >> 1;
-  return (unsigned)__builtin_popcountll(y & 0x1111111111111111ull);
-}
-// occurrences of character c in W[0 .. pos]  (RankAndSelect::rank(c, pos), kmrns.h:177-183)
-__device__ uint64_t sd_rank_w(const DevSdbg &g, unsigned c, uint64_t pos) {
-  const uint64_t itv = (pos + 1) >> 8;  // 256 items per level-1 interval
-  uint64_t r = (uint64_t)g.w_l2[c * g.num_l2_w + (itv >> 6)] + g.w_l1[c * g.num_l1_w + itv];
-  const uint64_t first = itv << 8, cnt = pos + 1 - first;  // items first .. pos
-  const uint64_t w0 = first >> 4;
-  uint64_t full = cnt >> 4;
-  for (uint64_t i = 0; i < full; ++i) r += nib_count(g.w[w0 + i], c);
-  const unsigned rem = (unsigned)(cnt & 15);
-  if (rem) {
-    // count only the low `rem` nibbles: make the others differ from every c by a per-nibble mask
-    unsigned long long x = g.w[w0 + full], y = x ^ ~(0x1111111111111111ull * (unsigned long long)c);
-    y &= y >> 2;
-    y &= y >> 1;
-    r += (unsigned)__builtin_popcountll(y & 0x1111111111111111ull & ((1ull << (4 * rem)) - 1));
-  }
-  return r;
-}
-// ones in last[0 .. pos]
-__device__ uint64_t sd_rank_last(const DevSdbg &g, uint64_t pos) {
-  const uint64_t itv = (pos + 1) >> 10;  // 1024 bits per level-1 interval
-  uint64_t r = (uint64_t)g.last_l2[itv >> 6] + g.last_l1[itv];
-  const uint64_t first = itv << 10, cnt = pos + 1 - first;
-  const uint64_t w0 = first >> 6;
-  const uint64_t full = cnt >> 6;
-  for (uint64_t i = 0; i < full; ++i) r += (uint64_t)__builtin_popcountll(g.last[w0 + i]);
-  const unsigned rem = (unsigned)(cnt & 63);
-  if (rem) r += (uint64_t)__builtin_popcountll(g.last[w0 + full] & ((1ull << rem) - 1));
-  return r;
-}
-// position of the (k+1)-th one of last (k 0-based); n if k == #ones  (RankAndSelect::select, kmrns.h:185-191,282-320)
-__device__ uint64_t sd_select_last(const DevSdbg &g, uint64_t k) {
-  if (k > g.last_count) return kNull;
-  if (k == g.last_count) return g.n;
-  uint64_t lo = g.last_sel[k >> 12], hi = g.last_sel[(k + 4095) >> 12];
-  auto occ = [&](uint64_t i) -> uint64_t { return (uint64_t)g.last_l2[i >> 6] + g.last_l1[i]; };
-  while (hi > lo) {  // largest interval whose start count is <= k
-    const uint64_t mid = (lo + hi + 1) >> 1;
-    if (occ(mid) > k) hi = mid - 1;
-    else lo = mid;
-  }
-  uint64_t remain = k + 1 - occ(lo);
-  uint64_t wi = (lo << 10) >> 6;
-  for (;; ++wi) {
-    const unsigned pc = (unsigned)__builtin_popcountll(g.last[wi]);
-    if (pc >= remain) break;
-    remain -= pc;
-  }
-  unsigned long long x = g.last[wi];
-  for (uint64_t t = 1; t < remain; ++t) x &= x - 1;  // drop the lowest remain-1 ones
-  return (wi << 6) + (uint64_t)__builtin_ctzll(x);
-}
-// position of the (k+1)-th occurrence of character c in W
-__device__ uint64_t sd_select_w(const DevSdbg &g, unsigned c, uint64_t k) {
-  if (k > g.w_count[c]) return kNull;
-  if (k == g.w_count[c]) return g.n;
-  const uint32_t *sel = g.w_sel + g.w_sel_off[c];
-  uint64_t lo = sel[k >> 12], hi = sel[(k + 4095) >> 12];
-  auto occ = [&](uint64_t i) -> uint64_t { return (uint64_t)g.w_l2[c * g.num_l2_w + (i >> 6)] + g.w_l1[c * g.num_l1_w + i]; };
-  while (hi > lo) {
-    const uint64_t mid = (lo + hi + 1) >> 1;
-    if (occ(mid) > k) hi = mid - 1;
-    else lo = mid;
-  }
-  uint64_t remain = k + 1 - occ(lo);
-  uint64_t wi = (lo << 8) >> 4;
-  unsigned long long y;
-  for (;; ++wi) {
-    y = g.w[wi] ^ ~(0x1111111111111111ull * (unsigned long long)c);
-    y &= y >> 2;
-    y &= y >> 1;
-    y &= 0x1111111111111111ull;
-    const unsigned pc = (unsigned)__builtin_popcountll(y);
-    if (pc >= remain) break;
-    remain -= pc;
-  }
-  for (uint64_t t = 1; t < remain; ++t) y &= y - 1;
-  return (wi << 4) + (uint64_t)(__builtin_ctzll(y) >> 2);
-}
-__device__ __forceinline__ unsigned sd_last_char_of(const DevSdbg &g, uint64_t x) {  // sdbg.h:83-90
-  for (unsigned i = 1; i < 6; ++i)
-    if (g.f[i] > (long long)x) return i - 1;
-  return 6;
-}
-__device__ uint64_t sd_forward(const DevSdbg &g, uint64_t e) {  // sdbg.h:106-113
-  unsigned a = sd_w(g, e);
-  if (a > 4) a -= 4;
-  const uint64_t count_a = sd_rank_w(g, a, e);
-  return sd_select_last(g, (uint64_t)g.rank_f[a] + count_a - 1);
-}
-__device__ uint64_t sd_backward(const DevSdbg &g, uint64_t e) {  // sdbg.h:115-121
-  const unsigned a = sd_last_char_of(g, e);
-  const uint64_t count_a = (e == 0 ? 0 : sd_rank_last(g, e - 1)) - (uint64_t)g.rank_f[a];
-  return sd_select_w(g, a, count_a);
-}
-// ComputeIncomings (sdbg.h:240-283).  mode 0: the in-degree; kMustEq0: -1 as soon as one exists; kUnique: the in-degree,
-// -1 as soon as a second exists, *one = the incoming edge when there is exactly one
-enum { kAny = 0, kMustEq0 = 1, kUnique = 2 };
-__device__ int sd_incomings(const DevSdbg &g, uint64_t e, int mode, uint64_t *one) {
-  if (!sd_valid(g, e)) return -1;
-  const uint64_t first = sd_backward(g, e);
-  const unsigned c = sd_w(g, first);
-  unsigned count_ones = sd_last_or_tip(g, first);
-  int indeg = sd_valid(g, first) ? 1 : 0;
-  if (mode == kMustEq0 && indeg) return -1;
-  if (indeg && one) *one = first;
-  for (uint64_t y = first + 1; count_ones < 5 && y < g.n; ++y) {
-    count_ones += sd_last_or_tip(g, y);
-    const unsigned cur = sd_w(g, y);
-    if (cur == c) break;
-    if (cur == c + 4 && sd_valid(g, y)) {
-      if (mode == kMustEq0) return -1;
-      if (mode == kUnique && indeg == 1) return -1;
-      if (one) *one = y;  // (only meaningful when it stays the single one)
-      ++indeg;
-    }
-  }
-  return indeg;
-}
-// ComputeOutgoings (sdbg.h:294-323)
-__device__ int sd_outgoings(const DevSdbg &g, uint64_t e, int mode, uint64_t *one) {
-  if (!sd_valid(g, e)) return -1;
-  int outdeg = 0;
-  uint64_t next = sd_forward(g, e);
-  do {
-    if (sd_valid(g, next)) {
-      if (mode == kMustEq0) return -1;
-      if (mode == kUnique && outdeg == 1) return -1;
-      if (one) *one = next;
-      ++outdeg;
-    }
-    --next;
-  } while (next != kNull && !sd_last_or_tip(g, next));
-  return outdeg;
-}
-__device__ __forceinline__ bool sd_indeg_zero(const DevSdbg &g, uint64_t e) { return sd_incomings(g, e, kMustEq0, nullptr) == 0; }
-__device__ __forceinline__ bool sd_outdeg_zero(const DevSdbg &g, uint64_t e) { return sd_outgoings(g, e, kMustEq0, nullptr) == 0; }
-__device__ __forceinline__ uint64_t sd_unique_prev(const DevSdbg &g, uint64_t e) {
-  uint64_t r = 0;
-  return sd_incomings(g, e, kUnique, &r) == 1 ? r : kNull;
-}
-__device__ __forceinline__ uint64_t sd_unique_next(const DevSdbg &g, uint64_t e) {
-  uint64_t r = 0;
-  return sd_outgoings(g, e, kUnique, &r) == 1 ? r : kNull;
-}
-__device__ __forceinline__ void bit_set(unsigned long long *v, uint64_t x) { atomicOr(&v[x >> 6], 1ull << (x & 63)); }
-__device__ __forceinline__ void bit_unset(unsigned long long *v, uint64_t x) { atomicAnd(&v[x >> 6], ~(1ull << (x & 63))); }
 
 // RemoveTips, first loop (sdbg_pruning.cpp:150-157): everything that is neither a source nor a sink is ignored
 __global__ void k_tips_init(DevSdbg g, unsigned long long *__restrict__ ignored) {
@@ -259,11 +82,10 @@ __global__ void k_tips_apply(unsigned long long *__restrict__ invalid, unsigned 
   }
 }
 
-int sdbg_remove_tips(mhx_ctx *c, const mhx_sdbg_index_info *info, int max_tip_len, uint64_t *n_removed) {
-  hipStream_t st = c->stream;
+DevSdbg dev_sdbg(mhx_ctx *c, const mhx_sdbg_index_info *info, const char *who) {
   auto buf = [&](int which) -> DevBuf & {
     auto it = c->results.find(which);
-    if (it == c->results.end() || !it->second.p) throw Error("sdbg_remove_tips: run mhx_sdbg_build_index first");
+    if (it == c->results.end() || !it->second.p) throw Error(std::string(who) + ": run mhx_sdbg_build_index first");
     return it->second;
   };
   DevSdbg g{};
@@ -289,6 +111,19 @@ int sdbg_remove_tips(mhx_ctx *c, const mhx_sdbg_index_info *info, int max_tip_le
     g.f[i] = info->f[i];
     g.rank_f[i] = info->rank_f[i];
   }
+  g.tip_l2 = buf(MHX_BUF_SDBG_RS_TIP_L2).as<long long>();
+  g.tip_l1 = buf(MHX_BUF_SDBG_RS_TIP_L1).as<uint16_t>();
+  g.labels = buf(MHX_BUF_SDBG_TIP_LABELS).as<uint32_t>();
+  g.lkt = buf(MHX_BUF_SDBG_PREFIX_LKT).as<long long>();
+  g.mul = buf(MHX_BUF_SDBG_MUL).as<uint16_t>();
+  g.k = info->k;
+  g.wpt = info->words_per_tip_label;
+  return g;
+}
+
+int sdbg_remove_tips(mhx_ctx *c, const mhx_sdbg_index_info *info, int max_tip_len, uint64_t *n_removed) {
+  hipStream_t st = c->stream;
+  DevSdbg g = dev_sdbg(c, info, "sdbg_remove_tips");
   if (n_removed) *n_removed = 0;
   if (!g.n || max_tip_len <= 0) return 0;
   const uint64_t nw = div_ceil(g.n, 64);

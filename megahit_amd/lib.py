@@ -32,6 +32,13 @@ BUF_SORTED_ITEMS = 12
  BUF_SDBG_RS_TIP_L1) = range(20, 36)
 BUF_W_COUNT = 13
 BUF_LIB_RECORDS = 40
+BUF_UNITIG_VERTICES = 41
+BUF_UNITIG_SEQ = 42
+BUF_UNITIG_OFFSET = 43
+UNITIG_LOOP, UNITIG_PALINDROME, UNITIG_STANDALONE = 1, 2, 4
+# one mhx_unitig_vertex (include/mhx.h)
+UNITIG_VERTEX_DTYPE = np.dtype([("b", np.uint64), ("e", np.uint64), ("rb", np.uint64), ("re", np.uint64), ("total_depth", np.uint64),
+                                ("length", np.uint32), ("flags", np.uint32)])
 
 
 class MhxError(RuntimeError):
@@ -72,6 +79,11 @@ class SdbgIndexInfo(C.Structure):
                 ("num_l1_bits", C.c_uint64), ("num_l2_bits", C.c_uint64), ("w_char_count", C.c_uint64 * 9),
                 ("w_sel_offset", C.c_uint64 * 10), ("ones_in_last", C.c_uint64), ("ones_in_tip", C.c_uint64),
                 ("last_sel_count", C.c_uint64), ("f", C.c_longlong * 6), ("rank_f", C.c_longlong * 6)]
+
+
+class UnitigResult(C.Structure):
+    _fields_ = [("n_vertices", C.c_uint64), ("n_loops", C.c_uint64), ("n_palindromes", C.c_uint64), ("n_standalone", C.c_uint64),
+                ("n_bases", C.c_uint64)]
 
 
 class DistItems(C.Structure):
@@ -131,6 +143,7 @@ SYMBOLS = {
     "mhx_sdbg_build_index": (C.c_int, [_P, C.c_uint32, C.POINTER(SdbgIndexInfo)]),
     "mhx_sdbg_load_bytes": (C.c_int, [_P, _P, C.c_uint64, _P, _P, _P, _P]),
     "mhx_sdbg_remove_tips": (C.c_int, [_P, C.POINTER(SdbgIndexInfo), C.c_int, _P]),
+    "mhx_sdbg_unitigs": (C.c_int, [_P, C.POINTER(SdbgIndexInfo), C.POINTER(UnitigResult)]),
     "mhx_comm_unique_id": (C.c_int, [_P]),
     "mhx_comm_init_rank": (_P, [_P, _P, C.c_int, C.c_int]),
     "mhx_comm_local_group": (C.c_int, [C.c_int, _P, _P]),
@@ -388,6 +401,20 @@ class Engine:
         n = C.c_uint64(0)
         self._chk(self.lib.mhx_sdbg_remove_tips(self.h, C.byref(info), int(max_tip_len), C.byref(n)))
         return int(n.value)
+
+    def sdbg_unitigs(self, info):
+        """The unitig graph of the device-resident graph (include/mhx.h: mhx_sdbg_unitigs); returns a UnitigResult.  The
+        vertices (UNITIG_VERTEX_DTYPE), the contig text and its offsets stay on the device: BUF_UNITIG_*."""
+        r = UnitigResult()
+        self._chk(self.lib.mhx_sdbg_unitigs(self.h, C.byref(info), C.byref(r)))
+        return r
+
+    def unitig_contigs(self):
+        """-> (vertices as a UNITIG_VERTEX_DTYPE array, list of contig strings) of the last sdbg_unitigs call."""
+        v = self.fetch(BUF_UNITIG_VERTICES, np.uint8).view(UNITIG_VERTEX_DTYPE)
+        seq = self.fetch(BUF_UNITIG_SEQ, np.uint8).tobytes().decode()
+        off = self.fetch(BUF_UNITIG_OFFSET, np.uint64)
+        return v, [seq[off[i]:off[i + 1]] for i in range(v.size)]
 
     def sdbg_load_bytes(self, data, offset, items, tips, large):
         data = np.ascontiguousarray(data, dtype=np.uint8)

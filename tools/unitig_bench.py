@@ -1,0 +1,78 @@
+"""The unitig graph at bench size: 10 M x 150 bp PE reads of one genome (2.5 bp per read, 0.5 % errors: the bench.py
+workload family, synth.gen_shard_library), graph by `mhx_core read2sdbg -k 21 -m 2`, then `mhx_core assemble
+--bubble_level 0 --prune_level 0 --cleaning_rounds 0` with MHX_PROFILE=1 (per-kernel times of links / ranking / vertices /
+text), and the reference's `megahit_core assemble` on the same graph at -t 1 and -t 16: wall times and the digest of
+.contigs.fa (equal to ours at -t 1).  Too slow for the suite.  One JSON line on stdout.
+
+    python tools/unitig_bench.py [--reads 10000000] [--ref oracle/_ref/ref_megahit_core] [--ref-threads 1,16] [--workdir DIR]"""
+import argparse
+import hashlib
+import json
+import os
+import re
+import subprocess
+import sys
+import tempfile
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+from megahit_amd import synth  # noqa: E402
+
+MHX_CORE = os.path.join(ROOT, "megahit_amd", "mhx_core")
+QUAL = ["--bubble_level", "0", "--prune_level", "0", "--cleaning_rounds", "0"]
+
+
+def md5(path):
+    h = hashlib.md5()
+    with open(path, "rb") as f:
+        for chunk in iter(lambda: f.read(1 << 24), b""):
+            h.update(chunk)
+    return h.hexdigest()
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--reads", type=int, default=10_000_000)
+    ap.add_argument("--k", type=int, default=21)
+    ap.add_argument("--ref", default=os.path.join(ROOT, "oracle", "_ref", "ref_megahit_core"))
+    ap.add_argument("--ref-threads", default="1,16")
+    ap.add_argument("--workdir", default=None)
+    a = ap.parse_args()
+    d = a.workdir or tempfile.mkdtemp(prefix="mhx_unitig")
+    os.makedirs(d, exist_ok=True)
+    res = {"reads": a.reads, "k": a.k}
+    _, blocks = synth.gen_shard_library(a.reads, 1, 1001)
+    synth.write_read_lib(os.path.join(d, "reads"), blocks)
+    g = os.path.join(d, "g")
+    subprocess.run([MHX_CORE, "read2sdbg", "-k", str(a.k), "-m", "2", "--host_mem", "2e10", "--num_cpu_threads", "16", "--read_lib_file",
+                    os.path.join(d, "reads"), "--output_prefix", g], check=True, stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL)
+    env = dict(os.environ, MHX_PROFILE="1", MHX_SERVER="off")
+    t0 = time.time()
+    p = subprocess.run([MHX_CORE, "assemble", "-s", g, "-o", os.path.join(d, "mine"), "-t", "16"] + QUAL, env=env, stdout=subprocess.DEVNULL,
+                       stderr=subprocess.PIPE, text=True, check=True)
+    res["mhx_wall_s"] = round(time.time() - t0, 3)
+    res["kernels_ms"] = {m.group(1): float(m.group(2)) for m in re.finditer(r"profile (\S+)\s+\d+ launches\s+([\d.]+) ms", p.stderr)}
+    res["log"] = [l for l in p.stderr.splitlines() if re.search(r"Edges|Tips|unitig graph size|palindrome|Max:|output", l)]
+    res["mhx_digest"] = md5(os.path.join(d, "mine.contigs.fa"))
+    if os.path.exists(a.ref):
+        for t in [int(x) for x in a.ref_threads.split(",") if x]:
+            out = os.path.join(d, "ref_t%d" % t)
+            t0 = time.time()
+            q = subprocess.run([a.ref, "assemble", "-s", g, "-o", out, "-t", str(t)] + QUAL, stdout=subprocess.DEVNULL, stderr=subprocess.PIPE,
+                               text=True, check=True)
+            res["ref_t%d_wall_s" % t] = round(time.time() - t0, 3)
+            m = re.search(r"unitig graph size: \d+, time for building: ([\d.]+)", q.stderr)
+            res["ref_t%d_unitig_s" % t] = float(m.group(1)) if m else None
+            m = re.search(r"Tips removal done! Time elapsed\(sec\): ([\d.]+)", q.stderr)
+            res["ref_t%d_tips_s" % t] = float(m.group(1)) if m else None
+            m = re.search(r"Time to output: ([\d.]+)", q.stderr)
+            res["ref_t%d_output_s" % t] = float(m.group(1)) if m else None
+            if t == 1:
+                res["ref_t1_digest"] = md5(out + ".contigs.fa")
+                res["digest_equal"] = res["ref_t1_digest"] == res["mhx_digest"]
+    print(json.dumps(res))
+
+
+if __name__ == "__main__":
+    main()
