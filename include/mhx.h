@@ -62,7 +62,8 @@ int mhx_synchronize(mhx_ctx *);
  *                     bucket at most — 16 prefix bits in two passes up to that, 2^s sub-rounds per bucket up to
  *                     2^s1_stream_sub_max (1) times that, 17..24 bits in three passes beyond (their
  *                     width aims at s1_stream_max3 = s1_stream_max / 2 records per bucket: a third pass costs the same at any width); s1_stream_bits (0) /
- *                     s1_stream_sub0 (-1) force the prefix width / the sub-rounds (tests); s1_stream_fill: keys a
+ *                     s1_stream_sub0 (-1) force the prefix width / the sub-rounds (tests; on several ranks the width is at
+ *                     least 16 bits: the owners' slices are cut at lv1 bucket bounds); s1_stream_fill: keys a
  *                     round's table may end up with before the round is redone in two halves (7/8 of the table); s1_stream_probes (1024; the kernel looks at no more than 128 slots per insert)
  *   s1_filter_in_gen (1)  0: a bucket filter (memory plan) is applied to stage 1 by extraction batches + a keep/drop
  *                     split even where the generating first sort pass could leave the dropped buckets out itself

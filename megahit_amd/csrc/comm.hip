@@ -609,6 +609,11 @@ static void add_result(mhx_sdbg_result &a, const mhx_sdbg_result &b) {
   a.words_per_tip_label = b.words_per_tip_label;
   a.item_words = b.item_words;
 }
+// the density the ranks agreed on holds for one call: cleared on every way out of it, an exception included
+struct ClearDensity {
+  mhx_ctx *c;
+  ~ClearDensity() { c->s1_density = 0; }
+};
 
 }  // namespace mhx
 
@@ -787,6 +792,7 @@ int mhx_dist_read2sdbg(mhx_ctx *c, mhx_comm *cm, uint32_t k, uint32_t min_count,
         cm->all_reduce(mx, true);
         c->s1_density = std::max(1.0, (double)mx[0] * (double)cm->n / (double)MHX_NUM_BUCKETS);
       }
+      const mhx::ClearDensity clear_density{c};
       for (int pass = 0; pass < dp.n; ++pass) {
         mhx::set_pass(c, dp, pass, true);
         mhx_s1_result rp{};
@@ -875,6 +881,7 @@ int mhx_dist_count(mhx_ctx *c, mhx_comm *cm, uint32_t k, uint32_t min_count, mhx
       cm->all_reduce(mx, true);
       c->s1_density = std::max(1.0, (double)mx[0] * (double)cm->n / (double)MHX_NUM_BUCKETS);
     }
+    const mhx::ClearDensity clear_density{c};
     for (int pass = 0; pass < dp.n; ++pass) {
       mhx::set_pass(c, dp, pass, true);
       mhx_count_result rp{};

@@ -320,6 +320,9 @@ S1Plan s1_plan(const mhx_ctx *c, uint32_t k, uint64_t n_items, bool compact, int
       sub0 = std::min(16 + need - pbits, 6);  // (past 24 bits: the rest as sub-rounds; the kernel splits further if it has to)
     }
     if (const long long f = c->opt("s1_stream_bits", 0)) pbits = (int)std::min<long long>(std::max<long long>(f, 9), 24);
+    // several GPUs: the ranks cut each owner's slice of the pre-sorted records at lv1 bucket bounds (comm.hip, k_bucket_bounds
+    // over 16 bits), which are monotone in the array only when it is sorted on at least those 16 bits
+    if (c->n_parts > 1) pbits = std::max(pbits, 16);
     const long long fs = c->opt("s1_stream_sub0", -1);
     if (fs >= 0) sub0 = (int)std::min<long long>(fs, 6);
     pbits = std::min(pbits, kmer_bits);
@@ -454,7 +457,8 @@ struct S1Stage {
     // (records that carry position bits between the (k-1)-mer and head/tail must not be ordered by whole key words)
     tagged_keys = compact && s1_rank_tagged(c, k);
     pos_stride = compact ? s1_pos_stride(c, k) : 0;
-    plan = s1_plan(c, k, n_items, compact, want_mercy);
+    // (an owner that receives no record still makes the plan its senders sorted for: s1_plan declines an empty stage)
+    plan = s1_plan(c, k, pre ? std::max<uint64_t>(n_items, 1) : n_items, compact, want_mercy);
     // pre: the records come pre-sorted by the plan's prefix in several arrays (multi-GPU: one per sending rank, comm.hip);
     // n_items is their total.  Only the bucket-streaming group-by reads them in place; if it gives up, they are gathered and
     // the stage continues as if they had arrived unsorted.
@@ -905,7 +909,7 @@ struct S1Stage {
 int s1_process(mhx_ctx *c, uint32_t k, uint32_t m, int want_mercy, uint32_t *buf_a, uint32_t *buf_b, uint64_t n_items,
                mhx_s1_result *out, const S1Sources *pre) {
   S1Stage stage(c, k, m, want_mercy, buf_a, buf_b, n_items, pre);
-  c->last_s1_plan = s1_plan_text(c, k, n_items);
+  c->last_s1_plan = s1_plan_text(c, k, pre ? std::max<uint64_t>(n_items, 1) : n_items);
   if (c->s1_var_gen) c->last_s1_plan += " [reads of several lengths: " + std::to_string(c->seqs.max_len - k + 4) + " item slots per read on the generating pass]";
   c->s1_var_gen = false;
   stage.sort_records();

@@ -294,6 +294,58 @@ def test_cli_gpus_flag_reproduces_reference(ent, gpus, tmp_path, monkeypatch):
         assert got.get(key) == want, key
 
 
+@pytest.mark.parametrize("ent", [e for e in gu.cases() if e["case"]["prog"] in ("count", "read2sdbg")][:3] +
+                         [e for e in gu.cases() if e["case"]["prog"] == "seq2sdbg" and e["case"].get("input") == "count" and e["case"].get("mercy")][:1],
+                         ids=gu.case_id)
+@pytest.mark.parametrize("gpus", [4, 8])
+def test_cli_gpus_flag_reproduces_reference_wide(ent, gpus, tmp_path, monkeypatch):
+    """`mhx_core --gpus 4 / 8`: the same golden digests with four and eight ranks, all on device 0"""
+    test_cli_gpus_flag_reproduces_reference(ent, gpus, tmp_path, monkeypatch)
+
+
+def test_cli_eight_gpus_on_the_super_kmer_exchange(tmp_path):
+    """`mhx_core --gpus 8` with MHX_S1_SKM=2: stage 1 on super-k-mer records exchanged by bin between eight ranks, the golden digest"""
+    ent = [e for e in gu.cases() if e["case"]["prog"] == "read2sdbg" and not e["case"].get("mercy") and 19 <= e["case"]["k"] <= 22][0]
+    c = ent["case"]
+    env = dict(os.environ, MHX_NUM_GPUS="8", MHX_GPU_MAP=",".join("0" for _ in range(8)), MHX_S1_SKM="2", MHX_S1_SKM_MAX_BIN=str(1 << 30),
+               MHX_S1_VAR_MIN_FILL="5")
+    out = str(tmp_path / "out")
+    p = subprocess.run([gu.MHX_CORE, "read2sdbg", "-k", str(c["k"]), "-m", str(c["m"]), "--read_lib_file", os.path.join(gu.GOLD, c["lib"]),
+                        "--output_prefix", out, "--host_mem", "2e9", "--num_cpu_threads", "3"],
+                       env=env, stdout=subprocess.DEVNULL, stderr=subprocess.PIPE, text=True, timeout=300)
+    assert p.returncode == 0, p.stderr[-2000:]
+    assert "exchanged by bin" in p.stderr, p.stderr[-2000:]
+    assert canon.digest_sdbg(out) == ent["sdbg"]
+
+
+@pytest.mark.parametrize("prog", ["read2sdbg", "count"])
+def test_cli_eight_gpus_on_five_reads(prog, tmp_path, monkeypatch):
+    """five reads over eight ranks: three ranks hold no reads at all (mhx_core shards a library contiguously); against oracle_core"""
+    from megahit_amd import synth
+    d = str(tmp_path)
+    genome = np.random.default_rng(41).integers(0, 4, size=300, dtype=np.uint8)
+    reads = [genome[o:o + 100].copy() for o in (0, 40, 80, 120, 160)]
+    synth.write_fasta(os.path.join(d, "r.fa"), reads)
+    with open(os.path.join(d, "lib"), "w") as f:
+        f.write("five reads\nse %s\n" % os.path.join(d, "r.fa"))
+    lib_ = os.path.join(d, "five")
+    subprocess.run([gu.MHX_CORE, "buildlib", os.path.join(d, "lib"), lib_], check=True, stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL,
+                   env=dict(os.environ, MHX_BUILDLIB_HOST="1"), timeout=120)
+    args = [prog, "-k", "21", "-m", "2", "--read_lib_file", lib_, "--host_mem", "2e9", "--num_cpu_threads", "3"]
+    subprocess.run([gu.ORACLE_CORE] + args + ["--output_prefix", os.path.join(d, "want")], check=True, stdout=subprocess.DEVNULL,
+                   stderr=subprocess.DEVNULL, timeout=120)
+    monkeypatch.setenv("MHX_NUM_GPUS", "8")
+    monkeypatch.setenv("MHX_GPU_MAP", ",".join("0" for _ in range(8)))
+    p = subprocess.run([gu.MHX_CORE] + args + ["--output_prefix", os.path.join(d, "got")], stdout=subprocess.DEVNULL, stderr=subprocess.PIPE,
+                       text=True, timeout=300)
+    assert p.returncode == 0, p.stderr[-2000:]
+    if prog == "count":
+        assert canon.canonical_edges(os.path.join(d, "want"))[1].shape[0] > 0
+        assert canon.digest_edges(os.path.join(d, "got")) == canon.digest_edges(os.path.join(d, "want"))
+    else:
+        assert canon.digest_sdbg(os.path.join(d, "got")) == canon.digest_sdbg(os.path.join(d, "want"))
+
+
 def test_cli_failing_rank_ends_the_process(tmp_path, monkeypatch):
     """a rank that fails before its first collective must not leave the others waiting in a barrier:
     the process ends at once with the rank's message"""

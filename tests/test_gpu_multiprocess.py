@@ -1,4 +1,4 @@
-"""GPU: the C++ multi-GPU drivers with the ranks as separate PROCESSES (world_size 2 and 3, all on cuda:0), the bytes moved by
+"""GPU: the C++ multi-GPU drivers with the ranks as separate PROCESSES (world_size 2 to 5, all on cuda:0), the bytes moved by
 torch.distributed over gloo through libmhx's hosted communicator (include/mhx.h mhx_comm_init_hosted, megahit_amd/hosted.py).
 tests/test_gpu_comm.py runs the same drivers with thread ranks behind the in-process transport; RCCL needs one GPU per rank
 and only runs in the driver's multi-GPU bench.  Every rank's output against the oracle on the concatenated input."""
@@ -83,7 +83,10 @@ def run_world(world, mode, k, m, opts=None):
 @pytest.mark.parametrize("world,k,m,opts", [(2, 21, 2, None), (3, 21, 2, {"dist_max_items": 40000}), (2, 27, 1, None), (2, 21, 2, {"dist_presort": 0}),
                                             # round 6: super-k-mer records exchanged by bin (comm.hip dist_s1_skm), rank processes over the hosted transport
                                             (2, 21, 2, {"s1_skm": 2, "s1_skm_max_bin": 1 << 30, "s1_var_min_fill": 5}),
-                                            (3, 22, 2, {"s1_skm": 2, "s1_skm_max_bin": 1 << 30, "s1_var_min_fill": 5, "s1_stream_fill": 40})])
+                                            (3, 22, 2, {"s1_skm": 2, "s1_skm_max_bin": 1 << 30, "s1_var_min_fill": 5, "s1_stream_fill": 40}),
+                                            # four and five rank processes (at most five with the GPU open besides the parent)
+                                            (4, 21, 2, None), (5, 21, 2, {"s1_skm": 2, "s1_skm_max_bin": 1 << 30, "s1_var_min_fill": 5}),
+                                            (4, 22, 2, {"s1_skm": 2, "s1_skm_max_bin": 1 << 30, "s1_var_min_fill": 5})])
 def test_read2sdbg_rank_processes(world, k, m, opts):
     import oracle_binding as ob
     from dist_inputs import reads_of
@@ -104,9 +107,18 @@ def test_read2sdbg_rank_processes(world, k, m, opts):
 
 
 def test_count_rank_processes():
+    check_count_world(2)
+
+
+@pytest.mark.parametrize("world", [4, 5])
+def test_count_rank_processes_wide(world):
+    check_count_world(world)
+
+
+def check_count_world(world):
     import oracle_binding as ob
     from dist_inputs import reads_of
-    world, k, m = 2, 21, 2
+    k, m = 21, 2
     outs = run_world(world, "count", k, m)
     want = ob.count(ob.Package(sum((reads_of(100 + r, n_pairs=600) for r in range(world)), []), reverse=True), k, m)
     assert np.array_equal(np.concatenate([o["edges"] for o in outs]).reshape(-1, want["wpe"]), want["edges"])

@@ -1,10 +1,11 @@
-"""CPU, world_size 2 and 3 on gloo: the byte movers behind libmhx's hosted communicator (megahit_amd/hosted.py — what the
+"""CPU, world_size 2 to 8 on gloo: the byte movers behind libmhx's hosted communicator (megahit_amd/hosted.py — what the
 multi-GPU drivers of comm.hip call back into when the ranks are processes without a shared RCCL world).  No libmhx compute
 here (that needs a GPU: tests/test_gpu_multiprocess.py runs the same callbacks under mhx_dist_*); this checks the part that
 runs anywhere: the in-place 64-bit reductions (including the "~0 - x" values libmhx max-reduces to find a minimum) and the
 variable-size all-to-all built from point-to-point pairs, with empty and uneven segments."""
 import ctypes as C
 import os
+import socket
 import sys
 
 import numpy as np
@@ -59,11 +60,13 @@ def _worker(rank, world, port, q):
     dist.destroy_process_group()
 
 
-@pytest.mark.parametrize("world", [2, 3])
+@pytest.mark.parametrize("world", [2, 3, 4, 5, 7, 8])  # (odd worlds: no perfect pairing of the peers exists)
 def test_hosted_transport_over_gloo(world):
     ctx = mp.get_context("spawn")
     q = ctx.Queue()
-    port = 29700 + (os.getpid() % 2000)
+    with socket.socket() as s:  # a port no earlier world of this run may still hold
+        s.bind(("127.0.0.1", 0))
+        port = s.getsockname()[1]
     procs = [ctx.Process(target=_worker, args=(r, world, port, q)) for r in range(world)]
     for p in procs:
         p.start()

@@ -1,6 +1,9 @@
-"""Randomised libraries on 2-3 thread ranks through mhx_dist_read2sdbg with the super-k-mer exchange, against the oracle on the union (GPU).
+"""Randomised libraries on 2-9 thread ranks through mhx_dist_read2sdbg with the super-k-mer exchange, against the oracle on the union (GPU).
 
-    python tools/fuzz_skm_dist.py [seconds] [seed]"""
+    python tools/fuzz_skm_dist.py [seconds] [seed]
+
+Sometimes one rank's shard is empty or degenerate (reads shorter than k + 1, a single homopolymer read): such a rank vetoes the
+super-k-mer exchange for every rank, as do nine ranks (more senders than k_s1_skm takes); the job then runs on the pre-sorted exchange."""
 import os
 import sys
 import time
@@ -24,9 +27,14 @@ def main():
     while time.time() - t0 < seconds:
         seed = seed0 + rounds
         rng = np.random.default_rng(seed)
-        world = int(rng.integers(2, 4))
+        world = int(rng.integers(2, 10))
         k = int(rng.integers(19, 23))
         shards = [library(np.random.default_rng(seed * 10 + r)) for r in range(world)]
+        odd = ""
+        if rng.random() < 0.25:  # one empty or degenerate shard
+            r_odd, odd = int(rng.integers(0, world)), str(rng.choice(["empty", "short", "homopolymer"]))
+            shards[r_odd] = {"empty": [], "short": [x[: int(rng.integers(0, k + 1))] for x in shards[r_odd][:50]],
+                             "homopolymer": [np.zeros(int(rng.integers(k + 1, 200)), dtype=np.uint8)]}[odd]
         opts = dict(s1_skm=2, s1_var_min_fill=1, s1_skm_max_bin=1 << 30, s1_skm_cap_pct=400)
         if rng.random() < 0.5:
             opts["s1_skm_bin_bits"] = int(rng.choice([8, 9, 12, 16, 18, 20]))
@@ -59,7 +67,7 @@ def main():
             print("seed %d: world %d k %d %s *** %s | %s" % (seed, world, k, opts, ex, outs[0][6]), flush=True)
             sys.exit(1)
         on_path += outs[0][6].startswith("super-k-mers")
-        print("seed %d: world %d, %d reads, k %d, %s | %s" % (seed, world, sum(len(s) for s in shards), k,
+        print("seed %d: world %d%s, %d reads, k %d, %s | %s" % (seed, world, " (%s shard)" % odd if odd else "", sum(len(s) for s in shards), k,
                                                             " ".join("%s=%d" % kv for kv in sorted(opts.items()) if kv[0] not in ("s1_skm", "s1_var_min_fill", "s1_skm_cap_pct")), outs[0][6][:40]), flush=True)
         rounds += 1
     print("%d rounds, %d on the super-k-mer exchange, all equal to the oracle" % (rounds, on_path))
