@@ -571,12 +571,6 @@ int mhx_reset(mhx_ctx *c) {
     c->agg_valid = false; c->solid_plain_k = 0;
     c->agg_n = 0;
     c->n_route = 0;
-    c->pre_hist_buf = nullptr;
-    // (whatever a failed request left half-way: a deferred first pass, a filter handed to an extraction)
-    c->gen_first_pass = nullptr;
-    c->gen_buf = nullptr;
-    c->gen_n = c->gen_slots = 0;
-    c->s1_defer_items = c->s2_filter_in_extract = c->s1_filter_in_gen = false;
     c->s1_density = 0;
     c->filter_kept = 0;
     c->filter_on = c->accumulate = false;
@@ -923,7 +917,7 @@ int mhx_dist_extract(mhx_ctx *c, int stage, uint32_t k, uint32_t min_count, mhx_
     if (c->work.find("owner_lut") == c->work.end()) throw mhx::Error("dist_extract: call mhx_set_partition first");
     const mhx::StageItems it = mhx::extract_stage(c, stage, k, min_count);
     if (stage == MHX_STAGE_S2) c->dist_s2_agg = it.agg;
-    c->pre_hist_buf = nullptr;  // the items are about to be partitioned and exchanged
+    // (the items are about to be partitioned and exchanged: what the extraction prepared for a sort of them lapses)
     const uint64_t n = it.n;
     const int S = it.S;
     uint32_t *a = c->work["items_a"].as<uint32_t>();
@@ -1089,38 +1083,31 @@ uint64_t mhx_stage_pass_bytes(mhx_ctx *c, int stage, uint32_t k, uint32_t min_co
   // what a pass over n_items (kept) items of `stage` holds on the device besides the stage's fixed state
   try {
     (void)min_count;
+    // (the question is about a filtered pass: asked with the filter fields set, restored whatever happens)
+    struct AsFilteredPass {
+      mhx_ctx *c;
+      bool on;
+      uint64_t exp;
+      AsFilteredPass(mhx_ctx *ctx, uint64_t n) : c(ctx), on(ctx->filter_on), exp(ctx->filter_expected) {
+        c->filter_on = true;
+        c->filter_expected = n;
+      }
+      ~AsFilteredPass() {
+        c->filter_on = on;
+        c->filter_expected = exp;
+      }
+    };
     if (stage == MHX_STAGE_S1 && c->seqs.n_seqs) {
-      // (the question is about a filtered pass: asked with the filter fields set, restored whatever happens)
-      struct Restore {
-        mhx_ctx *c;
-        bool on;
-        uint64_t exp;
-        ~Restore() {
-          c->filter_on = on;
-          c->filter_expected = exp;
-        }
-      } restore{c, c->filter_on, c->filter_expected};
-      c->filter_on = true;
-      c->filter_expected = n_items;
+      const AsFilteredPass filtered(c, n_items);
       const bool gen = mhx::s1_filter_in_gen_applies(c, k);
       // the generating first pass: two 12-byte record buffers, nothing staged, nothing split; its status words walk ALL item slots
       if (gen) return n_items * 24 + n_items / 2 + (c->seqs.n_bases + 4 * c->seqs.n_seqs) / 3;
       return n_items * (3 * (uint64_t)mhx::s1_stride(k, mhx::s1_compact(c, k, 0)) * 4 + 1);
     }
     if (stage == MHX_STAGE_COUNT && c->seqs.n_seqs) {
-      struct Restore {
-        mhx_ctx *c;
-        bool on;
-        uint64_t exp;
-        ~Restore() {
-          c->filter_on = on;
-          c->filter_expected = exp;
-        }
-      } restore{c, c->filter_on, c->filter_expected};
-      c->filter_on = true;
-      c->filter_expected = n_items;
+      const AsFilteredPass filtered(c, n_items);
       // count on the stage-1 design: two 12-byte record buffers (the solid edges and the events live in the spare one)
-      if (mhx::count_stream_applies(c, k, min_count) && (2 * (k + 1) + 16 + 31) / 32 <= 3)
+      if (mhx::count_stream_applies(c, k, min_count, false) && (2 * (k + 1) + 16 + 31) / 32 <= 3)
         return n_items * 24 + n_items / 2 + c->seqs.n_bases / 3;
     }
     // stage 2 from a count of the (k+1)-mers (s2.hip s2_agg_from_count): two 12-byte record buffers per edge occurrence — about one per

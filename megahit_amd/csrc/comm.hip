@@ -330,7 +330,7 @@ __global__ void k_bucket_bounds(const uint32_t *__restrict__ items, uint64_t n, 
 // plan's prefix as one sub-range per sender (k_s1_stream's sources) instead of sorting the received records again.  Replaces: owner histogram + owner scatter + a second histogram + two more passes over the
 // received records (round 2: 91 ms against 53 ms for a single rank).  Returns false (nothing exchanged yet, the extracted
 // items are in ws "items_a") when the plan does not apply on every rank.
-static bool dist_s1_presorted(mhx_ctx *c, mhx_comm *cm, uint32_t k, uint32_t m, const StageItems &it, mhx_s1_result *r1) {
+static bool dist_s1_presorted(mhx_ctx *c, mhx_comm *cm, uint32_t k, uint32_t m, StageItems &it, mhx_s1_result *r1) {
   const int n = cm->n, rank = cm->rank;
   std::vector<uint64_t> v{it.n, it.S == 3 ? 0ull : 1ull};
   cm->all_reduce(v, true);  // the largest local item count decides for everybody; any rank with other records vetoes
@@ -340,7 +340,8 @@ static bool dist_s1_presorted(mhx_ctx *c, mhx_comm *cm, uint32_t k, uint32_t m, 
   uint32_t *b = c->ws("items_b", it.n * 12 + 64).as<uint32_t>();
   // (deferred items: the histograms taken at extraction belong to the plan of the agreed density, the one s1_presort makes)
   int pbits = 16;
-  uint32_t *sorted = s1_presort(c, k, a, b, it.n, &pbits);
+  const bool var_gen = it.prep.gen_var;
+  uint32_t *sorted = s1_presort(c, k, a, b, it.n, &pbits, &it.prep);
   uint64_t *d_bounds = c->ws("dist_bounds", (MHX_NUM_BUCKETS + 2) * 8).as<uint64_t>();
   std::vector<uint64_t> bounds(MHX_NUM_BUCKETS + 1, 0);
   if (it.n) {
@@ -373,7 +374,7 @@ static bool dist_s1_presorted(mhx_ctx *c, mhx_comm *cm, uint32_t k, uint32_t m, 
   // the group-by's output regions: the local ping-pong buffer that does not hold the sorted records, if it is large enough
   uint32_t *other = sorted == a ? b : a;
   src.spare = total <= it.n ? other : c->ws("s1_spare", total * 12 + 64).as<uint32_t>();
-  s1_process(c, k, m, 0, nullptr, nullptr, total, r1, &src);
+  s1_process(c, k, m, 0, nullptr, nullptr, total, r1, &src, nullptr, var_gen);
   c->last_s1_plan += " [pre-sorted exchange]";
   return true;
 }
@@ -399,8 +400,6 @@ static bool dist_s1_skm(mhx_ctx *c, mhx_comm *cm, uint32_t k, uint32_t m, mhx_s1
   if (const long long fb = c->opt("s1_skm_bin_bits", 0)) bin_bits = (int)std::min<long long>(20, std::max<long long>(8, fb));
   hipStream_t st = c->stream;
   SkmFront f{};
-  c->gen_first_pass = nullptr;
-  c->pre_hist_buf = nullptr;
   std::vector<uint64_t> fail{s1_skm_front(c, k, &f, 0, 1, bin_bits) ? 0ull : 1ull};
   cm->all_reduce(fail, true);
   if (fail[0]) {
@@ -802,17 +801,11 @@ int mhx_dist_read2sdbg(mhx_ctx *c, mhx_comm *cm, uint32_t k, uint32_t min_count,
         if (!need_mercy && !done) {
           // (the pre-sort's first pass may make the records itself — and drop those of the buckets a pass leaves out: then
           // "items_a" holds nothing yet — s1.hip, S1GenT)
-          c->gen_first_pass = nullptr;
-          c->s1_defer_items = c->opt("dist_presort", 1) != 0;
-          mhx::StageItems it = mhx::extract_stage(c, MHX_STAGE_S1, k, min_count);
-          c->s1_defer_items = false;
+          mhx::StageItems it = mhx::extract_stage(c, MHX_STAGE_S1, k, min_count, c->opt("dist_presort", 1) != 0);
           done = mhx::dist_s1_presorted(c, cm, k, min_count, it, &rp);
           if (!done) {  // the classic exchange of the items extracted above: owner multisplit, all-to-all, sort at the owner
-            if (c->gen_first_pass) {  // ... which were deferred to a sort that will not happen: make them now
-              c->gen_first_pass = nullptr;
-              it = mhx::extract_stage(c, MHX_STAGE_S1, k, min_count);
-            }
-            c->pre_hist_buf = nullptr;
+            // ... which were deferred to a sort that will not happen: make them now
+            if (it.prep.gen) it = mhx::extract_stage(c, MHX_STAGE_S1, k, min_count);
             mhx_dist_items di{};
             std::vector<uint64_t> counts(cm->n, 0);
             uint32_t *send = c->ws("items_send", it.n * (size_t)it.S * 4 + 64).as<uint32_t>();
@@ -886,8 +879,6 @@ int mhx_dist_count(mhx_ctx *c, mhx_comm *cm, uint32_t k, uint32_t min_count, mhx
       mhx::set_pass(c, dp, pass, true);
       mhx_count_result rp{};
       if (!mhx::dist_count_presorted(c, cm, k, min_count, &rp)) {  // the classic exchange: 16-byte items, owner multisplit, tile path at the owner
-        c->gen_first_pass = nullptr;
-        c->pre_hist_buf = nullptr;
         const uint64_t n = mhx::exchange_stage(c, cm, MHX_STAGE_COUNT, k, min_count);
         MHX_CK(mhx_dist_process_count(c, k, min_count, n, &rp));
       }

@@ -735,8 +735,8 @@ static std::vector<SortPass> count_sort_passes(mhx_ctx *c, uint32_t k, uint32_t 
 }
 
 // items of the local reads -> c->ws("items_a"); returns their number.  m > 0: the caller will sort them for mhx_count with
-// this minimum count, so the digit histograms of that sort can be taken on the way (fixed-length reads)
-uint64_t count_extract(mhx_ctx *c, uint32_t k, uint32_t m) {
+// this minimum count, so the digit histograms of that sort can be taken on the way (fixed-length reads) and are returned in *prep
+uint64_t count_extract(mhx_ctx *c, uint32_t k, uint32_t m, SortPrep *prep) {
   SeqSet &s = c->seqs;
   if (k < 9 || k > MHX_MAX_K) throw Error("count: k out of range [9,255]");
   const int KWv = count_kw(k), S = count_stride(k);
@@ -757,7 +757,7 @@ uint64_t count_extract(mhx_ctx *c, uint32_t k, uint32_t m) {
   }
   const size_t item_bytes = (size_t)S * 4;
   uint32_t *buf_a = c->ws("items_a", n_items * item_bytes + 64).as<uint32_t>();
-  c->pre_hist_buf = nullptr;
+  *prep = SortPrep{};
   if (n_items) {
     const unsigned grid = 256 * 8;
     const bool fixed = s.fixed_len >= k + 1 && n_items == (uint64_t)ns * (s.fixed_len - k) && c->opt("count_extract_fixed", 1) != 0;
@@ -767,14 +767,14 @@ uint64_t count_extract(mhx_ctx *c, uint32_t k, uint32_t m) {
     if (fixed && m > 0) {
       const std::vector<SortPass> passes = count_sort_passes(c, k, m, n_items, nullptr);
       if ((int)passes.size() <= kMaxFusedPasses) {
-        c->pre_hist_sig = passes_signature(passes);
+        prep->hist_sig = passes_signature(passes);
         specs.n = (int)passes.size();
         for (int p = 0; p < specs.n; ++p) specs.d[p] = spec_of_pass(passes[p], KWv);
         pre_hist = c->ws("sort_pre_hist", (size_t)kMaxFusedPasses * 256 * 8).as<unsigned long long>();
         MHX_HIP(hipMemsetAsync(pre_hist, 0, (size_t)specs.n * 256 * 8, st));
-        c->pre_hist_buf = buf_a;
-        c->pre_hist_n = n_items;
-        c->pre_hist_passes = specs.n;
+        prep->buf = buf_a;
+        prep->n = n_items;
+        prep->hist_passes = specs.n;
       }
     }
 #define MHX_CX(SV)                                                                                                               \
@@ -799,7 +799,7 @@ uint64_t count_extract(mhx_ctx *c, uint32_t k, uint32_t m) {
 }
 
 // sort + run reduction of n_items items held in buf_a (buf_b = ping-pong space of the same size)
-int count_process(mhx_ctx *c, uint32_t k, uint32_t m, uint32_t *buf_a, uint32_t *buf_b, uint64_t n_items, mhx_count_result *out) {
+int count_process(mhx_ctx *c, uint32_t k, uint32_t m, uint32_t *buf_a, uint32_t *buf_b, uint64_t n_items, mhx_count_result *out, SortPrep *prep) {
   SeqSet &s = c->seqs;
   const int KWv = count_kw(k), S = count_stride(k);
   const int wpe = (int)div_ceil((k + 1) * 2 + 16, 32);
@@ -811,7 +811,7 @@ int count_process(mhx_ctx *c, uint32_t k, uint32_t m, uint32_t *buf_a, uint32_t 
   int seg_bits = 0;
   const std::vector<SortPass> sort_passes = count_sort_passes(c, k, m, n_items, &seg_bits);
   // (no segment group-by: the whole zero-padded (k+1)-mer is the key; equal keys keep their input order)
-  uint32_t *sorted = seg_bits ? radix_sort(c, buf_a, buf_b, n_items, S, KWv, sort_passes) : sort_whole_key(c, buf_a, buf_b, n_items, S, KWv, sort_passes);
+  uint32_t *sorted = seg_bits ? radix_sort(c, buf_a, buf_b, n_items, S, KWv, sort_passes, prep) : sort_whole_key(c, buf_a, buf_b, n_items, S, KWv, sort_passes, prep);
   uint32_t *spare = sorted == buf_a ? buf_b : buf_a;
 
   c->last_s1_plan = seg_bits ? "count: tile path, segment group-by on " + std::to_string(seg_bits) + " prefix bits" : "count: tile path, full sort";
@@ -1135,14 +1135,12 @@ int count_process_presorted(mhx_ctx *c, uint32_t k, uint32_t m, const S1Sources 
 int run_count(mhx_ctx *c, uint32_t k, uint32_t m, mhx_count_result *out) {
   if (c->global_bases) throw Error("count: the global layout is set; use the mhx_dist_* entry points (or mhx_set_global_layout(0, 0))");
   if (count_stream_applies(c, k, m) && (int)div_ceil((k + 1) * 2 + 16, 32) <= 3) {
-    c->gen_first_pass = nullptr;
-    if (count_run_stream(c, k, m, out)) return 0;
-    c->gen_first_pass = nullptr;  // (gave up: the extraction + tile path redoes the job from the reads)
+    if (count_run_stream(c, k, m, out)) return 0;  // (gave up: the extraction + tile path redoes the job from the reads)
   }
-  const StageItems it = extract_stage(c, MHX_STAGE_COUNT, k, m);
+  StageItems it = extract_stage(c, MHX_STAGE_COUNT, k, m);
   uint32_t *buf_a = c->work["items_a"].as<uint32_t>();
   uint32_t *buf_b = c->ws("items_b", it.n * (size_t)it.S * 4 + 64).as<uint32_t>();
-  return count_process(c, k, m, buf_a, buf_b, it.n, out);
+  return count_process(c, k, m, buf_a, buf_b, it.n, out, &it.prep);
 }
 
 }  // namespace mhx

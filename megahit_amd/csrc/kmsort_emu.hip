@@ -860,11 +860,11 @@ __global__ void k_bucket_bounds(const uint32_t *__restrict__ items, uint64_t n, 
 
 // in: n records of stride S (key words first) in the reference's global emission order, in buf_a.
 // out: pointer to the records sorted exactly as the reference's per-bucket kmsort leaves them.
-uint32_t *kmsort_exact(mhx_ctx *c, uint32_t *buf_a, uint32_t *buf_b, uint64_t n, int S, int key_words) {
+uint32_t *kmsort_exact(mhx_ctx *c, uint32_t *buf_a, uint32_t *buf_b, uint64_t n, int S, int key_words, SortPrep *prep) {
   if (n == 0) return buf_a;
   hipStream_t st = c->stream;
   // 1. stable grouping by lv1 bucket (top 16 bits of word 0)
-  uint32_t *grouped = radix_sort(c, buf_a, buf_b, n, S, key_words, make_passes(key_words, key_words * 32 - 16, key_words * 32));
+  uint32_t *grouped = radix_sort(c, buf_a, buf_b, n, S, key_words, make_passes(key_words, key_words * 32 - 16, key_words * 32), prep);
   // 2. bucket boundaries
   uint64_t *bstart = c->ws("emu_bstart", (MHX_NUM_BUCKETS + 2) * 8).as<uint64_t>();
   MHX_LAUNCH(c, "bucket_bounds", (double)MHX_NUM_BUCKETS * 8 * 30,

@@ -87,28 +87,12 @@ struct mhx_ctx {
   // the is_solid bitmap is exactly what stage 1 found for this (k, m) — no mercy edges added, not set by the caller: stage 2 may then take its
   // solid items from a count of the (k+1)-mers instead of from every occurrence (s2.hip s2_agg_from_count; 0: not so)
   uint32_t solid_plain_k = 0, solid_plain_m = 0;
-  bool count_edges_only = false;  // count_stream_groups: only the solid edges are wanted (no first_0_out / last_0_in: positions do not matter)
   uint64_t n_route = 0;      // multi-GPU: records in ws("route_records") (count events)
-  // digit histograms of the next sort, taken by the extraction kernel (ws "sort_pre_hist"): valid for exactly this buffer
-  const void *pre_hist_buf = nullptr;
-  uint64_t pre_hist_n = 0;
-  int pre_hist_passes = 0;
-  uint64_t pre_hist_sig = 0;  // passes_signature() of the plan the histograms were taken for
-  // first sort pass whose records are generated instead of loaded (sort_kernels.h OnesweepLaunch; set by s1.hip, consumed by
-  // the next radix_sort on exactly this buffer and item count): the buffer then holds NO items yet
-  std::function<void(const mhx::OnesweepLaunch &)> gen_first_pass;
-  const void *gen_buf = nullptr;
-  uint64_t gen_n = 0;      // records the generated pass leaves (= what the rest of the sort handles)
-  uint64_t gen_slots = 0;  // item slots it walks (> gen_n when it drops the items of filtered-out lv1 buckets)
-  bool s2_filter_in_extract = false;  // passes.hip -> s2_extract: apply ws "filter_lut" while counting / writing the items
-  bool s1_filter_in_gen = false;      // passes.hip -> s1_extract: the generating first sort pass applies ws "filter_bits" (s1.hip S1GenT<true>)
   uint32_t filter_kept = 0;           // lv1 buckets the filter keeps
   // stage 1: records per lv1 bucket the ranks of a multi-GPU run agreed on (comm.hip; 0: each call derives it from its own
   // item count, s1.hip s1_density) — every rank must make the same sort plan
   double s1_density = 0;
-  bool s1_var_gen = false;            // the last s1_extract armed the variable-length generating pass (S1GenVarT)
   std::string last_s1_plan;           // what the last stage 1 ran as (mhx_last_s1_plan; bench.py prints it)
-  bool s1_defer_items = false;  // the caller of extract_stage(S1) will sort right away: s1_extract may defer the items to that sort
   // memory-bounded passes (passes.hip): only items of the kept lv1 buckets are materialised
   bool filter_on = false, accumulate = false;
   uint64_t filter_expected = 0, filter_batch_bytes = 0;
@@ -174,18 +158,32 @@ struct SortPass {
   // that agree on every bit the plan sorts — lets the pass rank with LDS atomics where that cannot matter (sort_kernels.h RANK 2)
   int prev_lo = -1;
 };
+// What an extraction prepared for the very next sort of the records it stands for.  It travels by value from the extraction
+// to that sort; the sort that receives it empties it, one that is never handed it cannot meet it.
+struct SortPrep {
+  const void *buf = nullptr;  // the sort buffer it was made for
+  uint64_t n = 0;             // records the sort handles (what a generated first pass leaves)
+  // digit histograms of the sort's passes, taken by the extraction kernel (ws "sort_pre_hist"); hist_passes == 0: none
+  int hist_passes = 0;
+  uint64_t hist_sig = 0;  // passes_signature() of the plan they were taken for
+  // first sort pass whose records are generated instead of loaded (sort_kernels.h OnesweepLaunch): the buffer holds NO items yet
+  std::function<void(const OnesweepLaunch &)> gen;
+  uint64_t gen_slots = 0;  // item slots it walks (> n when it drops the items of filtered-out lv1 buckets)
+  bool gen_var = false;    // ... padded to the longest read's count: reads of several lengths (S1GenVarT; the plan text says so)
+};
 // Sorts n items of `stride` uint32 words held in buf_a (ping-pong with buf_b) by the digit passes
-// (least-significant pass first).  Returns the buffer holding the result.
+// (least-significant pass first).  Returns the buffer holding the result.  prep: what the extraction of exactly these
+// records left for this sort (consumed).
 uint32_t *radix_sort(mhx_ctx *c, uint32_t *buf_a, uint32_t *buf_b, uint64_t n, int stride, int key_words,
-                     const std::vector<SortPass> &passes);
+                     const std::vector<SortPass> &passes, SortPrep *prep = nullptr);
 // prefix passes + segment finish in LDS when that saves passes (sort.hip); same result as radix_sort with `passes`
 uint32_t *sort_whole_key(mhx_ctx *c, uint32_t *buf_a, uint32_t *buf_b, uint64_t n, int stride, int key_words,
-                         const std::vector<SortPass> &passes);
+                         const std::vector<SortPass> &passes, SortPrep *prep = nullptr);
 std::vector<SortPass> make_passes(int key_words, int lo_bit, int hi_bit);
 bool sort_takes_generated_first_pass(const mhx_ctx *c, uint64_t n, int stride, const std::vector<SortPass> &passes);
 uint64_t passes_signature(const std::vector<SortPass> &ps);
 // kmsort_emu.hip: sort with the reference's exact (unstable) tie order, one GPU thread per lv1 bucket
-uint32_t *kmsort_exact(mhx_ctx *c, uint32_t *buf_a, uint32_t *buf_b, uint64_t n, int S, int key_words);
+uint32_t *kmsort_exact(mhx_ctx *c, uint32_t *buf_a, uint32_t *buf_b, uint64_t n, int S, int key_words, SortPrep *prep = nullptr);
 
 // ---- scan.hip ----
 // exclusive scan of n uint32 values into uint64 (in != out); returns total via d_total (device, uint64[1])
@@ -205,7 +203,7 @@ void emit_sdbg(mhx_ctx *c, const uint32_t *sorted, uint64_t n_items, int S, int 
 
 void partition_by_owner(mhx_ctx *c, const uint32_t *a, uint32_t *b, uint64_t n, int stride, const uint8_t *lut, int n_parts,
                         uint64_t *counts);
-uint64_t s1_extract(mhx_ctx *c, uint32_t k, bool compact);
+uint64_t s1_extract(mhx_ctx *c, uint32_t k, bool compact, SortPrep *prep, bool defer_items = false, bool filter_in_gen = false);
 bool s1_compact(const mhx_ctx *c, uint32_t k, int want_mercy);
 bool s1_rank_tagged(const mhx_ctx *c, uint32_t k);
 int s1_stride(uint32_t k, bool compact);
@@ -247,18 +245,18 @@ void s1_skm_hp_publish(mhx_ctx *c, const SkmFront &f, uint32_t k, uint32_t m, ui
 bool s1_skm_owner(mhx_ctx *c, uint32_t k, uint32_t m, const SkmFront &f, mhx_s1_result *out);
 
 bool s1_presort_applies(const mhx_ctx *c, uint32_t k, uint64_t n_local_items);
-uint32_t *s1_presort(mhx_ctx *c, uint32_t k, uint32_t *buf_a, uint32_t *buf_b, uint64_t n_items, int *pbits);
+uint32_t *s1_presort(mhx_ctx *c, uint32_t k, uint32_t *buf_a, uint32_t *buf_b, uint64_t n_items, int *pbits, SortPrep *prep);
 bool s1_filter_in_gen_applies(const mhx_ctx *c, uint32_t k);
 bool s1_bucket_histogram_fast(mhx_ctx *c, uint32_t k, unsigned long long *hist);
 uint32_t s1_pos_bits(const mhx_ctx *c);
 uint64_t s1_pos_stride(const mhx_ctx *c, uint32_t k);
 std::string s1_plan_text(const mhx_ctx *c, uint32_t k, uint64_t n_items);
 int s1_process(mhx_ctx *c, uint32_t k, uint32_t m, int want_mercy, uint32_t *buf_a, uint32_t *buf_b, uint64_t n_items, mhx_s1_result *out,
-               const S1Sources *pre = nullptr);
+               const S1Sources *pre = nullptr, SortPrep *prep = nullptr, bool var_gen = false);
 __global__ void k_add_u64(unsigned long long *__restrict__ a, const unsigned long long *__restrict__ b, int n);
 void sdbg_accumulate(mhx_ctx *c, bool first);
 void sdbg_publish_accumulated(mhx_ctx *c);
-uint64_t s2_extract(mhx_ctx *c, uint32_t k, uint32_t m);
+uint64_t s2_extract(mhx_ctx *c, uint32_t k, uint32_t m, bool filter_in_extract = false);
 int s2_process(mhx_ctx *c, uint32_t k, uint32_t *buf_a, uint32_t *buf_b, uint64_t n_items, mhx_sdbg_result *out);
 bool s2_use_aggregated(const mhx_ctx *c, uint32_t k, uint32_t m);
 uint64_t s2_agg_extract(mhx_ctx *c, uint32_t k);
@@ -268,15 +266,16 @@ struct StageItems {
   int S;           // words per item
   bool agg;        // stage 2: aggregated items (s2.hip)
   bool batchable;  // produced by a scan over reads
+  SortPrep prep;   // for the sort of exactly these items (empty: nothing prepared)
 };
-StageItems extract_stage(mhx_ctx *c, int stage, uint32_t k, uint32_t m);
+StageItems extract_stage(mhx_ctx *c, int stage, uint32_t k, uint32_t m, bool s1_defer_items = false);
 void bucket_histogram(mhx_ctx *c, int stage, uint32_t k, uint32_t m, uint64_t *h_out);
 int s2_stride(uint32_t k);
 constexpr int MHX_BUF_IS_SOLID_LOCAL = 100;  // internal: this rank's slice of the global bitmap (multi-GPU)
 constexpr int MHX_BUF_MERCY_CAND_LOCAL = 101;  // internal: routed mercy candidates of the local reads, local positions
-uint64_t count_extract(mhx_ctx *c, uint32_t k, uint32_t m = 0);
+uint64_t count_extract(mhx_ctx *c, uint32_t k, uint32_t m, SortPrep *prep);
 int count_stride(uint32_t k);
-int count_process(mhx_ctx *c, uint32_t k, uint32_t m, uint32_t *buf_a, uint32_t *buf_b, uint64_t n_items, mhx_count_result *out);
+int count_process(mhx_ctx *c, uint32_t k, uint32_t m, uint32_t *buf_a, uint32_t *buf_b, uint64_t n_items, mhx_count_result *out, SortPrep *prep = nullptr);
 void count_apply_events(mhx_ctx *c, const unsigned long long *ev, uint64_t n);
 uint64_t seq2sdbg_extract(mhx_ctx *c, uint32_t k);
 int seq2sdbg_stride(uint32_t k);
@@ -300,7 +299,7 @@ int sdbg_load_bytes(mhx_ctx *c, const uint8_t *bytes, uint64_t n_bytes, const ui
 int run_count(mhx_ctx *c, uint32_t k, uint32_t m, mhx_count_result *out);
 // count on the bucket streaming of stage 1 (s1.hip: CountGenT, k_s1_stream<COUNT>)
 int s2_agg_compact_bits(uint32_t k);
-bool s2_agg_from_count_applies(mhx_ctx *c, uint32_t k, uint32_t m);  // s2.hip: stage 2's solid items from a count of the (k+1)-mers  // count bits of a compact aggregated stage-2 item (k = 23..28), 0: none
+bool s2_agg_from_count_applies(const mhx_ctx *c, uint32_t k, uint32_t m);  // s2.hip: stage 2's solid items from a count of the (k+1)-mers  // count bits of a compact aggregated stage-2 item (k = 23..28), 0: none
 struct CountStreamOut {
   unsigned grid;      // workgroups = edge regions
   uint32_t cap;       // 8-byte edges a region holds
@@ -317,7 +316,8 @@ struct CountStreamOut {
   uint32_t skm_max_bin = 0;
   int skm_bin_bits = 0;
 };
-bool count_stream_applies(const mhx_ctx *c, uint32_t k, uint32_t m);
+// edges_only: only the solid edges are wanted (no first_0_out / last_0_in: positions do not matter)
+bool count_stream_applies(const mhx_ctx *c, uint32_t k, uint32_t m, bool edges_only = false);
 // `count` on super-k-mer records (s1_skm.hip): one GPU, 19 <= k <= 21, min count <= 2.  *touched: the caller's arrays may hold partial results
 bool count_skm_applies(const mhx_ctx *c, uint32_t k, uint32_t m);
 bool count_skm_groups(mhx_ctx *c, uint32_t k, uint32_t m, uint32_t *first_0_out, uint32_t *last_0_in_p1, unsigned long long *hist, CountStreamOut *o, bool *touched,
@@ -329,7 +329,7 @@ uint32_t *count_presort(mhx_ctx *c, uint32_t k, uint64_t *n_items, uint32_t **ot
 int count_process_presorted(mhx_ctx *c, uint32_t k, uint32_t m, const S1Sources &src, mhx_count_result *out);  // count.hip; -1: gave up
 bool count_bucket_histogram_fast(mhx_ctx *c, uint32_t k, unsigned long long *hist);  // s1_front.hip
 bool count_stream_groups(mhx_ctx *c, uint32_t k, uint32_t m, uint32_t *first_0_out, uint32_t *last_0_in_p1, unsigned long long *hist, CountStreamOut *o,
-                         const S1Sources *pre = nullptr);
+                         const S1Sources *pre = nullptr, bool edges_only = false);
 int run_s1(mhx_ctx *c, uint32_t k, uint32_t m, int want_mercy, mhx_s1_result *out);
 int run_s1_mercy(mhx_ctx *c, uint32_t k, uint64_t *num_mercy);
 int run_s2(mhx_ctx *c, uint32_t k, uint32_t m, mhx_sdbg_result *out);

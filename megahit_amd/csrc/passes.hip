@@ -48,14 +48,15 @@ __global__ void k_bucket_hist(const uint32_t *__restrict__ items, uint64_t n, in
 }
 
 // all items of the current c->seqs for `stage` -> ws("items_a")
-static StageItems extract_all(mhx_ctx *c, int stage, uint32_t k, uint32_t m) {
+// s1_defer_items: see extract_stage; s2_filter: stage 2 per occurrence leaves out the items of the dropped buckets itself
+static StageItems extract_all(mhx_ctx *c, int stage, uint32_t k, uint32_t m, bool s1_defer_items = false, bool s2_filter = false) {
   StageItems r{0, 0, false, true};
   if (stage == MHX_STAGE_S1 || stage == MHX_STAGE_S1_MERCY) {
     const bool compact = s1_compact(c, k, stage == MHX_STAGE_S1_MERCY ? 1 : 0);
-    r.n = s1_extract(c, k, compact);
+    r.n = s1_extract(c, k, compact, &r.prep, s1_defer_items);
     r.S = s1_stride(k, compact);
   } else if (stage == MHX_STAGE_COUNT) {
-    r.n = count_extract(c, k, m);
+    r.n = count_extract(c, k, m, &r.prep);
     r.S = count_stride(k);
   } else if (stage == MHX_STAGE_SEQ2SDBG) {
     r.n = seq2sdbg_extract(c, k);
@@ -69,7 +70,7 @@ static StageItems extract_all(mhx_ctx *c, int stage, uint32_t k, uint32_t m) {
       r.S = 2;
       r.batchable = false;
     } else {
-      r.n = s2_extract(c, k, m);
+      r.n = s2_extract(c, k, m, s2_filter);
       r.S = s2_stride(k);
     }
   } else throw Error("unknown stage");
@@ -127,39 +128,25 @@ void bucket_histogram(mhx_ctx *c, int stage, uint32_t k, uint32_t m, uint64_t *h
 }
 
 // items of `stage` -> ws("items_a"), restricted to the kept buckets when a filter is set
-StageItems extract_stage(mhx_ctx *c, int stage, uint32_t k, uint32_t m) {
-  if (!c->filter_on) return extract_all(c, stage, k, m);
+// s1_defer_items: the caller sorts right away and hands that sort the returned prep, so stage 1 may leave the records to the
+// sort's first pass ("items_a" then holds nothing yet)
+StageItems extract_stage(mhx_ctx *c, int stage, uint32_t k, uint32_t m, bool s1_defer_items) {
+  if (!c->filter_on) return extract_all(c, stage, k, m, s1_defer_items);
   if (stage == MHX_STAGE_S2 && !s2_use_aggregated(c, k, m) && c->opt("s2_filter_in_extract", 1)) {
     // stage 2 per occurrence: the extraction itself leaves out the items of the dropped buckets (s2.hip s2_kept_mask) — one
     // scan of the reads per pass, no staging batches, no keep/drop split, nothing of the dropped buckets ever written
-    c->s2_filter_in_extract = true;
-    StageItems r;
-    try {
-      r = extract_all(c, stage, k, m);
-    } catch (...) {
-      c->s2_filter_in_extract = false;
-      throw;
-    }
-    c->s2_filter_in_extract = false;
+    StageItems r = extract_all(c, stage, k, m, false, true);
     if (r.n > c->filter_expected) throw Error("bucket filter: more items in the kept buckets than announced");
-    c->pre_hist_buf = nullptr;
     return r;
   }
-  if (stage == MHX_STAGE_S1 && c->s1_defer_items && s1_filter_in_gen_applies(c, k)) {
+  if (stage == MHX_STAGE_S1 && s1_defer_items && s1_filter_in_gen_applies(c, k)) {
     // stage 1 on the fast shape: the first sort pass makes the records and leaves out those of the dropped buckets (s1.hip
     // S1GenT<true>) — one scan of the reads per pass, nothing staged, nothing split; "items_a" is empty until that pass ran
-    c->s1_filter_in_gen = true;
     StageItems r{0, 0, false, true};
-    try {
-      r.n = s1_extract(c, k, true);
-    } catch (...) {
-      c->s1_filter_in_gen = false;
-      throw;
-    }
+    r.n = s1_extract(c, k, true, &r.prep, true, true);
     r.S = s1_stride(k, true);
     return r;
   }
-  c->s1_defer_items = false;  // (batches: the items are materialised here)
   hipStream_t st = c->stream;
   const uint8_t *lut = c->work["filter_lut"].as<uint8_t>();
   uint64_t kept = 0;
@@ -177,7 +164,7 @@ StageItems extract_stage(mhx_ctx *c, int stage, uint32_t k, uint32_t m) {
   });
   MHX_HIP(hipStreamSynchronize(st));
   if (keep) std::swap(c->work["items_a"], *keep);  // the engines take their input from "items_a"
-  c->pre_hist_buf = nullptr;
+  res.prep = SortPrep{};  // (the first batch's: the kept items lie elsewhere)
   res.n = kept;
   return res;
 }

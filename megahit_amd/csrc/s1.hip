@@ -394,13 +394,11 @@ bool s1_presort_applies(const mhx_ctx *c, uint32_t k, uint64_t n_local_items) {
 }
 // the LSD passes that order this rank's stage-1 records by the plan's prefix (the first half of s1_process on the stream
 // plan; the ranks agreed on the density the plan follows: mhx_ctx::s1_density)
-uint32_t *s1_presort(mhx_ctx *c, uint32_t k, uint32_t *buf_a, uint32_t *buf_b, uint64_t n_items, int *pbits) {
+uint32_t *s1_presort(mhx_ctx *c, uint32_t k, uint32_t *buf_a, uint32_t *buf_b, uint64_t n_items, int *pbits, SortPrep *prep) {
   const S1Plan plan = s1_plan(c, k, std::max<uint64_t>(n_items, 1), true, 0);
   if (!plan.stream) throw Error("s1_presort: the bucket-streaming plan does not apply");
   *pbits = plan.seg_bits;
-  uint32_t *sorted = n_items ? radix_sort(c, buf_a, buf_b, n_items, 3, s1_kw(k), plan.passes) : buf_a;
-  c->pre_hist_buf = nullptr;
-  return sorted;
+  return n_items ? radix_sort(c, buf_a, buf_b, n_items, 3, s1_kw(k), plan.passes, prep) : buf_a;
 }
 
 // ---- stage 1 behind the extraction, in steps (Read2SdbgS1::Lv2Postprocess and what it needs, read_to_sdbg_s1.cpp:368-555) ----
@@ -466,14 +464,13 @@ struct S1Stage {
     if (pre && pre->pbits != plan.seg_bits) throw Error("s1_process: the sources were sorted for another plan than the one this rank makes");
   }
 
-  void sort_records() {
+  void sort_records(SortPrep *prep) {  // prep: what the extraction of these records left for their sort
     // want_mercy == 2: records with equal keys in exactly the order the reference's kmsort leaves them (H1)
     sorted = pre ? nullptr
              : want_mercy == 2
-                 ? kmsort_exact(c, buf_a, buf_b, n_items, S, KWv)
-                 : (plan.seg_bits || tagged_keys ? radix_sort(c, buf_a, buf_b, n_items, S, KWv, plan.passes)
-                                                 : sort_whole_key(c, buf_a, buf_b, n_items, S, KWv, plan.passes));
-    c->pre_hist_buf = nullptr;
+                 ? kmsort_exact(c, buf_a, buf_b, n_items, S, KWv, prep)
+                 : (plan.seg_bits || tagged_keys ? radix_sort(c, buf_a, buf_b, n_items, S, KWv, plan.passes, prep)
+                                                 : sort_whole_key(c, buf_a, buf_b, n_items, S, KWv, plan.passes, prep));
     set_spare(pre ? pre->spare : (sorted == buf_a ? buf_b : buf_a));
   }
   void set_spare(uint32_t *sp) {
@@ -907,12 +904,11 @@ struct S1Stage {
 }  // namespace
 
 int s1_process(mhx_ctx *c, uint32_t k, uint32_t m, int want_mercy, uint32_t *buf_a, uint32_t *buf_b, uint64_t n_items,
-               mhx_s1_result *out, const S1Sources *pre) {
+               mhx_s1_result *out, const S1Sources *pre, SortPrep *prep, bool var_gen) {
   S1Stage stage(c, k, m, want_mercy, buf_a, buf_b, n_items, pre);
   c->last_s1_plan = s1_plan_text(c, k, pre ? std::max<uint64_t>(n_items, 1) : n_items);
-  if (c->s1_var_gen) c->last_s1_plan += " [reads of several lengths: " + std::to_string(c->seqs.max_len - k + 4) + " item slots per read on the generating pass]";
-  c->s1_var_gen = false;
-  stage.sort_records();
+  if (var_gen) c->last_s1_plan += " [reads of several lengths: " + std::to_string(c->seqs.max_len - k + 4) + " item slots per read on the generating pass]";
+  stage.sort_records(prep);
   stage.open_outputs();
   if (n_items) {
     stage.polarity();
@@ -965,7 +961,7 @@ static uint64_t count_plan_items(const mhx_ctx *c, uint32_t k) {  // the item co
   return s.fixed_len ? s.n_seqs * (uint64_t)(s.fixed_len - k) : s.n_bases - s.n_seqs * (uint64_t)k;
 }
 // what both forms need: the shape the generators serve, the plan's digits in the first key word, a 32-bit table key
-static bool count_stream_shape(const mhx_ctx *c, uint32_t k, uint32_t m, S1Plan *plan_out) {
+static bool count_stream_shape(const mhx_ctx *c, uint32_t k, uint32_t m, bool edges_only) {
   const SeqSet &s = c->seqs;
   if (!c->opt("count_stream", 1)) return false;
   if (c->filter_on && !c->opt("s1_filter_in_gen", 1)) return false;
@@ -973,9 +969,9 @@ static bool count_stream_shape(const mhx_ctx *c, uint32_t k, uint32_t m, S1Plan 
   if (!c->opt("count_seg", 1) || c->opt("count_seg_bits", 0) || !c->opt("count_extract_fixed", 1)) return false;
   // (min count 1, 2: seen-once / seen-twice bits per prev / next char in the table slot; 3..15: 4-bit counters that stop at m)
   if (!s.n_seqs || k < 9 || m < 1 || m > 15) return false;  // (k: count_shape_is_fast — up to 22 with a shared window per run, up to 27 with one per item)
-  if (!count_shape_is_fast(c, k)) return false;  // (reads of several lengths: item slots padded to the longest read's, CountGenVarT)
+  if (!count_shape_is_fast(c, k, edges_only)) return false;  // (reads of several lengths: item slots padded to the longest read's, CountGenVarT)
   if (!c->opt("s1_fused_first_pass", 1) || !c->opt("sort_unit_runs", 1) || !c->opt("s1_gen_any_order", 1)) return false;
-  const uint64_t n_bits = c->count_edges_only ? 0 : (c->global_bases ? c->global_bases : s.n_bases);  // (edges only: nobody reads the positions)
+  const uint64_t n_bits = edges_only ? 0 : (c->global_bases ? c->global_bases : s.n_bases);  // (edges only: nobody reads the positions)
   if ((n_bits >> s1_pos_bits(c)) >= 256) return false;  // (positions beyond the tags)
   const uint64_t n_items = count_plan_items(c, k);
   const S1Plan plan = s1_plan(c, k, n_items, true, 0);
@@ -985,19 +981,18 @@ static bool count_stream_shape(const mhx_ctx *c, uint32_t k, uint32_t m, S1Plan 
   // the table key is the (k+1)-mer below the prefix: 32 bits (the all-ones word stands for an empty slot) up to k = 22 at a 16-bit
   // prefix, the 64-bit form beyond (k = 23..27, or a forced narrow prefix — s1_stream_bits), which carries no position tags
   if (2 * ((int)k + 1) - plan.seg_bits > 31 && (n_bits >> s1_pos_bits(c)) != 0) return false;
-  if (plan_out) *plan_out = plan;
   return sort_takes_generated_first_pass(c, c->filter_on ? std::max<uint64_t>(c->filter_expected, 1) : n_items, 3, plan.passes);
 }
-bool count_stream_applies(const mhx_ctx *c, uint32_t k, uint32_t m) {
+bool count_stream_applies(const mhx_ctx *c, uint32_t k, uint32_t m, bool edges_only) {
   // (under a bucket filter — a pass of the memory plan — the generating pass keeps only the records of the kept lv1 buckets and the
   //  plan follows the density of that bucket range, as in stage 1; first_0_out / last_0_in and the histogram accumulate over the passes)
   if (c->global_bases || c->n_parts > 1) return false;
-  return count_stream_shape(c, k, m, nullptr);
+  return count_stream_shape(c, k, m, edges_only);
 }
 // several GPUs: this rank's say (the ranks decide together, comm.hip); the plan follows the density they agreed on (mhx_ctx::s1_density)
 bool count_presort_applies(const mhx_ctx *c, uint32_t k, uint32_t m) {
   if (!c->global_bases || c->n_parts > kStreamSrcMax || !c->opt("dist_presort", 1)) return false;
-  return count_stream_shape(c, k, m, nullptr);
+  return count_stream_shape(c, k, m, false);
 }
 // the front half on a rank of a multi-GPU run: this rank's records, made by the first sort pass and ordered by the plan's prefix
 // (n_items == 0: a rank or pass without an edge — nothing made, `sorted` is an empty buffer)
@@ -1007,17 +1002,14 @@ uint32_t *count_presort(mhx_ctx *c, uint32_t k, uint64_t *n_items, uint32_t **ot
   *pbits = plan.seg_bits;
   uint32_t *buf_a = nullptr, *buf_b = nullptr;
   *n_items = 0;
-  c->gen_first_pass = nullptr;
-  if (!count_stream_front(c, k, plan, &buf_a, &buf_b, n_items)) {
+  SortPrep prep;
+  if (!count_stream_front(c, k, plan, false, &buf_a, &buf_b, n_items, &prep)) {
     *n_items = 0;
-    c->gen_first_pass = nullptr;
-    c->pre_hist_buf = nullptr;
     buf_a = c->ws("items_a", 64).as<uint32_t>();
     *other = c->ws("items_b", 64).as<uint32_t>();
     return buf_a;
   }
-  uint32_t *sorted = radix_sort(c, buf_a, buf_b, *n_items, 3, 2, plan.passes);
-  c->pre_hist_buf = nullptr;
+  uint32_t *sorted = radix_sort(c, buf_a, buf_b, *n_items, 3, 2, plan.passes, &prep);
   *other = sorted == buf_a ? buf_b : buf_a;
   return sorted;
 }
@@ -1026,7 +1018,7 @@ uint32_t *count_presort(mhx_ctx *c, uint32_t k, uint64_t *n_items, uint32_t **ot
 // pre: the records lie pre-sorted by the plan's prefix in several arrays (several GPUs: one per sending rank); the events that move
 // first_0_out / last_0_in then leave as a list (o->events) for the ranks that hold the reads instead of being applied here.
 bool count_stream_groups(mhx_ctx *c, uint32_t k, uint32_t m, uint32_t *first_0_out, uint32_t *last_0_in_p1, unsigned long long *hist,
-                         CountStreamOut *o, const S1Sources *pre) {
+                         CountStreamOut *o, const S1Sources *pre, bool edges_only) {
   SeqSet &s = c->seqs;
   hipStream_t st = c->stream;
   const bool global = c->global_bases != 0;
@@ -1042,12 +1034,12 @@ bool count_stream_groups(mhx_ctx *c, uint32_t k, uint32_t m, uint32_t *first_0_o
     spare = pre->spare;
   } else {
     uint32_t *buf_a = nullptr, *buf_b = nullptr;
-    if (!count_stream_front(c, k, plan, &buf_a, &buf_b, &n_items)) return false;  // (no read holds an edge: the general path knows what to publish)
-    sorted = radix_sort(c, buf_a, buf_b, n_items, 3, KWv, plan.passes);
-    c->pre_hist_buf = nullptr;
+    SortPrep prep;
+    if (!count_stream_front(c, k, plan, edges_only, &buf_a, &buf_b, &n_items, &prep)) return false;  // (no read holds an edge: the general path knows what to publish)
+    sorted = radix_sort(c, buf_a, buf_b, n_items, 3, KWv, plan.passes, &prep);
     spare = sorted == buf_a ? buf_b : buf_a;
   }
-  const uint64_t n_bits = c->count_edges_only ? 0 : (global ? c->global_bases : s.n_bases);
+  const uint64_t n_bits = edges_only ? 0 : (global ? c->global_bases : s.n_bases);
   const uint64_t pos_stride = (n_bits >> s1_pos_bits(c)) ? 1ull << s1_pos_bits(c) : 0ull;
   // bucket streaming
   const uint64_t n_buckets = 1ull << plan.seg_bits;
@@ -1095,8 +1087,8 @@ bool count_stream_groups(mhx_ctx *c, uint32_t k, uint32_t m, uint32_t *first_0_o
   a.c_fixed_len = s.fixed_len;
   a.first_0_out = first_0_out;
   a.last_0_in_p1 = last_0_in_p1;
-  a.c_wpe = c->count_edges_only ? 3 : (int)div_ceil((k + 1) * 2 + 16, 32);  // (edges only: always the 16-byte entries, s2.hip reads them)
-  a.c_edges_only = c->count_edges_only ? 1 : 0;
+  a.c_wpe = edges_only ? 3 : (int)div_ceil((k + 1) * 2 + 16, 32);  // (edges only: always the 16-byte entries, s2.hip reads them)
+  a.c_edges_only = edges_only ? 1 : 0;
   uint32_t ecap = 0;
   uint32_t *ecounts = nullptr;
   if (global) {
@@ -1261,20 +1253,16 @@ int run_s1(mhx_ctx *c, uint32_t k, uint32_t m, int want_mercy, mhx_s1_result *ou
   if (c->global_bases) throw Error("read2sdbg_s1: a global layout is set; use the mhx_dist_* entry points");
   std::string skm_why;
   if (s1_skm_applies(c, k, m, want_mercy)) {
-    c->gen_first_pass = nullptr;
-    c->pre_hist_buf = nullptr;
     if (s1_skm_try(c, k, m, out, &skm_why)) return 0;
     // s1_skm = 3: a caller that left the memory plan to this path (mhx_s1_self_planned) hears that it did not serve — the prefix plan
     // of a whole job that was never cut into lv1 bucket ranges may not fit
     if (c->opt("s1_skm", 1) == 3) throw Error("read2sdbg_s1: super-k-mer records given up (" + skm_why + ")");
   }
-  c->s1_defer_items = !want_mercy;  // s1_process sorts "items_a" first thing: its first pass may make the records (and apply a bucket filter)
-  c->gen_first_pass = nullptr;
-  const StageItems it = extract_stage(c, want_mercy ? MHX_STAGE_S1_MERCY : MHX_STAGE_S1, k, m);
-  c->s1_defer_items = false;
+  // s1_process sorts "items_a" first thing: its first pass may make the records (and apply a bucket filter)
+  StageItems it = extract_stage(c, want_mercy ? MHX_STAGE_S1_MERCY : MHX_STAGE_S1, k, m, !want_mercy);
   uint32_t *buf_a = c->work["items_a"].as<uint32_t>();
   uint32_t *buf_b = c->ws("items_b", it.n * (size_t)it.S * 4 + 64).as<uint32_t>();
-  const int rc = s1_process(c, k, m, want_mercy, buf_a, buf_b, it.n, out);
+  const int rc = s1_process(c, k, m, want_mercy, buf_a, buf_b, it.n, out, nullptr, &it.prep, it.prep.gen_var);
   if (!skm_why.empty()) c->last_s1_plan += " [super-k-mer records given up: " + skm_why + "]";
   return rc;
 }

@@ -830,12 +830,12 @@ bool s1_bucket_histogram_fast(mhx_ctx *c, uint32_t k, unsigned long long *hist) 
 
 // the shapes CountGenT / CountGenVarT serve: >= 8 item slots per read, k <= kCountStreamMaxK; a library of several read lengths while at
 // least s1_var_min_fill per cent of the padded slots are edges
-bool count_shape_is_fast(const mhx_ctx *c, uint32_t k) {
+bool count_shape_is_fast(const mhx_ctx *c, uint32_t k, bool edges_only) {
   const SeqSet &s = c->seqs;
   if (!s.n_seqs || k < 9) return false;
   if ((int)k > kCountStreamMaxK)  // k = 23..27: a window per item (CountGenWideT), reads of one length, no position tags
     return (int)k <= kCountStreamWideMaxK && c->opt("count_stream_wide", 1) && s.fixed_len >= k + 1 && s.fixed_len - k >= 8 &&
-           (c->count_edges_only || ((s.n_bases >> s1_pos_bits(c)) == 0 && (c->global_bases >> s1_pos_bits(c)) == 0));
+           (edges_only || ((s.n_bases >> s1_pos_bits(c)) == 0 && (c->global_bases >> s1_pos_bits(c)) == 0));
   if (s.fixed_len) return s.fixed_len >= k + 1 && s.fixed_len - k >= 8;
   if (!c->opt("s1_var_fast", 1) || s.max_len < k + 1 || s.max_len - k < 8 || s.n_bases <= s.n_seqs * (uint64_t)k) return false;
   return (double)s.n_bases * 100.0 >= (double)c->opt("s1_var_min_fill", 50) * (double)s.n_seqs * s.max_len;
@@ -843,7 +843,7 @@ bool count_shape_is_fast(const mhx_ctx *c, uint32_t k) {
 // -> true when it ran; hist: device, 65 536 counters, zeroed by the caller
 bool count_bucket_histogram_fast(mhx_ctx *c, uint32_t k, unsigned long long *hist) {
   SeqSet &s = c->seqs;
-  if (!c->opt("s1_bucket_hist_fast", 1) || !c->opt("count_stream", 1) || !count_shape_is_fast(c, k)) return false;
+  if (!c->opt("s1_bucket_hist_fast", 1) || !c->opt("count_stream", 1) || !count_shape_is_fast(c, k, false)) return false;
   constexpr int IT = 8;
   const bool var = s.fixed_len == 0;
   const uint32_t per = (var ? s.max_len : s.fixed_len) - k;
@@ -931,10 +931,11 @@ __global__ __launch_bounds__(256) void k_s1_extract_fast(const uint32_t *__restr
 }
 
 
-// items of the local reads -> c->ws("items_a"); returns their number.
+// items of the local reads -> c->ws("items_a"); returns their number.  *prep: what the sort of exactly these items may use.
 // Three ways, fastest first: (1) deferred — only the digit histograms of the coming sort are taken here and the sort's first
 // pass makes the records itself (fixed-length reads, 12-byte records; under a bucket filter that pass drops the items of
-// the other buckets: c->s1_filter_in_gen); (2) the window-arithmetic extraction; (3) the general kernels.
+// the other buckets: filter_in_gen); (2) the window-arithmetic extraction; (3) the general kernels.
+// defer_items: the caller sorts "items_a" right away and hands that sort *prep, so (1) may be taken.
 bool s1_shape_is_fast(const mhx_ctx *c, uint32_t k, bool compact) {
   const SeqSet &s = c->seqs;
   return s.n_seqs && s.fixed_len >= k + 1 && compact && s1_kw(k) == 2 && s1_stride(k, compact) == 3 && k <= 29 && c->opt("s1_extract_fast", 1) != 0;
@@ -962,22 +963,20 @@ bool s1_filter_in_gen_applies(const mhx_ctx *c, uint32_t k) {
   return plan.seg_bits > 0 && (int)plan.passes.size() <= kFastPasses && sort_takes_generated_first_pass(c, std::max<uint64_t>(c->filter_expected, 1), 3, plan.passes);
 }
 
-uint64_t s1_extract(mhx_ctx *c, uint32_t k, bool compact) {
+uint64_t s1_extract(mhx_ctx *c, uint32_t k, bool compact, SortPrep *prep, bool defer_items, bool filter_in_gen) {
   SeqSet &s = c->seqs;
   if (k < 9 || k > MHX_MAX_K) throw Error("read2sdbg: k out of range [9,255]");
   const int KWv = s1_kw(k), S = s1_stride(k, compact);
   const uint64_t ns = s.n_seqs;
   hipStream_t st = c->stream;
-  const bool filter_in_gen = c->s1_filter_in_gen;
-  c->s1_filter_in_gen = false;
+  *prep = SortPrep{};
   uint32_t *cnt = c->ws("seq_item_cnt", (ns + 1) * 4).as<uint32_t>();
   uint64_t *item_start = c->ws("seq_item_start", (ns + 2) * 8).as<uint64_t>();
   uint64_t n_items = 0;
   // reads of any length on the generating pass (S1GenVarT): only as deferred items — there is no extraction kernel of that form
-  const bool var_fast = s1_shape_is_var_fast(c, k, compact) && (filter_in_gen || c->s1_defer_items) && c->opt("s1_fused_first_pass", 1) &&
+  const bool var_fast = s1_shape_is_var_fast(c, k, compact) && (filter_in_gen || defer_items) && c->opt("s1_fused_first_pass", 1) &&
                         c->opt("s1_gen_blocked", 0) && c->opt("s1_gen_roll", 1) && c->opt("s1_digit_hist_roll", 1) && c->opt("s1_digit_hist_blocked", 1) &&
                         c->opt("s1_digit_hist_plain", 1) && c->opt("s1_gen_any_order", 1) && c->opt("sort_unit_runs", 1);
-  c->s1_var_gen = false;
   const bool shape_fast = s1_shape_is_fast(c, k, compact) || var_fast;
   if (ns && shape_fast && s.fixed_len >= k + 1) {
     n_items = ns * (uint64_t)(s.fixed_len - k + 4);  // (no per-read table for reads of one length)
@@ -1004,19 +1003,18 @@ uint64_t s1_extract(mhx_ctx *c, uint32_t k, bool compact) {
     DigitSpecs specs;
     specs.n = 0;
     unsigned long long *pre_hist = nullptr;
-    c->pre_hist_buf = nullptr;
     std::vector<SortPass> plan_passes;
     if ((fixed || var_fast) && S <= 4) {
       plan_passes = s1_plan(c, k, n_items, compact, compact ? 0 : 1).passes;
       if ((int)plan_passes.size() <= kMaxFusedPasses) {
-        c->pre_hist_sig = passes_signature(plan_passes);
+        prep->hist_sig = passes_signature(plan_passes);
         specs.n = (int)plan_passes.size();
         for (int p = 0; p < specs.n; ++p) specs.d[p] = spec_of_pass(plan_passes[p], KWv);
         pre_hist = c->ws("sort_pre_hist", (size_t)kMaxFusedPasses * 256 * 8).as<unsigned long long>();
         MHX_HIP(hipMemsetAsync(pre_hist, 0, (size_t)specs.n * 256 * 8, st));
-        c->pre_hist_buf = buf_a;
-        c->pre_hist_n = n_items;
-        c->pre_hist_passes = specs.n;
+        prep->buf = buf_a;
+        prep->n = n_items;
+        prep->hist_passes = specs.n;
       }
     }
     // (a variable-length library whose plan or sort cannot take the generated pass goes the general way below)
@@ -1028,7 +1026,7 @@ uint64_t s1_extract(mhx_ctx *c, uint32_t k, bool compact) {
       if (filter_in_gen) throw Error("s1_extract: the bucket filter was left to a generating pass that does not apply");
       specs.n = 0;
       pre_hist = nullptr;
-      c->pre_hist_buf = nullptr;
+      prep->hist_passes = 0;
     }
     const bool fast = (fixed || var_ok) && shape_fast && specs.n <= kFastPasses;
     if (fast) {
@@ -1036,7 +1034,7 @@ uint64_t s1_extract(mhx_ctx *c, uint32_t k, bool compact) {
       const uint32_t per = per_slots;
       // Deferred items: the caller sorts right away (run_s1, the multi-GPU pre-sort), so only the digit histograms are taken
       // here and the first sort pass makes the records itself (S1Gen): "items_a" stays empty until that pass has run.
-      const bool defer = filter_in_gen || var_ok || (c->s1_defer_items && pre_hist && c->opt("s1_fused_first_pass", 1) &&
+      const bool defer = filter_in_gen || var_ok || (defer_items && pre_hist && c->opt("s1_fused_first_pass", 1) &&
                                                       sort_takes_generated_first_pass(c, n_items, 3, plan_passes));
 #define MHX_FAST(ITV, WR, NAME)                                                                                                        \
   do {                                                                                                                                 \
@@ -1116,8 +1114,6 @@ uint64_t s1_extract(mhx_ctx *c, uint32_t k, bool compact) {
           for (unsigned long long v : h0) n_records += v;
           if (n_records > c->filter_expected) throw Error("bucket filter: more items in the kept buckets than announced");
           buf_a = c->ws("items_a", n_records * item_bytes + 64).as<uint32_t>();
-          c->pre_hist_buf = buf_a;
-          c->pre_hist_n = n_records;
         }
         // The consumers of this pass (the LDS group-bys behind the remaining passes; compact records, no mercy) count equal
         // keys: they need the records grouped, not in input order — so the first pass may place the records of a digit in
@@ -1134,7 +1130,7 @@ uint64_t s1_extract(mhx_ctx *c, uint32_t k, bool compact) {
         // s1_gen_roll: the blocked generator with one window + one reverse complement per run of a thread's items (k <= 23)
         const bool roll = blocked && (int)k <= kS1RollMaxK && c->opt("s1_gen_roll", 1) != 0;
         if (var_ok && !roll) throw Error("s1_extract: the variable-length generating pass needs s1_gen_blocked and s1_gen_roll");
-        c->s1_var_gen = var_ok;
+        prep->gen_var = var_ok;
         const S1GenVarT<false> gv{s.words.as<uint32_t>(), s.start.as<uint64_t>(), ns, per, (int)k, pos_base, pos_bits, (uint32_t)(kSortThreads * 8) / per,
                                   (uint32_t)(kSortThreads * 8) % per, nullptr};
         const S1GenVarT<true> gvf{s.words.as<uint32_t>(), s.start.as<uint64_t>(), ns, per, (int)k, pos_base, pos_bits, (uint32_t)(kSortThreads * 8) / per,
@@ -1143,7 +1139,7 @@ uint64_t s1_extract(mhx_ctx *c, uint32_t k, bool compact) {
                                    (uint32_t)(kSortThreads * 8) % per, nullptr};
         const S1GenRollT<true> grf{s.words.as<uint32_t>(), s.fixed_len, per, (int)k, pos_base, pos_bits, (uint32_t)(kSortThreads * 8) / per,
                                    (uint32_t)(kSortThreads * 8) % per, keep};
-        c->gen_first_pass = [g, gf, gb, gbf, gr, grf, gv, gvf, var_ok, roll, any_order, blocked, filter_in_gen](const OnesweepLaunch &l) {
+        prep->gen = [g, gf, gb, gbf, gr, grf, gv, gvf, var_ok, roll, any_order, blocked, filter_in_gen](const OnesweepLaunch &l) {
 #define MHX_GEN(KERNEL, SRCT, RANKV, SRCV)                                                                                              \
   hipLaunchKernelGGL((KERNEL<3, 8, 3, SRCT, RANKV>), dim3(l.grid), dim3(kSortThreads), 0, l.stream, SRCV, l.out, l.n, l.ds, l.nbits, l.bin_start, \
                      l.status, l.ticket, l.err, l.tag, l.xcd_units)
@@ -1168,17 +1164,16 @@ uint64_t s1_extract(mhx_ctx *c, uint32_t k, bool compact) {
 #undef MHX_GEN
 #undef MHX_GEN_U
         };
-        c->gen_buf = buf_a;
-        c->gen_n = n_records;
-        c->gen_slots = n_slots;
-        if (n_records == 0) c->gen_first_pass = nullptr;  // (a pass or rank that keeps no record: no sort will come and consume it)
+        prep->buf = buf_a;
+        prep->n = n_records;
+        prep->gen_slots = n_slots;
+        if (n_records == 0) prep->gen = nullptr;  // (a pass or rank that keeps no record: nothing to make)
         n_items = n_records;
       } else if (it >= 8) MHX_FAST(8, true, "s1_extract");
       else if (it >= 4) MHX_FAST(4, true, "s1_extract");
       else if (it >= 2) MHX_FAST(2, true, "s1_extract");
       else MHX_FAST(1, true, "s1_extract");
 #undef MHX_FAST
-      c->s1_defer_items = false;
     } else {
       if (ns && shape_fast) {  // (the per-read table was skipped above: the general kernels want it)
         MHX_LAUNCH(c, "item_counts", (double)ns * 12,
@@ -1209,14 +1204,16 @@ uint64_t s1_extract(mhx_ctx *c, uint32_t k, bool compact) {
 #undef MHX_S1X
     }
   }
-  c->s1_defer_items = false;
   return n_items;
 }
 
 // ---- the front of `count` on the bucket-streaming design (KmerCounter::Lv1FillOffsets + Lv2ExtractSubString, kmer_counter.cpp:158-252) ----
-bool count_stream_front(mhx_ctx *c, uint32_t k, const S1Plan &plan, uint32_t **buf_a_out, uint32_t **buf_b_out, uint64_t *n_items_out) {
+// edges_only: only the solid edges are wanted (stage 2's aggregated items from a count): positions do not matter.  *prep: for the sort of the records
+bool count_stream_front(mhx_ctx *c, uint32_t k, const S1Plan &plan, bool edges_only, uint32_t **buf_a_out, uint32_t **buf_b_out, uint64_t *n_items_out,
+                        SortPrep *prep) {
   SeqSet &s = c->seqs;
   hipStream_t st = c->stream;
+  *prep = SortPrep{};
   const bool var = s.fixed_len == 0;
   const uint32_t per = (var ? s.max_len : s.fixed_len) - k;  // item slots per read
   const uint64_t n_slots = s.n_seqs * (uint64_t)per;
@@ -1279,13 +1276,13 @@ bool count_stream_front(mhx_ctx *c, uint32_t k, const S1Plan &plan, uint32_t **b
   *buf_a_out = buf_a;
   *buf_b_out = buf_b;
   *n_items_out = n_items;
-  c->pre_hist_sig = passes_signature(plan.passes);
-  c->pre_hist_buf = buf_a;
-  c->pre_hist_n = n_items;
-  c->pre_hist_passes = hd.n;
+  prep->hist_sig = passes_signature(plan.passes);
+  prep->buf = buf_a;
+  prep->n = n_items;
+  prep->hist_passes = hd.n;
   // (edges only — stage 2's aggregated items from a count — nobody reads the positions: no tag bits either, which at k >= 23 would sit
   //  on bits of the (k+1)-mer; count_stream_shape declines tagged read sets there in every other case)
-  const uint32_t pos_bits = c->count_edges_only ? 63u : s1_pos_bits(c);
+  const uint32_t pos_bits = edges_only ? 63u : s1_pos_bits(c);
   const uint32_t tq = (uint32_t)(kSortThreads * 8) / per, tr = (uint32_t)(kSortThreads * 8) % per;
   const CountGenT<false> g{s.words.as<uint32_t>(), s.fixed_len, per, (int)k, c->pos_base, pos_bits, tq, tr, nullptr};
   const CountGenT<true> gf{s.words.as<uint32_t>(), s.fixed_len, per, (int)k, c->pos_base, pos_bits, tq, tr, keep};
@@ -1294,7 +1291,7 @@ bool count_stream_front(mhx_ctx *c, uint32_t k, const S1Plan &plan, uint32_t **b
   const bool filter = keep != nullptr;
   const CountGenWideT<false> gw{s.words.as<uint32_t>(), s.fixed_len, per, (int)k, c->pos_base, pos_bits, tq, tr, nullptr};
   const CountGenWideT<true> gwf{s.words.as<uint32_t>(), s.fixed_len, per, (int)k, c->pos_base, pos_bits, tq, tr, keep};
-  c->gen_first_pass = [g, gf, gv, gvf, gw, gwf, var, filter, wide](const OnesweepLaunch &l) {
+  prep->gen = [g, gf, gv, gvf, gw, gwf, var, filter, wide](const OnesweepLaunch &l) {
     if (!(l.unit_runs && l.wi == 0)) throw Error("count: the generating pass needs the unit-wide pass on a first-word digit");
 #define MHX_CGEN(SRCT, SRCV)                                                                                                                \
   hipLaunchKernelGGL((k_radix_onesweep_u<3, 8, 3, SRCT, 1, 0>), dim3(l.grid), dim3(kSortThreads), 0, l.stream, SRCV, l.out, l.n, l.ds, l.nbits, \
@@ -1307,9 +1304,7 @@ bool count_stream_front(mhx_ctx *c, uint32_t k, const S1Plan &plan, uint32_t **b
     else MHX_CGEN(CountGenT<false>, g);
 #undef MHX_CGEN
   };
-  c->gen_buf = buf_a;
-  c->gen_n = n_items;
-  c->gen_slots = n_slots;
+  prep->gen_slots = n_slots;
   return true;
 }
 

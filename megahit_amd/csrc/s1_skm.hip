@@ -1325,12 +1325,12 @@ bool s1_skm_front(mhx_ctx *c, uint32_t k, SkmFront *f, int pass, int n_passes, i
       return false;
     }
   }
-  c->pre_hist_buf = buf_a;  // (radix_sort: no histogram read of its own)
-  c->pre_hist_n = n;
-  c->pre_hist_passes = (int)passes.size();
-  c->pre_hist_sig = passes_signature(passes);
-  uint32_t *sorted = radix_sort(c, reinterpret_cast<uint32_t *>(buf_a), reinterpret_cast<uint32_t *>(buf_b), n, 4, 1, passes);
-  c->pre_hist_buf = nullptr;
+  SortPrep prep;  // (radix_sort: no histogram read of its own)
+  prep.buf = buf_a;
+  prep.n = n;
+  prep.hist_passes = (int)passes.size();
+  prep.hist_sig = passes_signature(passes);
+  uint32_t *sorted = radix_sort(c, reinterpret_cast<uint32_t *>(buf_a), reinterpret_cast<uint32_t *>(buf_b), n, 4, 1, passes, &prep);
   uint64_t *bounds = c->ws("s1_bucket_bounds", ((size_t)n_bins + 1) * 8 + 64).as<uint64_t>();
   MHX_LAUNCH(c, "s1_skm_bounds", (double)n_bins * 8 * 30,
              hipLaunchKernelGGL(k_skm_bounds, dim3((n_bins + 1 + 255) / 256), dim3(256), 0, st, reinterpret_cast<const uint4 *>(sorted), n, n_bins, bounds, max_bin));
@@ -1392,7 +1392,7 @@ void s1_skm_groups_launch(mhx_ctx *c, bool agg, unsigned grid, const SkmFront &f
 bool count_skm_applies(const mhx_ctx *c, uint32_t k, uint32_t m) {
   const SeqSet &s = c->seqs;
   const long long knob = c->opt("count_skm", 1);
-  if (!knob || !c->opt("s1_skm", 1) || c->global_bases || c->n_parts > 1 || c->filter_on || c->accumulate || c->pos_base || c->count_edges_only) return false;
+  if (!knob || !c->opt("s1_skm", 1) || c->global_bases || c->n_parts > 1 || c->filter_on || c->accumulate || c->pos_base) return false;
   if (k < 19 || k > 21 || m < 1 || m > 2) return false;
   if (!s.n_seqs || s.max_len < k + 1 || (s.n_bases >> 36)) return false;
   if (!s.fixed_len && (double)s.n_bases * 100.0 < (double)c->opt("s1_var_min_fill", 50) * (double)s.n_seqs * s.max_len) return false;
@@ -1407,8 +1407,6 @@ bool count_skm_groups(mhx_ctx *c, uint32_t k, uint32_t m, uint32_t *first_0_out,
   SeqSet &s = c->seqs;
   hipStream_t st = c->stream;
   SkmFront f{};
-  c->gen_first_pass = nullptr;
-  c->pre_hist_buf = nullptr;
   if (!s1_skm_front(c, k, &f, pass, n_passes, 0, true)) return false;
   const uint64_t cus = c->n_cus > 0 ? (uint64_t)c->n_cus : 256;
   const unsigned grid = (unsigned)std::min<uint64_t>(cus, std::max<uint64_t>(1, div_ceil((uint64_t)(f.bin_hi - f.bin_lo), (uint64_t)kSkmBatch)));

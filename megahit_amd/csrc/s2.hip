@@ -1248,7 +1248,7 @@ static int s2_kw(uint32_t k) { return (int)div_ceil(k * 2 + 4, 32); }  // read_t
 int s2_stride(uint32_t k) { return round_up2(s2_kw(k)); }
 
 // items of the local reads -> c->ws("items_a"); returns their number
-uint64_t s2_extract(mhx_ctx *c, uint32_t k, uint32_t m) {
+uint64_t s2_extract(mhx_ctx *c, uint32_t k, uint32_t m, bool filter_in_extract) {
   SeqSet &s = c->seqs;
   if (k < 9 || k > MHX_MAX_K) throw Error("read2sdbg: k out of range [9,255]");
   const int KWv = s2_kw(k), S = round_up2(KWv);
@@ -1267,7 +1267,7 @@ uint64_t s2_extract(mhx_ctx *c, uint32_t k, uint32_t m) {
   uint64_t n_items = 0;
   const unsigned grid = 256 * 8;
   // bucket-range passes: only the items of the kept buckets are counted and written (s2_kept_mask)
-  const uint8_t *drop = c->s2_filter_in_extract ? c->work["filter_lut"].as<uint8_t>() : nullptr;
+  const uint8_t *drop = filter_in_extract ? c->work["filter_lut"].as<uint8_t>() : nullptr;
   if (ns) {
     MHX_DISPATCH_KW(KWv, {
       MHX_LAUNCH(c, "s2_count", (double)s.n_bases * 3 / 8 + (double)ns * 20,
@@ -1413,15 +1413,11 @@ __global__ __launch_bounds__(256) void k_valid_starts(unsigned long long *__rest
   words[w] = v;
 }
 
-bool s2_agg_from_count_applies(mhx_ctx *c, uint32_t k, uint32_t m) {
+bool s2_agg_from_count_applies(const mhx_ctx *c, uint32_t k, uint32_t m) {
   if (!c->opt("s2_agg_from_count", 1) || c->filter_on || c->accumulate || c->n_parts > 1 || c->global_bases) return false;
   if (m < 1 || k < 10 || k > 27) return false;
   if (m > 1 && (k <= 22 || c->solid_plain_k != k || c->solid_plain_m != m)) return false;  // (k <= 22: stage 1 made the aggregated items itself)
-  const bool was = c->count_edges_only;
-  c->count_edges_only = true;
-  const bool ok = count_stream_applies(c, k, m);
-  c->count_edges_only = was;
-  return ok;
+  return count_stream_applies(c, k, m, true);
 }
 // -> false: the count gave up (nothing published: the per-occurrence path runs)
 static bool s2_agg_from_count(mhx_ctx *c, uint32_t k, uint32_t m, mhx_sdbg_result *out) {
@@ -1459,19 +1455,7 @@ static bool s2_agg_from_count(mhx_ctx *c, uint32_t k, uint32_t m, mhx_sdbg_resul
     knobs.put("s1_stream_sub_max", 0);
     knobs.put("s1_stream_max3", 12000);
   }
-  c->count_edges_only = true;
-  c->gen_first_pass = nullptr;
-  bool ok = false;
-  try {
-    ok = count_stream_groups(c, k, m, first, last, hist, &o, nullptr);
-  } catch (...) {
-    c->count_edges_only = false;
-    c->gen_first_pass = nullptr;
-    throw;
-  }
-  c->count_edges_only = false;
-  c->gen_first_pass = nullptr;
-  if (!ok) return false;
+  if (!count_stream_groups(c, k, m, first, last, hist, &o, nullptr, true)) return false;
   std::vector<uint32_t> h_counts(o.grid);
   MHX_HIP(hipMemcpyAsync(h_counts.data(), o.counts, (size_t)o.grid * 4, hipMemcpyDeviceToHost, st));
   MHX_HIP(hipStreamSynchronize(st));

@@ -280,28 +280,22 @@ static SortEnv sort_env() {
   const char *e = getenv("MHX_SORT"), *sh = getenv("MHX_SORT_SHAPE"), *it = getenv("MHX_SORT_ITEMS");
   return SortEnv{e && !strcmp(e, "classic"), sh ? sh : "", it ? atoi(it) : 0};
 }
-// a generated first pass that this call does not consume would leave the buffer without records: never sort that
-static void refuse_unconsumed_generator(mhx_ctx *c, const void *a, const char *who) {
-  if (c->gen_first_pass && c->gen_buf == a) {
-    c->gen_first_pass = nullptr;
-    throw Error(std::string(who) + ": the records of this buffer are to be made by a generated first pass, which this sort path cannot run");
-  }
+// a generated first pass that this call does not run would leave the buffer without records: never sort that
+static void refuse_unconsumed_generator(const SortPrep &prep, const char *who) {
+  if (prep.gen) throw Error(std::string(who) + ": the records of this buffer are to be made by a generated first pass, which this sort path cannot run");
 }
 
 // chained-scan sort (8/12/16-byte records, <= 8 passes); MHX_SORT=classic selects the histogram + scan + scatter passes
 template <int S, int NI, int UT>
-static uint32_t *radix_sort_onesweep(mhx_ctx *c, uint32_t *a, uint32_t *b, uint64_t n, int key_words, const std::vector<SortPass> &passes) {
+static uint32_t *radix_sort_onesweep(mhx_ctx *c, uint32_t *a, uint32_t *b, uint64_t n, int key_words, const std::vector<SortPass> &passes,
+                                     const SortPrep &prep) {
   const int P = (int)passes.size();
+  const bool prep_fits = prep.buf == (const void *)a && prep.n == n;
   // a generated first pass (s1.hip): valid for exactly this buffer, item count and unit shape
-  std::function<void(const OnesweepLaunch &)> gen;
-  // (gen_slots: item slots the generator walks — more than n when it drops the items of filtered-out lv1 buckets)
-  uint64_t gen_slots = n;
-  if (c->gen_first_pass && c->gen_buf == (const void *)a && c->gen_n == n && S == 3 && NI == 8 && UT == 3) {
-    gen = c->gen_first_pass;
-    gen_slots = std::max<uint64_t>(c->gen_slots, n);
-  }
-  if (!gen) refuse_unconsumed_generator(c, a, "radix sort (chained scan)");
-  c->gen_first_pass = nullptr;
+  const bool gen = prep.gen && prep_fits && S == 3 && NI == 8 && UT == 3;
+  if (!gen) refuse_unconsumed_generator(prep, "radix sort (chained scan)");
+  // (item slots the generator walks — more than n when it drops the items of filtered-out lv1 buckets)
+  const uint64_t gen_slots = gen ? std::max<uint64_t>(prep.gen_slots, n) : n;
   // Per-XCD tickets (see k_radix_onesweep): a unit may wait for a unit whose block id is up to 127 higher, so the scheme needs
   // the whole 8-XCD part with a couple of hundred workgroups resident at once (MI355X in SPX mode: 256 CUs x 3-4 workgroups).
   // On a partition (CPX: 32 CUs, one XCD) or an unknown device the single ticket counter is used: its look-back only ever
@@ -334,9 +328,7 @@ static uint32_t *radix_sort_onesweep(mhx_ctx *c, uint32_t *a, uint32_t *b, uint6
   std::vector<DigitSpec> all(P);
   for (int p = 0; p < P; ++p) all[p] = spec_of_pass(passes[p], key_words);
   // extraction may have taken the digit histograms while it produced the records (s1.hip): then no read at all
-  const bool pre = c->pre_hist_buf == (const void *)a && c->pre_hist_n == n && c->pre_hist_passes == P && P <= kMaxFusedPasses &&
-                   c->pre_hist_sig == passes_signature(passes);
-  c->pre_hist_buf = nullptr;
+  const bool pre = prep_fits && prep.hist_passes == P && P > 0 && P <= kMaxFusedPasses && prep.hist_sig == passes_signature(passes);
   if (gen && !pre) throw Error("radix sort: a generated first pass needs the digit histograms of the plan (pre-hist)");
   if (pre) MHX_HIP(hipMemcpyAsync(gh, c->work["sort_pre_hist"].p, (size_t)P * 256 * 8, hipMemcpyDeviceToDevice, st));
   for (int p0 = 0; p0 < P && !pre; p0 += kMaxFusedPasses) {  // one read of the input per 16 passes
@@ -360,7 +352,7 @@ static uint32_t *radix_sort_onesweep(mhx_ctx *c, uint32_t *a, uint32_t *b, uint6
     if (p == 0 && gen) {  // the records of the first pass are made on the fly (no input array): the generator's owner launches
       static const std::string nm_gen = nm_scat + "_gen";
       MHX_LAUNCH(c, nm_gen.c_str(), bytes,
-                 gen(OnesweepLaunch{(unsigned)n_units_gen, st, b, gen_slots, all[p], nb, starts + p * 256, status, tickets + p * 8,
+                 prep.gen(OnesweepLaunch{(unsigned)n_units_gen, st, b, gen_slots, all[p], nb, starts + p * 256, status, tickets + p * 8,
                                     tickets + kErrSlot, (unsigned long long)(p + 1), xcd_units, unit_runs ? 1 : 0, wi}));
     } else if (unit_runs) {
       if constexpr (kHasUnitRuns) {
@@ -406,13 +398,8 @@ static uint32_t *radix_sort_onesweep(mhx_ctx *c, uint32_t *a, uint32_t *b, uint6
 
 template <int S, int NI>
 static uint32_t *radix_sort_impl2(mhx_ctx *c, uint32_t *a, uint32_t *b, uint64_t n, int key_words,
-                                  const std::vector<SortPass> &passes) {
-  if (n == 0) {
-    // nothing to sort: a generated first pass armed for this buffer (a bucket-range pass or a rank that keeps no record)
-    // is spent with it — left armed it would meet the next sort of the same buffer
-    if (c->gen_first_pass && c->gen_buf == (const void *)a) c->gen_first_pass = nullptr;
-    return a;
-  }
+                                  const std::vector<SortPass> &passes, const SortPrep &prep) {
+  if (n == 0) return a;
   const SortEnv env = sort_env();
   if constexpr (S <= 8 && NI == default_items<S>()) {
     const bool classic = env.classic;
@@ -423,18 +410,18 @@ static uint32_t *radix_sort_impl2(mhx_ctx *c, uint32_t *a, uint32_t *b, uint64_t
         // (classic 3-kernel passes: 63 + 20 histogram): 2048-record tiles halve the number of scattered runs, units of
         // 4-6 K records amortise the look-back, more registers cost occupancy.
         const std::string shape = !env.shape.empty() ? env.shape : (S <= 3 ? "8x3" : "8x2");
-        if (shape == "8x2") return radix_sort_onesweep<S, 8, 2>(c, a, b, n, key_words, passes);
-        if (shape == "4x4") return radix_sort_onesweep<S, 4, 4>(c, a, b, n, key_words, passes);
-        if (shape == "16x1") return radix_sort_onesweep<S, 16, 1>(c, a, b, n, key_words, passes);
-        if (shape == "8x4" && S <= 3) return radix_sort_onesweep<S, 8, 4>(c, a, b, n, key_words, passes);
-        if (shape == "8x3" || S <= 3) return radix_sort_onesweep<S, 8, 3>(c, a, b, n, key_words, passes);
-        return radix_sort_onesweep<S, 8, 2>(c, a, b, n, key_words, passes);
+        if (shape == "8x2") return radix_sort_onesweep<S, 8, 2>(c, a, b, n, key_words, passes, prep);
+        if (shape == "4x4") return radix_sort_onesweep<S, 4, 4>(c, a, b, n, key_words, passes, prep);
+        if (shape == "16x1") return radix_sort_onesweep<S, 16, 1>(c, a, b, n, key_words, passes, prep);
+        if (shape == "8x4" && S <= 3) return radix_sort_onesweep<S, 8, 4>(c, a, b, n, key_words, passes, prep);
+        if (shape == "8x3" || S <= 3) return radix_sort_onesweep<S, 8, 3>(c, a, b, n, key_words, passes, prep);
+        return radix_sort_onesweep<S, 8, 2>(c, a, b, n, key_words, passes, prep);
       } else {
-        return radix_sort_onesweep<S, 4, 2>(c, a, b, n, key_words, passes);  // 24/32-byte records: 8 per thread in registers
+        return radix_sort_onesweep<S, 4, 2>(c, a, b, n, key_words, passes, prep);  // 24/32-byte records: 8 per thread in registers
       }
     }
   }
-  refuse_unconsumed_generator(c, a, "radix sort (classic passes)");
+  refuse_unconsumed_generator(prep, "radix sort (classic passes)");
   const uint64_t n_chunks = div_ceil(n, SortCfg<S, NI>::kChunk);
   uint32_t *hist = c->ws("sort_hist", n_chunks * 256 * 4).as<uint32_t>();
   uint64_t *offs = c->ws("sort_offs", n_chunks * 256 * 8).as<uint64_t>();
@@ -497,18 +484,18 @@ static uint32_t *radix_sort_impl2(mhx_ctx *c, uint32_t *a, uint32_t *b, uint64_t
 // tile-shape selection: MHX_SORT_ITEMS=8|16 overrides the default for 8- and 16-byte records (tuning knob)
 template <int S>
 static uint32_t *radix_sort_impl(mhx_ctx *c, uint32_t *a, uint32_t *b, uint64_t n, int key_words,
-                                 const std::vector<SortPass> &passes) {
+                                 const std::vector<SortPass> &passes, const SortPrep &prep) {
   if constexpr (S <= 4) {
     const SortEnv env = sort_env();
     const int items = env.items ? env.items : default_items<S>();
-    if (items == 2) return radix_sort_impl2<S, 2>(c, a, b, n, key_words, passes);
-    if (items == 3) return radix_sort_impl2<S, 3>(c, a, b, n, key_words, passes);
-    if (items == 6) return radix_sort_impl2<S, 6>(c, a, b, n, key_words, passes);
-    if (items == 16) return radix_sort_impl2<S, 16>(c, a, b, n, key_words, passes);
-    if (items == 8) return radix_sort_impl2<S, 8>(c, a, b, n, key_words, passes);
-    if (items == 12) return radix_sort_impl2<S, 12>(c, a, b, n, key_words, passes);
+    if (items == 2) return radix_sort_impl2<S, 2>(c, a, b, n, key_words, passes, prep);
+    if (items == 3) return radix_sort_impl2<S, 3>(c, a, b, n, key_words, passes, prep);
+    if (items == 6) return radix_sort_impl2<S, 6>(c, a, b, n, key_words, passes, prep);
+    if (items == 16) return radix_sort_impl2<S, 16>(c, a, b, n, key_words, passes, prep);
+    if (items == 8) return radix_sort_impl2<S, 8>(c, a, b, n, key_words, passes, prep);
+    if (items == 12) return radix_sort_impl2<S, 12>(c, a, b, n, key_words, passes, prep);
   }
-  return radix_sort_impl2<S, default_items<S>()>(c, a, b, n, key_words, passes);
+  return radix_sort_impl2<S, default_items<S>()>(c, a, b, n, key_words, passes, prep);
 }
 
 // ---------------------------------------------------------------------------
@@ -606,10 +593,11 @@ static bool seg_finish(mhx_ctx *c, const uint32_t *in, uint32_t *out, uint64_t n
 // k_seg_finish when that saves passes, else (or when a segment outgrows the look-ahead) the plain LSD plan `passes`.
 // The caller vouches that `passes` orders the records exactly as the whole key does (bits it leaves out are constant or
 // may order equal keys arbitrarily).
-uint32_t *sort_whole_key(mhx_ctx *c, uint32_t *a, uint32_t *b, uint64_t n, int stride, int key_words, const std::vector<SortPass> &passes) {
+uint32_t *sort_whole_key(mhx_ctx *c, uint32_t *a, uint32_t *b, uint64_t n, int stride, int key_words, const std::vector<SortPass> &passes,
+                         SortPrep *prep) {
   const int mode = (int)c->opt("sort_hybrid", 1);  // 0: never, 1: when the cost model says so, 2: always (tests)
   const uint64_t min_n = (uint64_t)c->opt("sort_hybrid_min", 1 << 16);
-  if (!mode || n < min_n || n >= (1ull << 40)) return radix_sort(c, a, b, n, stride, key_words, passes);
+  if (!mode || n < min_n || n >= (1ull << 40)) return radix_sort(c, a, b, n, stride, key_words, passes, prep);
   // Cost model, picoseconds per record on MI355X (measured at 0.8-1.2 x 10^8 records, round 3, profiles/r03_bench_klist.json):
   // an LSD pass moves the record twice, ~3 ps per 32-bit word (0.71 ms for 117 M 8-byte records, 1.9 ms for 82 M 40-byte
   // ones); the finish kernel moves it once and reads a couple of key words of every neighbour in its segment:
@@ -635,8 +623,8 @@ uint32_t *sort_whole_key(mhx_ctx *c, uint32_t *a, uint32_t *b, uint64_t n, int s
     while (best_bits < 32 && (double)n / 4.0 > (double)(1ull << best_bits)) best_bits += 8;
   }
   if (const long long f = c->opt("sort_hybrid_bits", 0)) best_bits = (int)std::min<long long>(32, std::max<long long>(1, f));
-  if (!best_bits) return radix_sort(c, a, b, n, stride, key_words, passes);
-  uint32_t *sorted = radix_sort(c, a, b, n, stride, key_words, make_passes(key_words, key_words * 32 - best_bits, key_words * 32));
+  if (!best_bits) return radix_sort(c, a, b, n, stride, key_words, passes, prep);
+  uint32_t *sorted = radix_sort(c, a, b, n, stride, key_words, make_passes(key_words, key_words * 32 - best_bits, key_words * 32), prep);
   uint32_t *other = sorted == a ? b : a;
   if (seg_finish(c, sorted, other, n, stride, key_words, best_bits)) return other;
   return radix_sort(c, sorted, other, n, stride, key_words, passes);  // a segment beyond the walk limit: every bit by LSD passes
@@ -688,7 +676,7 @@ void partition_by_owner(mhx_ctx *c, const uint32_t *a, uint32_t *b, uint64_t n, 
 }
 
 // true when radix_sort(stride 3, these passes) runs the chained-scan passes with the default 8x3 unit shape, i.e. when it
-// will take a generated first pass (mhx_ctx::gen_first_pass)
+// will take a generated first pass (SortPrep::gen)
 bool sort_takes_generated_first_pass(const mhx_ctx *c, uint64_t n, int stride, const std::vector<SortPass> &passes) {
   (void)c;
   const SortEnv env = sort_env();  // (the same per-call decision radix_sort_impl2 takes)
@@ -699,19 +687,21 @@ bool sort_takes_generated_first_pass(const mhx_ctx *c, uint64_t n, int stride, c
 }
 
 uint32_t *radix_sort(mhx_ctx *c, uint32_t *a, uint32_t *b, uint64_t n, int stride, int key_words,
-                     const std::vector<SortPass> &passes) {
+                     const std::vector<SortPass> &passes, SortPrep *prep_io) {
+  SortPrep prep;  // spent by this sort, whichever way it ends
+  if (prep_io) std::swap(prep, *prep_io);
   switch (stride) {
-    case 2: return radix_sort_impl<2>(c, a, b, n, key_words, passes);
-    case 3: return radix_sort_impl<3>(c, a, b, n, key_words, passes);
-    case 4: return radix_sort_impl<4>(c, a, b, n, key_words, passes);
-    case 6: return radix_sort_impl<6>(c, a, b, n, key_words, passes);
-    case 8: return radix_sort_impl<8>(c, a, b, n, key_words, passes);
-    case 10: return radix_sort_impl<10>(c, a, b, n, key_words, passes);
-    case 12: return radix_sort_impl<12>(c, a, b, n, key_words, passes);
-    case 14: return radix_sort_impl<14>(c, a, b, n, key_words, passes);
-    case 16: return radix_sort_impl<16>(c, a, b, n, key_words, passes);
-    case 18: return radix_sort_impl<18>(c, a, b, n, key_words, passes);
-    case 20: return radix_sort_impl<20>(c, a, b, n, key_words, passes);
+    case 2: return radix_sort_impl<2>(c, a, b, n, key_words, passes, prep);
+    case 3: return radix_sort_impl<3>(c, a, b, n, key_words, passes, prep);
+    case 4: return radix_sort_impl<4>(c, a, b, n, key_words, passes, prep);
+    case 6: return radix_sort_impl<6>(c, a, b, n, key_words, passes, prep);
+    case 8: return radix_sort_impl<8>(c, a, b, n, key_words, passes, prep);
+    case 10: return radix_sort_impl<10>(c, a, b, n, key_words, passes, prep);
+    case 12: return radix_sort_impl<12>(c, a, b, n, key_words, passes, prep);
+    case 14: return radix_sort_impl<14>(c, a, b, n, key_words, passes, prep);
+    case 16: return radix_sort_impl<16>(c, a, b, n, key_words, passes, prep);
+    case 18: return radix_sort_impl<18>(c, a, b, n, key_words, passes, prep);
+    case 20: return radix_sort_impl<20>(c, a, b, n, key_words, passes, prep);
     default: throw Error("radix_sort: unsupported record stride");
   }
 }
