@@ -230,7 +230,7 @@ enum mhx_buffer {
   MHX_BUF_SDBG_RS_TIP_L2 = 34,  /* rank-only structure over tip */
   MHX_BUF_SDBG_RS_TIP_L1 = 35,
   MHX_BUF_LIB_RECORDS = 40,     /* uint32[]: read-library records (len + packed words per read) of mhx_fastx_to_records */
-  /* the unitig graph of mhx_sdbg_unitigs (below), kept in HBM for the graph-cleaning steps */
+  /* the unitig graph of mhx_sdbg_unitigs (below), kept in HBM for the graph-cleaning steps (mhx_unitig_*, below) */
   MHX_BUF_UNITIG_VERTICES = 41, /* mhx_unitig_vertex[n_vertices], the reference's vertex order on one thread */
   MHX_BUF_UNITIG_SEQ = 42,      /* char[n_bases]: every vertex's contig text ('ACGT', before FoldPalindrome), back to back */
   MHX_BUF_UNITIG_OFFSET = 43    /* uint64[n_vertices + 1]: where vertex v's text starts in MHX_BUF_UNITIG_SEQ */
@@ -350,6 +350,27 @@ typedef struct {
   uint64_t n_bases;       /* size of MHX_BUF_UNITIG_SEQ */
 } mhx_unitig_result;
 int mhx_sdbg_unitigs(mhx_ctx *, const mhx_sdbg_index_info *info, mhx_unitig_result *out);
+/* Graph cleaning on that unitig graph, in place on MHX_BUF_UNITIG_VERTICES and MHX_BUF_SDBG_INVALID: together they are
+ * `assemble --bubble_level 0 --prune_level 0 --cleaning_rounds N` (main_assemble.cpp:182-249).  The result is the
+ * reference's at -t 1 and does not depend on any thread count.  Valid only after mhx_sdbg_unitigs on the same index (any
+ * other state returns an error); between these calls MHX_BUF_UNITIG_SEQ / _OFFSET and the vertices' STANDALONE flags are
+ * stale until mhx_unitig_finish.
+ *   mhx_unitig_disconnect_weak_links  DisconnectWeakLinks (assembly/weak_link_remover.cpp): at every vertex end with two or
+ *       more out-neighbours, a neighbour whose average depth is <= ratio * the neighbours' total is flagged on the strand it
+ *       is entered by; then UnitigGraph::Refresh (unitig_graph.cpp:140-355: flagged vertices lose their end edges, deleted
+ *       ones all their edges, linear paths and cycles merge, survivors are compacted in index order).  *n_flagged = the
+ *       (vertex, strand) flags set: the reference's "Number unitigs disconnected".
+ *   mhx_unitig_remove_tips  RemoveTips on the unitig graph (assembly/tip_remover.cpp): thresholds 2, 4, 8, ... below
+ *       max_tip_len, each followed by a Refresh; a vertex shorter than the threshold goes when it is a loop, has no
+ *       neighbour, or has one neighbour in all whose average depth is > 8 times its own.  *n_removed = "Tips removed".
+ *   mhx_unitig_finish  flags (MHX_UNITIG_STANDALONE from the degrees on the cleaned graph), MHX_BUF_UNITIG_SEQ and
+ *       MHX_BUF_UNITIG_OFFSET for the vertex table as it is now.  total_depth is no longer a sum of multiplicities once a
+ *       vertex was trimmed (lround(average * new length), unitig_graph.cpp:191-193).
+ * The CLI (`mhx_core assemble`) runs these rounds only when MHX_ASSEMBLE_CLEAN=1 is in its environment (and only at
+ * --bubble_level 0 --prune_level 0); otherwise such command lines are forwarded to MHX_REF_CORE.  MHX_ASSEMBLE_REF=1 wins. */
+int mhx_unitig_disconnect_weak_links(mhx_ctx *, const mhx_sdbg_index_info *info, double ratio, uint64_t *n_flagged);
+int mhx_unitig_remove_tips(mhx_ctx *, const mhx_sdbg_index_info *info, uint32_t max_tip_len, uint64_t *n_removed);
+int mhx_unitig_finish(mhx_ctx *, const mhx_sdbg_index_info *info, mhx_unitig_result *out);
 /* install an SdBG produced elsewhere (e.g. read back from .sdbg.* files: bucket byte ranges back to back) as the handle's
  * current SdBG; the four tables have 65536 entries (starting byte, items, tips, large multiplicities per bucket) */
 int mhx_sdbg_load_bytes(mhx_ctx *, const uint8_t *bytes, uint64_t n_bytes, const uint64_t *bucket_offset, const uint64_t *bucket_items,

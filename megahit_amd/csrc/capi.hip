@@ -544,6 +544,8 @@ int mhx_trim(mhx_ctx *c) {
     MHX_HIP(hipStreamSynchronize(c->stream));
     for (auto &kv : c->work) kv.second.release();
     c->work.clear();
+    // the unitig graph's cleaning state (owner map, flags, the edge ranking the owner map comes from) lives in workspaces
+    c->ut_ready = c->ut_owner = false;
     // the sorted-items view aliases a workspace
     auto it = c->results.find(MHX_BUF_SORTED_ITEMS);
     if (it != c->results.end()) c->results.erase(it);
@@ -564,6 +566,7 @@ int mhx_reset(mhx_ctx *c) {
     auto it = c->results.find(MHX_BUF_SORTED_ITEMS);  // a view into a workspace, not an allocation
     if (it != c->results.end()) c->results.erase(it);
     c->sorted_item_words = 0;
+    c->ut_ready = c->ut_owner = false;  // the vertex table is forgotten with the other results
     c->my_part = 0;
     c->n_parts = 1;
     c->part_begin.clear();
@@ -856,6 +859,25 @@ int mhx_sdbg_unitigs(mhx_ctx *c, const mhx_sdbg_index_info *info, mhx_unitig_res
     MHX_HIP(hipSetDevice(c->device));
     if (!info || !out) throw mhx::Error("sdbg_unitigs: bad arguments");
     mhx::sdbg_unitigs(c, info, out);
+  })
+}
+int mhx_unitig_disconnect_weak_links(mhx_ctx *c, const mhx_sdbg_index_info *info, double ratio, uint64_t *n_flagged) {
+  MHX_TRY({
+    MHX_HIP(hipSetDevice(c->device));
+    mhx::unitig_disconnect_weak_links(c, info, ratio, n_flagged);
+  })
+}
+int mhx_unitig_remove_tips(mhx_ctx *c, const mhx_sdbg_index_info *info, uint32_t max_tip_len, uint64_t *n_removed) {
+  MHX_TRY({
+    MHX_HIP(hipSetDevice(c->device));
+    mhx::unitig_remove_tips(c, info, max_tip_len, n_removed);
+  })
+}
+int mhx_unitig_finish(mhx_ctx *c, const mhx_sdbg_index_info *info, mhx_unitig_result *out) {
+  MHX_TRY({
+    MHX_HIP(hipSetDevice(c->device));
+    if (!out) throw mhx::Error("unitig_finish: bad arguments");
+    mhx::unitig_finish(c, info, out);
   })
 }
 int mhx_sdbg_load_bytes(mhx_ctx *c, const uint8_t *bytes, uint64_t n_bytes, const uint64_t *bucket_offset, const uint64_t *bucket_items,

@@ -1209,9 +1209,12 @@ int main_iterate(int argc, char **argv) {
 
 // ---------------------------------------------------------------------------
 // assemble (reference src/main_assemble.cpp) when its options ask for nothing beyond tip trimming, the unitig graph and
-// contig output: --bubble_level 0 --prune_level 0 --cleaning_rounds 0 (every other option set goes to the reference).
+// contig output: --bubble_level 0 --prune_level 0 --cleaning_rounds 0 — and, with MHX_ASSEMBLE_CLEAN=1 in the environment,
+// with --cleaning_rounds N >= 1 as well: the rounds of RemoveTips and DisconnectWeakLinks on the unitig graph
+// (main_assemble.cpp:182-249 at bubble level 0 and prune level 0).  Every other option set goes to the reference.
 // The SdBG files are read back into HBM, indexed (mhx_sdbg_build_index), trimmed (mhx_sdbg_remove_tips), turned into the
-// unitig graph and its contig text (mhx_sdbg_unitigs); the host folds palindromes and writes the ContigWriter files.
+// unitig graph and its contig text (mhx_sdbg_unitigs), cleaned in place (mhx_unitig_*); the host folds palindromes and
+// writes the ContigWriter files.  The cleaned result is the reference's at -t 1 whatever -t says.
 void add_assemble_options(Options &o) {  // main_assemble.cpp:66-101
   o.add("sdbg_name", "s", false, "");
   o.add("output_prefix", "o", false, "out");
@@ -1241,7 +1244,10 @@ bool assemble_on_gpu(int argc, char **argv) {
     return false;  // the reference reports it
   }
   if (o.get("sdbg_name").empty()) return false;
-  return atoi(o.get("bubble_level").c_str()) == 0 && atoi(o.get("prune_level").c_str()) == 0 && atoi(o.get("cleaning_rounds").c_str()) == 0;
+  if (atoi(o.get("bubble_level").c_str()) != 0 || atoi(o.get("prune_level").c_str()) != 0) return false;
+  const int rounds = atoi(o.get("cleaning_rounds").c_str());
+  if (rounds <= 0) return rounds == 0;
+  return getenv("MHX_ASSEMBLE_CLEAN") && atoi(getenv("MHX_ASSEMBLE_CLEAN")) != 0;  // the cleaning rounds on the GPU: opt-in
 }
 void revcomp_ascii(std::string &s) {  // contig_output.cpp:12-42
   auto comp = [](char c) { return c == 'A' ? 'T' : c == 'C' ? 'G' : c == 'G' ? 'C' : 'A'; };
@@ -1300,10 +1306,8 @@ int main_assemble(int argc, char **argv) {
   CK(mhx_sdbg_unitigs(c, &ix, &ur));
   info("Graph size without loops: %llu, palindrome: %llu", (unsigned long long)(ur.n_vertices - ur.n_loops), (unsigned long long)ur.n_palindromes);
   info("unitig graph size: %llu, time for building: %.3f", (unsigned long long)ur.n_vertices, t.lap());
-  const std::vector<mhx_unitig_vertex> vtx = fetch<mhx_unitig_vertex>(c, MHX_BUF_UNITIG_VERTICES);
-  const std::vector<char> seq = fetch<char>(c, MHX_BUF_UNITIG_SEQ);
-  const std::vector<uint64_t> off = fetch<uint64_t>(c, MHX_BUF_UNITIG_OFFSET);
-  {  // CalcAndPrintStat (contig_stat.h:15-47): contig lengths = length + k; std::map order of the names
+  // CalcAndPrintStat (contig_stat.h:15-47): contig lengths = length + k; std::map order of the names
+  auto print_stat = [&](const std::vector<mhx_unitig_vertex> &vtx) {
     std::map<uint64_t, uint64_t> hist;
     uint64_t total = 0, n_looped = 0, n_isolated = 0;
     for (const mhx_unitig_vertex &v : vtx) {
@@ -1324,7 +1328,33 @@ int main_assemble(int argc, char **argv) {
     info("Max: %llu, Min: %llu, N50: %llu, number contigs: %llu, number isolated: %llu, number looped: %llu, total size: %llu, ",
          (unsigned long long)(hist.empty() ? 0 : hist.rbegin()->first), (unsigned long long)(hist.empty() ? 0 : hist.begin()->first),
          (unsigned long long)n50, (unsigned long long)vtx.size(), (unsigned long long)n_isolated, (unsigned long long)n_looped, (unsigned long long)total);
+  };
+  // graph cleaning (main_assemble.cpp:182-249 with bubble level 0 and prune level 0)
+  const int cleaning_rounds = atoi(o.get("cleaning_rounds").c_str());
+  if (cleaning_rounds > 0) {
+    print_stat(fetch<mhx_unitig_vertex>(c, MHX_BUF_UNITIG_VERTICES));
+    const double disconnect_ratio = atof(o.get("disconnect_ratio").c_str());
+    for (int round = 1; round <= cleaning_rounds; ++round) {
+      info("Graph cleaning round %d", round);
+      bool changed = false;
+      if (round > 1) {
+        uint64_t n_tips = 0;
+        CK(mhx_unitig_remove_tips(c, &ix, (uint32_t)max_tip_len, &n_tips));
+        changed |= n_tips > 0;
+        info("Tips removed: %llu, time: %.3f", (unsigned long long)n_tips, t.lap());
+      }
+      uint64_t n_disconnected = 0;
+      CK(mhx_unitig_disconnect_weak_links(c, &ix, disconnect_ratio, &n_disconnected));
+      info("Number unitigs disconnected: %llu, time: %.3f", (unsigned long long)n_disconnected, t.lap());
+      changed |= n_disconnected > 0;
+      if (!changed) break;
+    }
+    CK(mhx_unitig_finish(c, &ix, &ur));
   }
+  const std::vector<mhx_unitig_vertex> vtx = fetch<mhx_unitig_vertex>(c, MHX_BUF_UNITIG_VERTICES);
+  const std::vector<char> seq = fetch<char>(c, MHX_BUF_UNITIG_SEQ);
+  const std::vector<uint64_t> off = fetch<uint64_t>(c, MHX_BUF_UNITIG_OFFSET);
+  print_stat(vtx);
   // OutputContigs (contig_output.cpp:62-119) with ContigWriter's record format
   std::vector<mhxio::ContigRecord> main_recs, final_recs;
   std::deque<std::string> folded;
@@ -1350,7 +1380,7 @@ int main_assemble(int argc, char **argv) {
   }
   mhxio::write_contigs(prefix + ".contigs.fa", f.k, main_recs, n_threads);
   mhxio::write_contigs(prefix + ".final.contigs.fa", f.k, final_recs, n_threads);
-  mhxio::write_contigs(prefix + ".bubble_seq.fa", f.k, {}, 1);  // no cleaning round: no bubble
+  mhxio::write_contigs(prefix + ".bubble_seq.fa", f.k, {}, 1);  // bubble level 0: no bubble
   info("Time to output: %.4f", t.lap());
   return finish(c);
 }

@@ -103,6 +103,10 @@ struct mhx_ctx {
   uint64_t n_marks = 0;          // multi-GPU, sparse marks: positions in ws("s1_marks") waiting to be routed
   uint64_t dist_local_solid = 0; // multi-GPU, sparse marks: solid occurrences in the local reads after the marks arrived
   bool dist_s2_agg = false;  // the items of the current multi-GPU stage-2 exchange are aggregated ones
+  // the unitig graph mhx_sdbg_unitigs left in MHX_BUF_UNITIG_VERTICES (sdbg_unitig.hip) and the cleaning steps change
+  // (unitig_clean.hip): valid until the SdBG or its index is replaced.  ut_owner: ws "uc_owner" maps every edge to its vertex
+  bool ut_ready = false, ut_owner = false;
+  uint64_t ut_edges = 0, ut_nv = 0;
   // tuning knobs (mhx_set_option): explicit value, else environment MHX_<NAME>, else the default
   std::map<std::string, long long> options;
   // tuned defaults of this installation: `name = value` lines of mhx_tuning.conf beside libmhx.so (MHX_TUNING_FILE names
@@ -289,6 +293,10 @@ void s1_apply_marks(mhx_ctx *c, const unsigned long long *recv, uint64_t n);
 int sdbg_build_index(mhx_ctx *c, uint32_t k, mhx_sdbg_index_info *out);
 int sdbg_remove_tips(mhx_ctx *c, const mhx_sdbg_index_info *info, int max_tip_len, uint64_t *n_removed);
 int sdbg_unitigs(mhx_ctx *c, const mhx_sdbg_index_info *info, mhx_unitig_result *out);
+int sdbg_unitig_text(mhx_ctx *c, const mhx_sdbg_index_info *info, uint64_t nv, uint64_t n_loop, mhx_unitig_result *out);
+int unitig_disconnect_weak_links(mhx_ctx *c, const mhx_sdbg_index_info *info, double ratio, uint64_t *n_flagged);
+int unitig_remove_tips(mhx_ctx *c, const mhx_sdbg_index_info *info, uint32_t max_tip_len, uint64_t *n_removed);
+int unitig_finish(mhx_ctx *c, const mhx_sdbg_index_info *info, mhx_unitig_result *out);
 int iterate_edges(mhx_ctx *c, uint32_t k, uint32_t step, const uint32_t *ctg_words, uint64_t ctg_n_words, uint64_t n_ctg, const uint64_t *ctg_start,
                   mhx_iterate_result *out);
 int fastx_to_records(mhx_ctx *c, const char *text1, uint64_t n1, const char *text2, uint64_t n2, mhx_fastx_result *out);

@@ -241,6 +241,7 @@ static RsResult build_rs(mhx_ctx *c, const unsigned long long *words, uint64_t s
 
 int sdbg_build_index(mhx_ctx *c, uint32_t k, mhx_sdbg_index_info *out) {
   hipStream_t st = c->stream;
+  c->ut_ready = c->ut_owner = false;  // a unitig graph of the previous index is gone
   auto need = [&](int which) -> DevBuf & {
     auto it = c->results.find(which);
     if (it == c->results.end() || !it->second.p) throw Error("sdbg_build_index: no SdBG in the handle (run stage 2 / seq2sdbg or mhx_sdbg_load_bytes first)");

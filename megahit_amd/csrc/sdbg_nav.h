@@ -179,6 +179,20 @@ static __device__ int sd_outgoings(const DevSdbg &g, uint64_t e, int mode, uint6
   } while (next != kNull && !sd_last_or_tip(g, next));
   return outdeg;
 }
+// OutgoingEdges (sdbg.h:354-356): all outgoing edges in the reference's order (from Forward(e) downwards), at most 4
+static __device__ int sd_outgoings_all(const DevSdbg &g, uint64_t e, uint64_t out[4]) {
+  if (!sd_valid(g, e)) return -1;
+  int outdeg = 0;
+  uint64_t next = sd_forward(g, e);
+  do {
+    if (sd_valid(g, next)) {
+      if (outdeg < 4) out[outdeg] = next;
+      ++outdeg;
+    }
+    --next;
+  } while (next != kNull && !sd_last_or_tip(g, next));
+  return outdeg < 4 ? outdeg : 4;
+}
 static __device__ __forceinline__ bool sd_indeg_zero(const DevSdbg &g, uint64_t e) { return sd_incomings(g, e, kMustEq0, nullptr) == 0; }
 static __device__ __forceinline__ bool sd_outdeg_zero(const DevSdbg &g, uint64_t e) { return sd_outgoings(g, e, kMustEq0, nullptr) == 0; }
 static __device__ __forceinline__ uint64_t sd_unique_prev(const DevSdbg &g, uint64_t e) {

@@ -124,6 +124,7 @@ DevSdbg dev_sdbg(mhx_ctx *c, const mhx_sdbg_index_info *info, const char *who) {
 int sdbg_remove_tips(mhx_ctx *c, const mhx_sdbg_index_info *info, int max_tip_len, uint64_t *n_removed) {
   hipStream_t st = c->stream;
   DevSdbg g = dev_sdbg(c, info, "sdbg_remove_tips");
+  c->ut_ready = c->ut_owner = false;  // a unitig graph built before this trimming no longer describes the SdBG
   if (n_removed) *n_removed = 0;
   if (!g.n || max_tip_len <= 0) return 0;
   const uint64_t nw = div_ceil(g.n, 64);

@@ -19,39 +19,16 @@
 //   text      ToUniqueFormat picks the strand that begins at min(b, rb); every edge of that strand's chain writes its
 //             character at offset[v] + k + rank, one thread per vertex writes GetLabel(begin).
 #include "sdbg_nav.h"
+#include "unitig_rank.h"
 
 namespace mhx {
 
 namespace {
 
-// one record per edge while ranking: the current jump target, the sum / minimum over (anc, i], the edges in (anc, i], the
-// chain head once anc is null.  32 bytes: one gather per jump.
-struct Rk {
-  uint64_t anc, val, d, head;
-};
-enum { kSum = 0, kMin = 1 };
-
-__device__ __forceinline__ void push_list(bool take, uint64_t v, uint64_t *__restrict__ list, unsigned long long *__restrict__ cnt) {
-  const uint64_t m = __ballot(take);
-  if (!m) return;
-  const int lane = lane_id();
-  const int leader = __builtin_ctzll(m);
-  unsigned long long base = 0;
-  if (lane == leader) base = atomicAdd(cnt, (unsigned long long)__builtin_popcountll(m));
-  base = __shfl(base, leader);
-  if (take) list[base + __builtin_popcountll(m & ((1ull << lane) - 1))] = v;
-}
-
 __global__ __launch_bounds__(256) void k_ut_links(DevSdbg g, uint64_t *__restrict__ succ) {
   const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= g.n) return;
   succ[i] = sd_valid(g, i) ? sd_next_simple(g, i) : kNull;
-}
-__global__ __launch_bounds__(256) void k_ut_pred(const uint64_t *__restrict__ succ, uint64_t n, uint64_t *__restrict__ pred) {
-  const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  const uint64_t s = succ[i];
-  if (s != kNull) pred[s] = i;
 }
 // first ranking: every valid edge; roots (no predecessor) are final at once
 __global__ __launch_bounds__(256) void k_ut_rank_init(DevSdbg g, const uint64_t *__restrict__ pred, Rk *__restrict__ rk, uint64_t *__restrict__ list,
@@ -64,47 +41,6 @@ __global__ __launch_bounds__(256) void k_ut_rank_init(DevSdbg g, const uint64_t 
     take = p != kNull;
   }
   push_list(take, i, list, cnt);
-}
-// one jump of every listed edge: reads rk only, writes nx[t]
-template <int MODE>
-__global__ __launch_bounds__(256) void k_ut_jump(const Rk *__restrict__ rk, const uint64_t *__restrict__ list, uint64_t n_act, Rk *__restrict__ nx) {
-  const uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (t >= n_act) return;
-  const Rk r = rk[list[t]];
-  const Rk a = rk[r.anc];
-  Rk o;
-  o.anc = a.anc;
-  if (MODE == kSum) {
-    o.val = r.val + a.val;
-    o.d = r.d + a.d;
-    o.head = a.anc == kNull ? a.head : r.head;
-  } else {
-    o.val = r.val < a.val ? r.val : a.val;
-    o.d = 0;
-    o.head = 0;
-  }
-  nx[t] = o;
-}
-// the jumped records back into place; edges whose target is still an edge go on to the next round
-__global__ __launch_bounds__(256) void k_ut_commit(Rk *__restrict__ rk, const uint64_t *__restrict__ list, uint64_t n_act, const Rk *__restrict__ nx,
-                                                  uint64_t *__restrict__ out, unsigned long long *__restrict__ cnt) {
-  const uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  bool take = false;
-  uint64_t i = 0;
-  if (t < n_act) {
-    i = list[t];
-    const Rk o = nx[t];
-    rk[i] = o;
-    take = o.anc != kNull;
-  }
-  push_list(take, i, out, cnt);
-}
-// cycle edges: start min-propagation (val = own index, anc = pred)
-__global__ __launch_bounds__(256) void k_ut_cyc_min_init(const uint64_t *__restrict__ pred, const uint64_t *__restrict__ list, uint64_t n_cyc, Rk *__restrict__ rk) {
-  const uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (t >= n_cyc) return;
-  const uint64_t i = list[t];
-  rk[i] = Rk{pred[i], i, 0, 0};
 }
 // each cycle's minimum edge x (head := the cycle minimum): the cycle pair is kept at x when x <= the minimum of the reverse
 // complement cycle (reference: the loop pass meets the pair first at its smaller minimum; a self-complementary cycle is
@@ -239,20 +175,114 @@ __global__ void k_ut_flag_count(const mhx_unitig_vertex *__restrict__ vtx, uint6
   }
 }
 
+// the cleaned vertex table's part in the text (sdbg_unitig_text): every vertex's output strand begins at min(b, rb); a loop's
+// cycle is cut there; len[v] = k + length
+__global__ __launch_bounds__(256) void k_ut_tab_heads(const mhx_unitig_vertex *__restrict__ vtx, uint64_t nv, uint32_t k, unsigned long long *__restrict__ out_head,
+                                                      unsigned long long *__restrict__ cut, uint64_t *__restrict__ len) {
+  const uint64_t v = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (v >= nv) return;
+  const uint64_t ob = vtx[v].b < vtx[v].rb ? vtx[v].b : vtx[v].rb;
+  bit_set(out_head, ob);
+  if (vtx[v].flags & MHX_UNITIG_LOOP) bit_set(cut, ob);
+  len[v] = (uint64_t)k + vtx[v].length;
+}
+__global__ __launch_bounds__(256) void k_ut_tab_vid(const mhx_unitig_vertex *__restrict__ vtx, uint64_t nv, const unsigned long long *__restrict__ out_head,
+                                                    const uint64_t *__restrict__ oh_off, uint64_t *__restrict__ out_vid) {
+  const uint64_t v = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (v >= nv) return;
+  out_vid[bit_rank(out_head, oh_off, vtx[v].b < vtx[v].rb ? vtx[v].b : vtx[v].rb)] = v;
+}
+
+// the workspaces of one edge-level ranking
+struct EdgeRank {
+  uint64_t n, nw;
+  uint64_t *succ, *pred;
+  Ranker rr;
+  EdgeRank(mhx_ctx *c, uint64_t n_) : n(n_), nw(div_ceil(n_, 64) + 1) {
+    succ = c->ws("ut_succ", n * 8 + 64).as<uint64_t>();
+    pred = c->ws("ut_pred", n * 8 + 64).as<uint64_t>();
+    rr.c = c;
+    rr.stat = "unitig_rank";
+    rr.rk = c->ws("ut_rank", n * sizeof(Rk) + 64).as<Rk>();
+    rr.nx = c->ws("ut_next", n * sizeof(Rk) + 64).as<Rk>();
+    rr.list[0] = c->ws("ut_list0", n * 8 + 64).as<uint64_t>();
+    rr.list[1] = c->ws("ut_list1", n * 8 + 64).as<uint64_t>();
+    rr.cnt = c->ws("ut_count", 64).as<unsigned long long>();
+  }
+  // links + the first ranking; returns the cycle edges left (in rr.list[rr.cur])
+  uint64_t chains(const DevSdbg &g) {
+    mhx_ctx *c = rr.c;
+    hipStream_t st = c->stream;
+    MHX_HIP(hipMemsetAsync(pred, 0xff, n * 8 + 8, st));
+    if (!n) return 0;
+    MHX_LAUNCH(c, "unitig_links", (double)n * 16, hipLaunchKernelGGL(k_ut_links, Ranker::grid(n), dim3(256), 0, st, g, succ));
+    hipLaunchKernelGGL(k_ut_pred, Ranker::grid(n), dim3(256), 0, st, succ, n, pred);
+    MHX_HIP(hipMemsetAsync(rr.cnt, 0, 8, st));
+    rr.cur = 0;
+    hipLaunchKernelGGL(k_ut_rank_init, Ranker::grid(n), dim3(256), 0, st, g, pred, rr.rk, rr.list[0], rr.cnt);
+    MHX_HIP(hipGetLastError());
+    return rr.jump_rounds(kSum, rr.count(), 128);
+  }
+  // the cycle edges, set aside
+  const uint64_t *keep_cycles(uint64_t n_cyc) { return rr.keep_cycles(rr.c->ws("ut_list2", n_cyc * 8 + 64).as<uint64_t>()); }
+  // second ranking of the cycle edges, cut at the bits of `cut`; returns the edges of cycles without a cut
+  uint64_t rank_cut_cycles(const DevSdbg &g, const uint64_t *cyc, uint64_t n_cyc, const unsigned long long *cut) {
+    hipStream_t st = rr.c->stream;
+    MHX_HIP(hipMemsetAsync(rr.cnt, 0, 8, st));
+    rr.cur = 0;
+    hipLaunchKernelGGL(k_ut_cyc_rank_init, Ranker::grid(n_cyc), dim3(256), 0, st, g, pred, cyc, n_cyc, cut, rr.rk, rr.list[0], rr.cnt);
+    MHX_HIP(hipGetLastError());
+    return rr.jump_rounds(kSum, rr.count(), 128);
+  }
+};
+
+// offsets, text and flag counts of the vertex table in MHX_BUF_UNITIG_VERTICES, given every output strand's edges ranked from
+// its head (rk) and the head -> vertex map (out_head / oh_off / out_vid)
+void write_text(mhx_ctx *c, const DevSdbg &g, const Rk *rk, uint64_t nv, uint64_t n_loop, const uint64_t *len, const unsigned long long *out_head,
+                const uint64_t *oh_off, const uint64_t *out_vid, unsigned long long *cnt, mhx_unitig_result *out) {
+  hipStream_t st = c->stream;
+  const uint64_t n = g.n;
+  auto grid = Ranker::grid;
+  const mhx_unitig_vertex *vtx = c->results[MHX_BUF_UNITIG_VERTICES].as<mhx_unitig_vertex>();
+  uint64_t *off = c->result(MHX_BUF_UNITIG_OFFSET, (nv + 2) * 8).as<uint64_t>();
+  c->results[MHX_BUF_UNITIG_OFFSET].used = (nv + 1) * 8;
+  if (nv) exclusive_scan_u64(c, len, off, nv, off + nv);
+  else MHX_HIP(hipMemsetAsync(off, 0, 8, st));
+  uint64_t n_bases = 0;
+  MHX_HIP(hipMemcpyAsync(&n_bases, off + nv, 8, hipMemcpyDeviceToHost, st));
+  MHX_HIP(hipStreamSynchronize(st));
+  char *seq = c->result(MHX_BUF_UNITIG_SEQ, n_bases + 64).as<char>();
+  c->results[MHX_BUF_UNITIG_SEQ].used = n_bases;
+  if (nv) {
+    MHX_LAUNCH(c, "unitig_text", (double)n * 40 + (double)n_bases,
+               hipLaunchKernelGGL(k_ut_text, grid(n), dim3(256), 0, st, g, rk, out_head, oh_off, out_vid, off, seq));
+    MHX_LAUNCH(c, "unitig_labels", (double)nv * g.k, hipLaunchKernelGGL(k_ut_labels, grid(nv), dim3(256), 0, st, g, vtx, nv, off, seq));
+  }
+  MHX_HIP(hipMemsetAsync(cnt, 0, 16, st));
+  if (nv) hipLaunchKernelGGL(k_ut_flag_count, grid(nv), dim3(256), 0, st, vtx, nv, cnt);
+  unsigned long long fc[2] = {0, 0};
+  MHX_HIP(hipMemcpyAsync(fc, cnt, 16, hipMemcpyDeviceToHost, st));
+  MHX_HIP(hipStreamSynchronize(st));
+  out->n_vertices = nv;
+  out->n_loops = n_loop;
+  out->n_palindromes = fc[0];
+  out->n_standalone = fc[1];
+  out->n_bases = n_bases;
+}
+
 }  // namespace
 
 int sdbg_unitigs(mhx_ctx *c, const mhx_sdbg_index_info *info, mhx_unitig_result *out) {
   hipStream_t st = c->stream;
   const DevSdbg g = dev_sdbg(c, info, "sdbg_unitigs");
-  const uint64_t n = g.n, nw = div_ceil(n, 64) + 1;
+  c->ut_ready = c->ut_owner = false;
   memset(out, 0, sizeof *out);
-  auto grid = [](uint64_t m) { return dim3((unsigned)div_ceil(m ? m : 1, 256)); };
-  uint64_t *succ = c->ws("ut_succ", n * 8 + 64).as<uint64_t>();
-  uint64_t *pred = c->ws("ut_pred", n * 8 + 64).as<uint64_t>();
-  Rk *rk = c->ws("ut_rank", n * sizeof(Rk) + 64).as<Rk>();
-  Rk *nx = c->ws("ut_next", n * sizeof(Rk) + 64).as<Rk>();
-  uint64_t *list[2] = {c->ws("ut_list0", n * 8 + 64).as<uint64_t>(), c->ws("ut_list1", n * 8 + 64).as<uint64_t>()};
-  unsigned long long *cnt = c->ws("ut_count", 64).as<unsigned long long>();
+  auto grid = Ranker::grid;
+  EdgeRank er(c, g.n);
+  const uint64_t n = er.n, nw = er.nw;
+  uint64_t *succ = er.succ, *pred = er.pred;
+  Rk *rk = er.rr.rk;
+  unsigned long long *cnt = er.rr.cnt;
   // bitmaps: chain keys, loop keys, output-strand heads, cycle cuts; per-word popcounts and their prefixes
   unsigned long long *bits = c->ws("ut_bits", 4 * nw * 8).as<unsigned long long>();
   unsigned long long *chain_key = bits, *loop_key = bits + nw, *out_head = bits + 2 * nw, *cut = bits + 3 * nw;
@@ -260,58 +290,14 @@ int sdbg_unitigs(mhx_ctx *c, const mhx_sdbg_index_info *info, mhx_unitig_result 
   uint64_t *woff = c->ws("ut_woff", 3 * (nw + 2) * 8).as<uint64_t>();
   uint64_t *chain_off = woff, *loop_off = woff + (nw + 2), *oh_off = woff + 2 * (nw + 2);
   MHX_HIP(hipMemsetAsync(bits, 0, 4 * nw * 8, st));
-  MHX_HIP(hipMemsetAsync(pred, 0xff, n * 8 + 8, st));
-  auto count = [&]() {
-    unsigned long long h = 0;
-    MHX_HIP(hipMemcpyAsync(&h, cnt, 8, hipMemcpyDeviceToHost, st));
-    MHX_HIP(hipStreamSynchronize(st));
-    return (uint64_t)h;
-  };
-  if (n) {
-    MHX_LAUNCH(c, "unitig_links", (double)n * 16, hipLaunchKernelGGL(k_ut_links, grid(n), dim3(256), 0, st, g, succ));
-    hipLaunchKernelGGL(k_ut_pred, grid(n), dim3(256), 0, st, succ, n, pred);
-  }
-  // pointer jumping until done (mode kSum) or until a round finishes no edge (only cycles left); returns the edges left in
-  // list[*cur] and the rounds run.  kMin: a fixed number of rounds.
-  int cur = 0;
-  auto jump_rounds = [&](int mode, uint64_t n_act, int max_rounds) -> uint64_t {
-    for (int r = 0; n_act && r < max_rounds; ++r) {
-      MHX_HIP(hipMemsetAsync(cnt, 0, 8, st));
-      if (mode == kSum)
-        MHX_LAUNCH(c, "unitig_rank", (double)n_act * 96, hipLaunchKernelGGL(k_ut_jump<kSum>, grid(n_act), dim3(256), 0, st, rk, list[cur], n_act, nx));
-      else
-        MHX_LAUNCH(c, "unitig_rank", (double)n_act * 96, hipLaunchKernelGGL(k_ut_jump<kMin>, grid(n_act), dim3(256), 0, st, rk, list[cur], n_act, nx));
-      MHX_LAUNCH(c, "unitig_rank", (double)n_act * 88,
-                 hipLaunchKernelGGL(k_ut_commit, grid(n_act), dim3(256), 0, st, rk, list[cur], n_act, nx, list[cur ^ 1], cnt));
-      const uint64_t left = count();
-      cur ^= 1;
-      if (mode == kSum && left == n_act) return left;  // nothing finished: cycles only
-      n_act = left;
-    }
-    return n_act;
-  };
-  MHX_HIP(hipMemsetAsync(cnt, 0, 8, st));
-  if (n) hipLaunchKernelGGL(k_ut_rank_init, grid(n), dim3(256), 0, st, g, pred, rk, list[cur], cnt);
-  MHX_HIP(hipGetLastError());
-  const uint64_t n_cyc = n ? jump_rounds(kSum, count(), 128) : 0;
+  const uint64_t n_cyc = er.chains(g);
   if (n_cyc) {
-    // the cycle edges: minimum by min-propagation (2^rounds >= n_cyc >= any cycle's length), then cut and rank again
-    uint64_t *cyc = list[cur];  // stays as it is; the rounds rotate two other lists
-    list[0] = list[cur ^ 1];
-    list[1] = c->ws("ut_list2", n_cyc * 8 + 64).as<uint64_t>();
-    cur = 0;
-    MHX_HIP(hipMemcpyAsync(list[0], cyc, n_cyc * 8, hipMemcpyDeviceToDevice, st));
-    hipLaunchKernelGGL(k_ut_cyc_min_init, grid(n_cyc), dim3(256), 0, st, pred, cyc, n_cyc, rk);
-    int rounds = 0;
-    while ((1ull << rounds) < n_cyc) ++rounds;
-    jump_rounds(kMin, n_cyc, rounds);
+    // the cycle edges: minimum by min-propagation, then cut and rank again
+    const uint64_t *cyc = er.keep_cycles(n_cyc);
+    er.rr.cycle_minima(cyc, n_cyc, pred);
     MHX_LAUNCH(c, "unitig_cycles", (double)n_cyc * 16,
                hipLaunchKernelGGL(k_ut_cyc_cut, grid(n_cyc), dim3(256), 0, st, g, succ, cyc, n_cyc, rk, cut, loop_key, out_head));
-    MHX_HIP(hipMemsetAsync(cnt, 0, 8, st));
-    cur = 0;
-    hipLaunchKernelGGL(k_ut_cyc_rank_init, grid(n_cyc), dim3(256), 0, st, g, pred, cyc, n_cyc, cut, rk, list[0], cnt);
-    MHX_HIP(hipGetLastError());
-    if (jump_rounds(kSum, count(), 128)) throw Error("sdbg_unitigs: a cycle without a cut (is the graph its own reverse complement?)");
+    if (er.rank_cut_cycles(g, cyc, n_cyc, cut)) throw Error("sdbg_unitigs: a cycle without a cut (is the graph its own reverse complement?)");
   }
   // chain keys (the reverse complements of chain ends: one EdgeReverseComplement per tail and per kept head)
   uint64_t *rc_tail = c->ws("ut_rc_tail", n * 8 + 64).as<uint64_t>();
@@ -333,8 +319,6 @@ int sdbg_unitigs(mhx_ctx *c, const mhx_sdbg_index_info *info, mhx_unitig_result 
     throw Error("Too many vertices in the unitig graph (" + std::to_string(nv) + " >= 4294967294), you may increase the kmer size to remove tons of erroneous kmers.");
   mhx_unitig_vertex *vtx = c->result(MHX_BUF_UNITIG_VERTICES, nv * sizeof(mhx_unitig_vertex) + 64).as<mhx_unitig_vertex>();
   c->results[MHX_BUF_UNITIG_VERTICES].used = nv * sizeof(mhx_unitig_vertex);
-  uint64_t *off = c->result(MHX_BUF_UNITIG_OFFSET, (nv + 2) * 8).as<uint64_t>();
-  c->results[MHX_BUF_UNITIG_OFFSET].used = (nv + 1) * 8;
   uint64_t *len = c->ws("ut_len", nv * 8 + 64).as<uint64_t>();
   uint64_t *out_vid = c->ws("ut_out_vid", nv * 8 + 64).as<uint64_t>();
   if (nv) {
@@ -344,30 +328,45 @@ int sdbg_unitigs(mhx_ctx *c, const mhx_sdbg_index_info *info, mhx_unitig_result 
     MHX_LAUNCH(c, "unitig_vertices", (double)nv * 64,
                hipLaunchKernelGGL(k_ut_vertices, grid(nw), dim3(256), 0, st, g, succ, pred, rk, loop_key, loop_off, n_chain, true, rc_tail, nw,
                                   out_head, oh_off, vtx, out_vid, len));
-    exclusive_scan_u64(c, len, off, nv, off + nv);
-  } else {
-    MHX_HIP(hipMemsetAsync(off, 0, 8, st));
   }
-  uint64_t n_bases = 0;
-  MHX_HIP(hipMemcpyAsync(&n_bases, off + nv, 8, hipMemcpyDeviceToHost, st));
+  write_text(c, g, rk, nv, n_loop, len, out_head, oh_off, out_vid, cnt, out);
+  c->ut_ready = true;
+  c->ut_edges = n;
+  c->ut_nv = nv;
+  return 0;
+}
+
+// Offsets, text and counts for the vertex table as the cleaning steps left it (unitig_clean.hip): the cleaned SdBG's maximal
+// simple paths are exactly the vertices, so the edge-level ranking runs again and every chain is attached to the vertex whose
+// output strand begins at its head.  Vertex order, length and depth are the table's.
+int sdbg_unitig_text(mhx_ctx *c, const mhx_sdbg_index_info *info, uint64_t nv, uint64_t n_loop, mhx_unitig_result *out) {
+  hipStream_t st = c->stream;
+  const DevSdbg g = dev_sdbg(c, info, "unitig_finish");
+  memset(out, 0, sizeof *out);
+  auto grid = Ranker::grid;
+  EdgeRank er(c, g.n);
+  const uint64_t nw = er.nw;
+  unsigned long long *bits = c->ws("ut_bits", 4 * nw * 8).as<unsigned long long>();
+  unsigned long long *out_head = bits + 2 * nw, *cut = bits + 3 * nw;
+  uint32_t *wcnt = c->ws("ut_wcnt", nw * 4 + 64).as<uint32_t>();
+  uint64_t *oh_off = c->ws("ut_woff", 3 * (nw + 2) * 8).as<uint64_t>() + 2 * (nw + 2);
+  const mhx_unitig_vertex *vtx = c->results[MHX_BUF_UNITIG_VERTICES].as<mhx_unitig_vertex>();
+  uint64_t *len = c->ws("ut_len", nv * 8 + 64).as<uint64_t>();
+  uint64_t *out_vid = c->ws("ut_out_vid", nv * 8 + 64).as<uint64_t>();
+  MHX_HIP(hipMemsetAsync(bits, 0, 4 * nw * 8, st));
+  if (nv) hipLaunchKernelGGL(k_ut_tab_heads, grid(nv), dim3(256), 0, st, vtx, nv, g.k, out_head, cut, len);
+  const uint64_t n_cyc = er.chains(g);
+  // cycles: the loops' output strands are cut at their begin; the other strand's cycle and the cycles of deleted loops have
+  // no cut, stay unranked and belong to no vertex
+  if (n_cyc) er.rank_cut_cycles(g, er.keep_cycles(n_cyc), n_cyc, cut);
+  uint64_t n_heads = 0;
+  hipLaunchKernelGGL(k_ut_word_pop, grid(nw), dim3(256), 0, st, out_head, nw, wcnt);
+  exclusive_scan_u32_u64(c, wcnt, oh_off, nw, oh_off + nw + 1);
+  MHX_HIP(hipMemcpyAsync(&n_heads, oh_off + nw + 1, 8, hipMemcpyDeviceToHost, st));
   MHX_HIP(hipStreamSynchronize(st));
-  char *seq = c->result(MHX_BUF_UNITIG_SEQ, n_bases + 64).as<char>();
-  c->results[MHX_BUF_UNITIG_SEQ].used = n_bases;
-  if (nv) {
-    MHX_LAUNCH(c, "unitig_text", (double)n * 40 + (double)n_bases,
-               hipLaunchKernelGGL(k_ut_text, grid(n), dim3(256), 0, st, g, rk, out_head, oh_off, out_vid, off, seq));
-    MHX_LAUNCH(c, "unitig_labels", (double)nv * g.k, hipLaunchKernelGGL(k_ut_labels, grid(nv), dim3(256), 0, st, g, vtx, nv, off, seq));
-  }
-  MHX_HIP(hipMemsetAsync(cnt, 0, 16, st));
-  if (nv) hipLaunchKernelGGL(k_ut_flag_count, grid(nv), dim3(256), 0, st, vtx, nv, cnt);
-  unsigned long long fc[2] = {0, 0};
-  MHX_HIP(hipMemcpyAsync(fc, cnt, 16, hipMemcpyDeviceToHost, st));
-  MHX_HIP(hipStreamSynchronize(st));
-  out->n_vertices = nv;
-  out->n_loops = n_loop;
-  out->n_palindromes = fc[0];
-  out->n_standalone = fc[1];
-  out->n_bases = n_bases;
+  if (n_heads != nv) throw Error("unitig_finish: two vertices begin at one edge");
+  if (nv) hipLaunchKernelGGL(k_ut_tab_vid, grid(nv), dim3(256), 0, st, vtx, nv, out_head, oh_off, out_vid);
+  write_text(c, g, er.rr.rk, nv, n_loop, len, out_head, oh_off, out_vid, er.rr.cnt, out);
   return 0;
 }
 

@@ -144,6 +144,9 @@ SYMBOLS = {
     "mhx_sdbg_load_bytes": (C.c_int, [_P, _P, C.c_uint64, _P, _P, _P, _P]),
     "mhx_sdbg_remove_tips": (C.c_int, [_P, C.POINTER(SdbgIndexInfo), C.c_int, _P]),
     "mhx_sdbg_unitigs": (C.c_int, [_P, C.POINTER(SdbgIndexInfo), C.POINTER(UnitigResult)]),
+    "mhx_unitig_disconnect_weak_links": (C.c_int, [_P, C.POINTER(SdbgIndexInfo), C.c_double, C.POINTER(C.c_uint64)]),
+    "mhx_unitig_remove_tips": (C.c_int, [_P, C.POINTER(SdbgIndexInfo), C.c_uint32, C.POINTER(C.c_uint64)]),
+    "mhx_unitig_finish": (C.c_int, [_P, C.POINTER(SdbgIndexInfo), C.POINTER(UnitigResult)]),
     "mhx_comm_unique_id": (C.c_int, [_P]),
     "mhx_comm_init_rank": (_P, [_P, _P, C.c_int, C.c_int]),
     "mhx_comm_local_group": (C.c_int, [C.c_int, _P, _P]),
@@ -409,8 +412,29 @@ class Engine:
         self._chk(self.lib.mhx_sdbg_unitigs(self.h, C.byref(info), C.byref(r)))
         return r
 
+    def unitig_disconnect_weak_links(self, info, ratio):
+        """DisconnectWeakLinks + Refresh on the unitig graph of the last sdbg_unitigs call (include/mhx.h:
+        mhx_unitig_disconnect_weak_links); returns the number of (vertex, strand) flags set."""
+        n = C.c_uint64(0)
+        self._chk(self.lib.mhx_unitig_disconnect_weak_links(self.h, C.byref(info), float(ratio), C.byref(n)))
+        return int(n.value)
+
+    def unitig_remove_tips(self, info, max_tip_len):
+        """RemoveTips on the unitig graph, a Refresh after every threshold (include/mhx.h: mhx_unitig_remove_tips);
+        returns the number of tips removed."""
+        n = C.c_uint64(0)
+        self._chk(self.lib.mhx_unitig_remove_tips(self.h, C.byref(info), int(max_tip_len), C.byref(n)))
+        return int(n.value)
+
+    def unitig_finish(self, info):
+        """Flags, contig text and offsets of the cleaned vertex table (include/mhx.h: mhx_unitig_finish); returns a
+        UnitigResult.  unitig_contigs() then returns the cleaned graph."""
+        r = UnitigResult()
+        self._chk(self.lib.mhx_unitig_finish(self.h, C.byref(info), C.byref(r)))
+        return r
+
     def unitig_contigs(self):
-        """-> (vertices as a UNITIG_VERTEX_DTYPE array, list of contig strings) of the last sdbg_unitigs call."""
+        """-> (vertices as a UNITIG_VERTEX_DTYPE array, list of contig strings) of the last sdbg_unitigs / unitig_finish call."""
         v = self.fetch(BUF_UNITIG_VERTICES, np.uint8).view(UNITIG_VERTEX_DTYPE)
         seq = self.fetch(BUF_UNITIG_SEQ, np.uint8).tobytes().decode()
         off = self.fetch(BUF_UNITIG_OFFSET, np.uint64)

@@ -2,9 +2,11 @@
 workload family, synth.gen_shard_library), graph by `mhx_core read2sdbg -k 21 -m 2`, then `mhx_core assemble
 --bubble_level 0 --prune_level 0 --cleaning_rounds 0` with MHX_PROFILE=1 (per-kernel times of links / ranking / vertices /
 text), and the reference's `megahit_core assemble` on the same graph at -t 1 and -t 16: wall times and the digest of
-.contigs.fa (equal to ours at -t 1).  Too slow for the suite.  One JSON line on stdout.
+.contigs.fa (equal to ours at -t 1); the wall time of mhx_core again --wall-runs times without MHX_PROFILE.  --clean: the same with `--cleaning_rounds 5` and MHX_ASSEMBLE_CLEAN=1 (the weak-link
+and tip rounds on the device: the clean_* kernel groups), the reference's cleaning time summed from its per-step log lines.
+Too slow for the suite.  One JSON line on stdout.
 
-    python tools/unitig_bench.py [--reads 10000000] [--ref oracle/_ref/ref_megahit_core] [--ref-threads 1,16] [--workdir DIR]"""
+    python tools/unitig_bench.py [--clean] [--reads 10000000] [--ref oracle/_ref/ref_megahit_core] [--ref-threads 1,16] [--workdir DIR]"""
 import argparse
 import hashlib
 import json
@@ -38,28 +40,40 @@ def main():
     ap.add_argument("--ref", default=os.path.join(ROOT, "oracle", "_ref", "ref_megahit_core"))
     ap.add_argument("--ref-threads", default="1,16")
     ap.add_argument("--workdir", default=None)
+    ap.add_argument("--wall-runs", type=int, default=5, help="runs of mhx_core assemble without MHX_PROFILE for the wall time")
+    ap.add_argument("--clean", action="store_true", help="--cleaning_rounds 5 on the GPU route (MHX_ASSEMBLE_CLEAN=1)")
     a = ap.parse_args()
+    qual = QUAL[:-1] + ["5"] if a.clean else QUAL
     d = a.workdir or tempfile.mkdtemp(prefix="mhx_unitig")
     os.makedirs(d, exist_ok=True)
-    res = {"reads": a.reads, "k": a.k}
+    res = {"reads": a.reads, "k": a.k, "options": " ".join(qual)}
     _, blocks = synth.gen_shard_library(a.reads, 1, 1001)
     synth.write_read_lib(os.path.join(d, "reads"), blocks)
     g = os.path.join(d, "g")
     subprocess.run([MHX_CORE, "read2sdbg", "-k", str(a.k), "-m", "2", "--host_mem", "2e10", "--num_cpu_threads", "16", "--read_lib_file",
                     os.path.join(d, "reads"), "--output_prefix", g], check=True, stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL)
-    env = dict(os.environ, MHX_PROFILE="1", MHX_SERVER="off")
+    env = dict(os.environ, MHX_PROFILE="1", MHX_SERVER="off", MHX_ASSEMBLE_CLEAN="1" if a.clean else "0")
     t0 = time.time()
-    p = subprocess.run([MHX_CORE, "assemble", "-s", g, "-o", os.path.join(d, "mine"), "-t", "16"] + QUAL, env=env, stdout=subprocess.DEVNULL,
+    p = subprocess.run([MHX_CORE, "assemble", "-s", g, "-o", os.path.join(d, "mine"), "-t", "16"] + qual, env=env, stdout=subprocess.DEVNULL,
                        stderr=subprocess.PIPE, text=True, check=True)
     res["mhx_wall_s"] = round(time.time() - t0, 3)
     res["kernels_ms"] = {m.group(1): float(m.group(2)) for m in re.finditer(r"profile (\S+)\s+\d+ launches\s+([\d.]+) ms", p.stderr)}
-    res["log"] = [l for l in p.stderr.splitlines() if re.search(r"Edges|Tips|unitig graph size|palindrome|Max:|output", l)]
+    res["log"] = [l for l in p.stderr.splitlines() if re.search(r"Edges|Tips|unitig graph size|palindrome|Max:|output|disconnected", l)]
     res["mhx_digest"] = md5(os.path.join(d, "mine.contigs.fa"))
+    # the wall time files to files with the profiler off (the events of MHX_PROFILE serialise the launches): every run listed
+    env.pop("MHX_PROFILE")
+    walls = []
+    for _ in range(a.wall_runs):
+        t0 = time.time()
+        subprocess.run([MHX_CORE, "assemble", "-s", g, "-o", os.path.join(d, "mine"), "-t", "16"] + qual, env=env, stdout=subprocess.DEVNULL,
+                       stderr=subprocess.DEVNULL, check=True)
+        walls.append(round(time.time() - t0, 3))
+    res["mhx_wall_unprofiled_s"] = walls
     if os.path.exists(a.ref):
         for t in [int(x) for x in a.ref_threads.split(",") if x]:
             out = os.path.join(d, "ref_t%d" % t)
             t0 = time.time()
-            q = subprocess.run([a.ref, "assemble", "-s", g, "-o", out, "-t", str(t)] + QUAL, stdout=subprocess.DEVNULL, stderr=subprocess.PIPE,
+            q = subprocess.run([a.ref, "assemble", "-s", g, "-o", out, "-t", str(t)] + qual, stdout=subprocess.DEVNULL, stderr=subprocess.PIPE,
                                text=True, check=True)
             res["ref_t%d_wall_s" % t] = round(time.time() - t0, 3)
             m = re.search(r"unitig graph size: \d+, time for building: ([\d.]+)", q.stderr)
@@ -68,6 +82,9 @@ def main():
             res["ref_t%d_tips_s" % t] = float(m.group(1)) if m else None
             m = re.search(r"Time to output: ([\d.]+)", q.stderr)
             res["ref_t%d_output_s" % t] = float(m.group(1)) if m else None
+            if a.clean:  # "Tips removed: N, time: T" and "Number unitigs disconnected: N, time: T" of every round
+                res["ref_t%d_cleaning_s" % t] = round(sum(float(x) for x in re.findall(r"(?:Tips removed|disconnected): \d+, time: ([\d.]+)", q.stderr)), 3)
+                res["ref_t%d_rounds" % t] = re.findall(r"(?:Tips removed|disconnected): (\d+)", q.stderr)
             if t == 1:
                 res["ref_t1_digest"] = md5(out + ".contigs.fa")
                 res["digest_equal"] = res["ref_t1_digest"] == res["mhx_digest"]
