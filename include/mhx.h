@@ -337,6 +337,7 @@ int mhx_sdbg_remove_tips(mhx_ctx *, const mhx_sdbg_index_info *info, int max_tip
 #define MHX_UNITIG_LOOP 1u        /* is_looped */
 #define MHX_UNITIG_PALINDROME 2u  /* is_palindrome: b == rb */
 #define MHX_UNITIG_STANDALONE 4u  /* a loop, or in-degree = out-degree = 0 (contig_output.cpp:83-117) */
+#define MHX_UNITIG_CHANGED 8u     /* is_changed: the survivor of a merge in a Refresh that was asked to mark (unitig_graph.cpp:293,334) */
 typedef struct {
   uint64_t b, e, rb, re;  /* begin / end edge of strand 0 and of its reverse complement (UnitigGraphVertex::strand_info) */
   uint64_t total_depth;   /* sum of EdgeMultiplicity over the unitig (a loop counts its end edge twice, unitig_graph.cpp:96-104) */
@@ -351,10 +352,13 @@ typedef struct {
 } mhx_unitig_result;
 int mhx_sdbg_unitigs(mhx_ctx *, const mhx_sdbg_index_info *info, mhx_unitig_result *out);
 /* Graph cleaning on that unitig graph, in place on MHX_BUF_UNITIG_VERTICES and MHX_BUF_SDBG_INVALID: together they are
- * `assemble --bubble_level 0 --prune_level 0 --cleaning_rounds N` (main_assemble.cpp:182-249).  The result is the
+ * `assemble --bubble_level 0 --prune_level 0..2 --cleaning_rounds N` (main_assemble.cpp:182-301).  The result is the
  * reference's at -t 1 and does not depend on any thread count.  Valid only after mhx_sdbg_unitigs on the same index (any
  * other state returns an error); between these calls MHX_BUF_UNITIG_SEQ / _OFFSET and the vertices' STANDALONE flags are
- * stale until mhx_unitig_finish.
+ * stale until mhx_unitig_finish.  mhx_unitig_finish may be called in mid-run: it reads the vertex table and the SdBG and
+ * rebuilds only the text, the offsets and the STANDALONE flags, so cleaning calls after a finish are valid and give what they
+ * give without it; SEQ / OFFSET / STANDALONE are then stale again until the next finish (the non-final `assemble` writes
+ * its contigs, prunes on, finishes again and writes the changed ones).
  *   mhx_unitig_disconnect_weak_links  DisconnectWeakLinks (assembly/weak_link_remover.cpp): at every vertex end with two or
  *       more out-neighbours, a neighbour whose average depth is <= ratio * the neighbours' total is flagged on the strand it
  *       is entered by; then UnitigGraph::Refresh (unitig_graph.cpp:140-355: flagged vertices lose their end edges, deleted
@@ -363,13 +367,28 @@ int mhx_sdbg_unitigs(mhx_ctx *, const mhx_sdbg_index_info *info, mhx_unitig_resu
  *   mhx_unitig_remove_tips  RemoveTips on the unitig graph (assembly/tip_remover.cpp): thresholds 2, 4, 8, ... below
  *       max_tip_len, each followed by a Refresh; a vertex shorter than the threshold goes when it is a loop, has no
  *       neighbour, or has one neighbour in all whose average depth is > 8 times its own.  *n_removed = "Tips removed".
+ *   mhx_unitig_remove_local_low_depth  RemoveLocalLowDepth (assembly/low_depth_remover.cpp:10-86), one pass: a vertex that is
+ *       no loop, no longer than max_len, has a neighbour and (in-degree <= 1 and out-degree <= 1, or one of them 0) is
+ *       deleted when its average depth is below min(min_depth, local_ratio * the mean depth of its neighbours, each
+ *       counted over at most local_width edges); then a Refresh, only if something was deleted.  mark_changed != 0 is
+ *       Refresh(true) (the reference's permanent_rm = false): survivors of merges get MHX_UNITIG_CHANGED, which every later
+ *       call keeps.  *n_removed = vertices deleted; *is_changed = the reference's return value (some vertex deleted, or some
+ *       qualifying vertex with min_depth < local_ratio * mean).  Plain IEEE double in the reference's order of operations.
+ *   mhx_unitig_iterate_local_low_depth  IterateLocalLowDepth (low_depth_remover.cpp:88-102): passes with min_depth, 1.1 *
+ *       min_depth, ... until one returns is_changed = 0 or min_depth reaches 65535.  *n_removed = the sum over the passes.
  *   mhx_unitig_finish  flags (MHX_UNITIG_STANDALONE from the degrees on the cleaned graph), MHX_BUF_UNITIG_SEQ and
  *       MHX_BUF_UNITIG_OFFSET for the vertex table as it is now.  total_depth is no longer a sum of multiplicities once a
  *       vertex was trimmed (lround(average * new length), unitig_graph.cpp:191-193).
- * The CLI (`mhx_core assemble`) runs these rounds only when MHX_ASSEMBLE_CLEAN=1 is in its environment (and only at
- * --bubble_level 0 --prune_level 0); otherwise such command lines are forwarded to MHX_REF_CORE.  MHX_ASSEMBLE_REF=1 wins. */
+ * The CLI (`mhx_core assemble`) runs the cleaning rounds only when MHX_ASSEMBLE_CLEAN=1 or MHX_ASSEMBLE_PRUNE=1 is in its
+ * environment and only at --bubble_level 0; --prune_level 1 and 2 (with an explicit --min_depth > 0) run here only with
+ * MHX_ASSEMBLE_PRUNE=1, which implies the cleaning rounds.  Otherwise such command lines are forwarded to MHX_REF_CORE.
+ * MHX_ASSEMBLE_REF=1 wins. */
 int mhx_unitig_disconnect_weak_links(mhx_ctx *, const mhx_sdbg_index_info *info, double ratio, uint64_t *n_flagged);
 int mhx_unitig_remove_tips(mhx_ctx *, const mhx_sdbg_index_info *info, uint32_t max_tip_len, uint64_t *n_removed);
+int mhx_unitig_remove_local_low_depth(mhx_ctx *, const mhx_sdbg_index_info *info, double min_depth, uint32_t max_len, uint32_t local_width,
+                                      double local_ratio, int mark_changed, uint64_t *n_removed, int *is_changed);
+int mhx_unitig_iterate_local_low_depth(mhx_ctx *, const mhx_sdbg_index_info *info, double min_depth, uint32_t max_len, uint32_t local_width,
+                                       double local_ratio, int mark_changed, uint64_t *n_removed);
 int mhx_unitig_finish(mhx_ctx *, const mhx_sdbg_index_info *info, mhx_unitig_result *out);
 /* install an SdBG produced elsewhere (e.g. read back from .sdbg.* files: bucket byte ranges back to back) as the handle's
  * current SdBG; the four tables have 65536 entries (starting byte, items, tips, large multiplicities per bucket) */

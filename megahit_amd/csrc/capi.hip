@@ -873,6 +873,20 @@ int mhx_unitig_remove_tips(mhx_ctx *c, const mhx_sdbg_index_info *info, uint32_t
     mhx::unitig_remove_tips(c, info, max_tip_len, n_removed);
   })
 }
+int mhx_unitig_remove_local_low_depth(mhx_ctx *c, const mhx_sdbg_index_info *info, double min_depth, uint32_t max_len, uint32_t local_width,
+                                      double local_ratio, int mark_changed, uint64_t *n_removed, int *is_changed) {
+  MHX_TRY({
+    MHX_HIP(hipSetDevice(c->device));
+    mhx::unitig_remove_local_low_depth(c, info, min_depth, max_len, local_width, local_ratio, mark_changed, n_removed, is_changed);
+  })
+}
+int mhx_unitig_iterate_local_low_depth(mhx_ctx *c, const mhx_sdbg_index_info *info, double min_depth, uint32_t max_len, uint32_t local_width,
+                                       double local_ratio, int mark_changed, uint64_t *n_removed) {
+  MHX_TRY({
+    MHX_HIP(hipSetDevice(c->device));
+    mhx::unitig_iterate_local_low_depth(c, info, min_depth, max_len, local_width, local_ratio, mark_changed, n_removed);
+  })
+}
 int mhx_unitig_finish(mhx_ctx *c, const mhx_sdbg_index_info *info, mhx_unitig_result *out) {
   MHX_TRY({
     MHX_HIP(hipSetDevice(c->device));

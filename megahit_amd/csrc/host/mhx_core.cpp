@@ -1211,7 +1211,10 @@ int main_iterate(int argc, char **argv) {
 // assemble (reference src/main_assemble.cpp) when its options ask for nothing beyond tip trimming, the unitig graph and
 // contig output: --bubble_level 0 --prune_level 0 --cleaning_rounds 0 — and, with MHX_ASSEMBLE_CLEAN=1 in the environment,
 // with --cleaning_rounds N >= 1 as well: the rounds of RemoveTips and DisconnectWeakLinks on the unitig graph
-// (main_assemble.cpp:182-249 at bubble level 0 and prune level 0).  Every other option set goes to the reference.
+// (main_assemble.cpp:182-249 at bubble level 0 and prune level 0) — and, with MHX_ASSEMBLE_PRUNE=1, at --prune_level 1 or 2
+// with an explicit --min_depth > 0 (InferMinDepth is not built): RemoveLocalLowDepth inside the rounds (level 2), the
+// IterateLocalLowDepth after them and the .addi.fa of the changed contigs (main_assemble.cpp:238-301).  Every other option
+// set goes to the reference.
 // The SdBG files are read back into HBM, indexed (mhx_sdbg_build_index), trimmed (mhx_sdbg_remove_tips), turned into the
 // unitig graph and its contig text (mhx_sdbg_unitigs), cleaned in place (mhx_unitig_*); the host folds palindromes and
 // writes the ContigWriter files.  The cleaned result is the reference's at -t 1 whatever -t says.
@@ -1244,10 +1247,13 @@ bool assemble_on_gpu(int argc, char **argv) {
     return false;  // the reference reports it
   }
   if (o.get("sdbg_name").empty()) return false;
-  if (atoi(o.get("bubble_level").c_str()) != 0 || atoi(o.get("prune_level").c_str()) != 0) return false;
-  const int rounds = atoi(o.get("cleaning_rounds").c_str());
+  const int prune_level = atoi(o.get("prune_level").c_str()), rounds = atoi(o.get("cleaning_rounds").c_str());
+  if (atoi(o.get("bubble_level").c_str()) != 0) return false;
+  const bool prune = getenv("MHX_ASSEMBLE_PRUNE") && atoi(getenv("MHX_ASSEMBLE_PRUNE")) != 0;  // low-depth pruning on the GPU: opt-in
+  if (prune_level != 0)  // levels 1 and 2 with a given minimum depth; the variable implies the cleaning rounds
+    return prune && (prune_level == 1 || prune_level == 2) && atof(o.get("min_depth").c_str()) > 0 && rounds >= 0;
   if (rounds <= 0) return rounds == 0;
-  return getenv("MHX_ASSEMBLE_CLEAN") && atoi(getenv("MHX_ASSEMBLE_CLEAN")) != 0;  // the cleaning rounds on the GPU: opt-in
+  return prune || (getenv("MHX_ASSEMBLE_CLEAN") && atoi(getenv("MHX_ASSEMBLE_CLEAN")) != 0);  // the cleaning rounds on the GPU: opt-in
 }
 void revcomp_ascii(std::string &s) {  // contig_output.cpp:12-42
   auto comp = [](char c) { return c == 'A' ? 'T' : c == 'C' ? 'G' : c == 'G' ? 'C' : 'A'; };
@@ -1329,8 +1335,11 @@ int main_assemble(int argc, char **argv) {
          (unsigned long long)(hist.empty() ? 0 : hist.rbegin()->first), (unsigned long long)(hist.empty() ? 0 : hist.begin()->first),
          (unsigned long long)n50, (unsigned long long)vtx.size(), (unsigned long long)n_isolated, (unsigned long long)n_looped, (unsigned long long)total);
   };
-  // graph cleaning (main_assemble.cpp:182-249 with bubble level 0 and prune level 0)
-  const int cleaning_rounds = atoi(o.get("cleaning_rounds").c_str());
+  // graph cleaning (main_assemble.cpp:182-249 with bubble level 0 and prune level 0, 1 or 2)
+  const int cleaning_rounds = atoi(o.get("cleaning_rounds").c_str()), prune_level = atoi(o.get("prune_level").c_str());
+  const bool is_final_round = o.get("is_final_round") == "1";
+  const double min_depth = atof(o.get("min_depth").c_str()), low_local_ratio = atof(o.get("low_local_ratio").c_str());
+  const uint32_t local_width = 1000;  // AssemblerOptions::local_width: no command-line option sets it
   if (cleaning_rounds > 0) {
     print_stat(fetch<mhx_unitig_vertex>(c, MHX_BUF_UNITIG_VERTICES));
     const double disconnect_ratio = atof(o.get("disconnect_ratio").c_str());
@@ -1347,41 +1356,75 @@ int main_assemble(int argc, char **argv) {
       CK(mhx_unitig_disconnect_weak_links(c, &ix, disconnect_ratio, &n_disconnected));
       info("Number unitigs disconnected: %llu, time: %.3f", (unsigned long long)n_disconnected, t.lap());
       changed |= n_disconnected > 0;
+      if (prune_level >= 2) {  // excessive pruning: permanent (no marks); its count does not feed `changed`
+        uint64_t n_pruned = 0;
+        CK(mhx_unitig_remove_local_low_depth(c, &ix, min_depth, (uint32_t)max_tip_len, local_width, std::min(low_local_ratio, 0.1), 0, &n_pruned,
+                                             nullptr));
+        info("Unitigs removed in excessive pruning: %llu, time: %.3f", (unsigned long long)n_pruned, t.lap());
+      }
       if (!changed) break;
     }
     CK(mhx_unitig_finish(c, &ix, &ur));
   }
-  const std::vector<mhx_unitig_vertex> vtx = fetch<mhx_unitig_vertex>(c, MHX_BUF_UNITIG_VERTICES);
-  const std::vector<char> seq = fetch<char>(c, MHX_BUF_UNITIG_SEQ);
-  const std::vector<uint64_t> off = fetch<uint64_t>(c, MHX_BUF_UNITIG_OFFSET);
-  print_stat(vtx);
-  // OutputContigs (contig_output.cpp:62-119) with ContigWriter's record format
-  std::vector<mhxio::ContigRecord> main_recs, final_recs;
-  std::deque<std::string> folded;
-  for (uint64_t i = 0; i < vtx.size(); ++i) {
-    const mhx_unitig_vertex &v = vtx[i];
-    const double multi = std::min(65535.0, (double)v.total_depth / v.length);  // kMaxMul
-    mhxio::ContigRecord r{i, 0, multi, seq.data() + off[i], (size_t)(off[i + 1] - off[i])};
-    const bool loop = v.flags & MHX_UNITIG_LOOP, pal = v.flags & MHX_UNITIG_PALINDROME;
-    if (loop || (v.flags & MHX_UNITIG_STANDALONE)) {
-      r.flag = loop && !pal ? 3 : 1;  // kLoop | kStandalone, or kStandalone
-      if (pal) {
-        folded.emplace_back(r.seq, r.len);
-        fold_palindrome(folded.back(), f.k, loop);
-        r.seq = folded.back().data();
-        r.len = folded.back().size();
+  std::vector<mhx_unitig_vertex> vtx;
+  std::vector<char> seq;
+  std::vector<uint64_t> off;
+  auto fetch_graph = [&]() {
+    vtx = fetch<mhx_unitig_vertex>(c, MHX_BUF_UNITIG_VERTICES);
+    seq = fetch<char>(c, MHX_BUF_UNITIG_SEQ);
+    off = fetch<uint64_t>(c, MHX_BUF_UNITIG_OFFSET);
+    print_stat(vtx);
+  };
+  // OutputContigs (contig_output.cpp:62-119) with ContigWriter's record format; change_only: the MHX_UNITIG_CHANGED vertices
+  // with multiplicity 1 and no split into final contigs, to `path`
+  auto output_contigs = [&](bool change_only, const std::string &path) {
+    std::vector<mhxio::ContigRecord> main_recs, final_recs;
+    std::deque<std::string> folded;
+    for (uint64_t i = 0; i < vtx.size(); ++i) {
+      const mhx_unitig_vertex &v = vtx[i];
+      if (change_only && !(v.flags & MHX_UNITIG_CHANGED)) continue;
+      const double multi = change_only ? 1.0 : std::min(65535.0, (double)v.total_depth / v.length);  // kMaxMul
+      mhxio::ContigRecord r{i, 0, multi, seq.data() + off[i], (size_t)(off[i + 1] - off[i])};
+      const bool loop = v.flags & MHX_UNITIG_LOOP, pal = v.flags & MHX_UNITIG_PALINDROME;
+      if (loop || (v.flags & MHX_UNITIG_STANDALONE)) {
+        r.flag = loop && !pal ? 3 : 1;  // kLoop | kStandalone, or kStandalone
+        if (pal) {
+          folded.emplace_back(r.seq, r.len);
+          fold_palindrome(folded.back(), f.k, loop);
+          r.seq = folded.back().data();
+          r.len = folded.back().size();
+        }
+        if (output_standalone && !change_only) {
+          if (r.len >= (size_t)std::max(0, min_standalone)) final_recs.push_back(r);
+          continue;
+        }
       }
-      if (output_standalone) {
-        if (r.len >= (size_t)std::max(0, min_standalone)) final_recs.push_back(r);
-        continue;
-      }
+      main_recs.push_back(r);
     }
-    main_recs.push_back(r);
+    mhxio::write_contigs(path, f.k, main_recs, n_threads);
+    if (!change_only) mhxio::write_contigs(prefix + ".final.contigs.fa", f.k, final_recs, n_threads);
+  };
+  fetch_graph();
+  if (!(is_final_round && prune_level >= 1)) {  // otherwise output after local low depth pruning
+    output_contigs(false, prefix + ".contigs.fa");
+    info("Time to output: %.4f", t.lap());
   }
-  mhxio::write_contigs(prefix + ".contigs.fa", f.k, main_recs, n_threads);
-  mhxio::write_contigs(prefix + ".final.contigs.fa", f.k, final_recs, n_threads);
+  // remove local low depth & output as contigs (main_assemble.cpp:270-301)
+  if (prune_level >= 1) {
+    uint64_t n_removed = 0;
+    CK(mhx_unitig_iterate_local_low_depth(c, &ix, min_depth, (uint32_t)max_tip_len, local_width, low_local_ratio, is_final_round ? 0 : 1, &n_removed));
+    info("Number of local low depth unitigs removed: %llu, complex bubbles removed: 0, time: %.4f", (unsigned long long)n_removed, t.lap());
+    CK(mhx_unitig_finish(c, &ix, &ur));
+    fetch_graph();
+    if (!is_final_round) {
+      output_contigs(true, prefix + ".addi.fa");
+    } else {
+      output_contigs(false, prefix + ".contigs.fa");
+      mhxio::write_contigs(prefix + ".addi.fa", f.k, {}, 1);  // the writer is opened at every prune level >= 1
+    }
+    // (the reference computes the changed-only statistics here without printing them: CalcAndPrintStat(graph, false, true))
+  }
   mhxio::write_contigs(prefix + ".bubble_seq.fa", f.k, {}, 1);  // bubble level 0: no bubble
-  info("Time to output: %.4f", t.lap());
   return finish(c);
 }
 

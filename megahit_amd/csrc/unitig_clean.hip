@@ -1,8 +1,10 @@
-// Graph cleaning on the device-resident unitig graph: what `assemble --bubble_level 0 --prune_level 0 --cleaning_rounds N`
-// does between UnitigGraph::UnitigGraph and OutputContigs (reference src/main_assemble.cpp:182-249) —
+// Graph cleaning on the device-resident unitig graph: what `assemble --bubble_level 0 --prune_level 0..2 --cleaning_rounds N`
+// does between UnitigGraph::UnitigGraph and the last OutputContigs (reference src/main_assemble.cpp:182-301) —
 //   DisconnectWeakLinks  assembly/weak_link_remover.cpp
 //   RemoveTips           assembly/tip_remover.cpp (on the unitig graph, not the SdBG-level one of sdbg_tips.hip)
-//   UnitigGraph::Refresh assembly/unitig_graph.cpp:140-355 (RefreshDisconnected, deletion, path and cycle merging, compaction)
+//   RemoveLocalLowDepth, IterateLocalLowDepth  assembly/low_depth_remover.cpp:10-102 (prune levels 1 and 2)
+//   UnitigGraph::Refresh assembly/unitig_graph.cpp:140-355 (RefreshDisconnected, deletion, path and cycle merging, compaction,
+//                        the is_changed mark of Refresh(true))
 // on MHX_BUF_UNITIG_VERTICES (the vertex table mhx_sdbg_unitigs left) and MHX_BUF_SDBG_INVALID.  The result is the
 // reference's at -t 1, where every step is independent of the order the vertices are visited in.
 //
@@ -19,7 +21,8 @@
 //             cycle is cut there and summed by the same jumps.  A hairpin path meets its survivor again in the other
 //             orientation and a self-complementary cycle meets every vertex twice: the sums count them twice, as the
 //             reference's walks do (and such a cycle's survivor deletes itself there, unless it is palindromic: it does here).
-//             Survivors are compacted in index order by a prefix sum.
+//             Survivors are compacted in index order by a prefix sum.  Refresh(true) marks the survivor of a merged path or
+//             cycle MHX_UNITIG_CHANGED (unitig_graph.cpp:293,334); a vertex that merged with nothing keeps the flag it had.
 //   cost      log2(longest merged path) jump rounds with one host synchronisation each, everything else O(1) launches.
 #include "sdbg_nav.h"
 #include "unitig_rank.h"
@@ -138,6 +141,64 @@ __global__ __launch_bounds__(256) void k_uc_tips(DevSdbg g, DevUg u, uint32_t th
     if (del) del = !(atomicOr(&u.mark[v], kDel) & kDel);
   }
   wave_count(del, cnt);
+}
+
+// ---- RemoveLocalLowDepth, one pass (low_depth_remover.cpp:10-86) ----
+// Every decision reads only what the pass never writes: the vertex's own length and average depth, the SdBG degrees at its two
+// ends, and length / total depth of its neighbours; the pass sets to-delete flags and nothing else (Refresh invalidates edges
+// afterwards).  The one thing that depends on the visiting order in the reference is the early `continue` of line 60
+// (is_changed already set and depth > min_depth) — and it changes nothing: threshold is min_depth or, in the else branch,
+// mean * local_ratio <= min_depth, so such a vertex has depth > threshold and is not deleted, and is_changed is already true.
+// Hence, whatever the order:  deleted = the qualifying vertices with depth < threshold;  is_changed = some qualifying vertex has
+// min_depth < mean * local_ratio, or some vertex is deleted;  removed = the number deleted (SetToDelete succeeds once each).
+// Qualifying (lines 49-58): no loop, length <= max_len, in + out degree > 0, and (in <= 1 and out <= 1) or in == 0 or out == 0.
+// LocalDepth in the reference's order and in plain IEEE double, nothing contracted: strand 0's out-neighbours in OutgoingEdges
+// order, then strand 1's (a palindromic vertex has e == re and counts its neighbours twice, as the strand loop does).
+// cnt[0] += flags newly set, cnt[1] |= 1 when is_changed — one atomic each per wavefront that needs it.
+__global__ __launch_bounds__(256) void k_uc_low_depth(DevSdbg g, DevUg u, double min_depth, uint32_t max_len, uint32_t local_width, double local_ratio,
+                                                     unsigned long long *__restrict__ cnt) {
+  const uint64_t v = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  bool del = false, chg = false;
+  if (v < u.nv && !(u.vtx[v].flags & MHX_UNITIG_LOOP) && u.vtx[v].length <= max_len) {
+    const mhx_unitig_vertex vx = u.vtx[v];
+    uint64_t outs[2][4];
+    int deg[2];
+    deg[0] = outs_of(g, vx.e, outs[0]);   // OutDegree
+    deg[1] = outs_of(g, vx.re, outs[1]);  // InDegree
+    if (deg[0] + deg[1] != 0 && ((deg[1] <= 1 && deg[0] <= 1) || deg[1] == 0 || deg[0] == 0)) {
+      double total = 0;
+      uint64_t added = 0;
+#pragma unroll
+      for (int s = 0; s < 2; ++s) {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          if (j >= deg[s]) continue;
+          const uint64_t nb = node_of_edge(u, outs[s][j]);
+          if (nb == kNull) continue;
+          const mhx_unitig_vertex &w = u.vtx[nb >> 1];
+          if (w.length <= local_width) {
+            added += w.length;
+            total = __dadd_rn(total, (double)w.total_depth);
+          } else {
+            added += local_width;
+            total = __dadd_rn(total, __dmul_rn(v_avg(w), (double)local_width));
+          }
+        }
+      }
+      const double mean = added ? total / (double)added : 0.0;
+      const double limit = __dmul_rn(mean, local_ratio);
+      double threshold = min_depth;
+      if (min_depth < limit) chg = true;
+      else threshold = limit;
+      if (v_avg(vx) < threshold) {
+        chg = true;
+        del = !(atomicOr(&u.mark[v], kDel) & kDel);
+      }
+    }
+  }
+  wave_count(del, cnt);
+  const uint64_t m = __ballot(chg);
+  if (m && lane_id() == __builtin_ctzll(m)) atomicOr(cnt + 1, 1ull);
 }
 
 // ---- RefreshDisconnected (unitig_graph.cpp:140-208) ----
@@ -264,12 +325,14 @@ __global__ __launch_bounds__(256) void k_uc_resolve(DevUg u, const uint64_t *__r
 // the survivors' new records, compacted in index order
 __global__ __launch_bounds__(256) void k_uc_write(DevUg u, const uint64_t *__restrict__ succ, const uint64_t *__restrict__ pred, const Rk *__restrict__ rk,
                                                  const uint64_t *__restrict__ lab, const uint32_t *__restrict__ alive, const uint64_t *__restrict__ newid,
-                                                 mhx_unitig_vertex *__restrict__ out) {
+                                                 uint32_t set_changed, mhx_unitig_vertex *__restrict__ out) {
   const uint64_t w = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (w >= u.nv || !alive[w]) return;
   const uint64_t n0 = 2 * w, n1 = (u.vtx[w].flags & MHX_UNITIG_PALINDROME) ? n0 : n0 + 1;
   mhx_unitig_vertex o = u.vtx[w];
-  o.flags &= MHX_UNITIG_LOOP | MHX_UNITIG_PALINDROME;
+  o.flags &= MHX_UNITIG_LOOP | MHX_UNITIG_PALINDROME | MHX_UNITIG_CHANGED;
+  // is_changed: kept, and set on the survivor of a merge when this Refresh marks (set_changed = MHX_UNITIG_CHANGED, else 0)
+  const uint32_t chg = (o.flags & MHX_UNITIG_CHANGED) | set_changed;
   if (o.flags & MHX_UNITIG_LOOP) {
   } else if (lab[n0] != kNull) {  // unitig_graph.cpp:309-333: the walk from (w, 0) round the cycle, cut at (w, 0)
     const uint64_t P = pred[n0], N = succ[n1];
@@ -277,7 +340,7 @@ __global__ __launch_bounds__(256) void k_uc_write(DevUg u, const uint64_t *__res
     if (N != kNull) o.rb = v_begin(u.vtx[N >> 1], (unsigned)(N & 1));  // NextSimplePathEdge(re)
     o.total_depth = rk[P].val;
     o.length = (uint32_t)rk[P].d;
-    o.flags = MHX_UNITIG_LOOP | (o.b == o.rb ? MHX_UNITIG_PALINDROME : 0u);
+    o.flags = MHX_UNITIG_LOOP | (o.b == o.rb ? MHX_UNITIG_PALINDROME : 0u) | chg;
   } else if (succ[n0] != kNull || pred[n0] != kNull) {  // unitig_graph.cpp:275-292: the walk X .. Y from the end without a predecessor
     const uint64_t H = rk[n0].head, T = rk[n1].head ^ 1;
     const uint64_t X = (H >> 1) <= (T >> 1) ? H : (T ^ 1), Y = (H >> 1) <= (T >> 1) ? T : (H ^ 1);
@@ -290,7 +353,7 @@ __global__ __launch_bounds__(256) void k_uc_write(DevUg u, const uint64_t *__res
     o.re = s ? ne : nre;
     o.total_depth = rk[Y].val;
     o.length = (uint32_t)rk[Y].d;
-    o.flags = o.b == o.rb ? MHX_UNITIG_PALINDROME : 0u;
+    o.flags = (o.b == o.rb ? MHX_UNITIG_PALINDROME : 0u) | chg;
   }
   out[newid[w]] = o;
 }
@@ -300,7 +363,7 @@ __global__ __launch_bounds__(256) void k_uc_final_flags(DevSdbg g, mhx_unitig_ve
   const uint64_t v = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
   bool loop = false;
   if (v < nv) {
-    uint32_t f = vtx[v].flags & (MHX_UNITIG_LOOP | MHX_UNITIG_PALINDROME);
+    uint32_t f = vtx[v].flags & (MHX_UNITIG_LOOP | MHX_UNITIG_PALINDROME | MHX_UNITIG_CHANGED);
     loop = f & MHX_UNITIG_LOOP;
     uint64_t outs[4];
     if (loop || (outs_of(g, vtx[v].e, outs) == 0 && outs_of(g, vtx[v].re, outs) == 0)) f |= MHX_UNITIG_STANDALONE;
@@ -354,8 +417,8 @@ struct Clean {
     return (uint64_t)h;
   }
 
-  // UnitigGraph::Refresh
-  void refresh() {
+  // UnitigGraph::Refresh(set_changed)
+  void refresh(bool set_changed = false) {
     const uint64_t nv = u.nv, n = g.n, nn = 2 * nv;
     if (!nv) return;
     uint64_t *inv = c->ws("uc_inv", nn * 2 * 8 + 64).as<uint64_t>();
@@ -401,7 +464,8 @@ struct Clean {
     MHX_LAUNCH(c, "clean_merge", (double)nv * 96, hipLaunchKernelGGL(k_uc_resolve, grid(nv), dim3(256), 0, st, u, succ, pred, rr.rk, lab, alive, rep));
     exclusive_scan_u32_u64(c, alive, newid, nv, newid + nv);
     MHX_LAUNCH(c, "clean_merge", (double)nv * 160,
-               hipLaunchKernelGGL(k_uc_write, grid(nv), dim3(256), 0, st, u, succ, pred, rr.rk, lab, alive, newid, tmp));
+               hipLaunchKernelGGL(k_uc_write, grid(nv), dim3(256), 0, st, u, succ, pred, rr.rk, lab, alive, newid,
+                                  set_changed ? MHX_UNITIG_CHANGED : 0u, tmp));
     MHX_LAUNCH(c, "clean_owner", (double)n * 12, hipLaunchKernelGGL(k_uc_own_rename, grid(n), dim3(256), 0, st, u.own, n, nv, rep, newid));
     uint64_t nv_new = 0;
     MHX_HIP(hipMemcpyAsync(&nv_new, newid + nv, 8, hipMemcpyDeviceToHost, st));
@@ -411,6 +475,21 @@ struct Clean {
     MHX_HIP(hipMemsetAsync(u.mark, 0, nv * 4, st));
     u.nv = c->ut_nv = nv_new;
     c->results[MHX_BUF_UNITIG_VERTICES].used = nv_new * sizeof(mhx_unitig_vertex);
+  }
+
+  // RemoveLocalLowDepth: one marking pass, one host read of both words, and a Refresh only when something was deleted
+  bool low_depth(double min_depth, uint32_t max_len, uint32_t local_width, double local_ratio, bool mark_changed, uint64_t *n_removed) {
+    *n_removed = 0;
+    if (!u.nv) return false;
+    MHX_HIP(hipMemsetAsync(cnt, 0, 16, st));
+    MHX_LAUNCH(c, "clean_low_depth", (double)u.nv * 240,
+               hipLaunchKernelGGL(k_uc_low_depth, grid(u.nv), dim3(256), 0, st, g, u, min_depth, max_len, local_width, local_ratio, cnt));
+    unsigned long long h[2] = {0, 0};
+    MHX_HIP(hipMemcpyAsync(h, cnt, 16, hipMemcpyDeviceToHost, st));
+    MHX_HIP(hipStreamSynchronize(st));
+    if (h[0]) refresh(mark_changed);
+    *n_removed = (uint64_t)h[0];
+    return h[1] != 0;
   }
 };
 
@@ -440,6 +519,31 @@ int unitig_remove_tips(mhx_ctx *c, const mhx_sdbg_index_info *info, uint32_t max
       total += k.read_count();
     }
     k.refresh();
+  }
+  if (n_removed) *n_removed = total;
+  return 0;
+}
+
+int unitig_remove_local_low_depth(mhx_ctx *c, const mhx_sdbg_index_info *info, double min_depth, uint32_t max_len, uint32_t local_width,
+                                  double local_ratio, int mark_changed, uint64_t *n_removed, int *is_changed) {
+  Clean k(c, info, "unitig_remove_local_low_depth");
+  uint64_t n = 0;
+  const bool chg = k.low_depth(min_depth, max_len, local_width, local_ratio, mark_changed != 0, &n);
+  if (n_removed) *n_removed = n;
+  if (is_changed) *is_changed = chg ? 1 : 0;
+  return 0;
+}
+
+int unitig_iterate_local_low_depth(mhx_ctx *c, const mhx_sdbg_index_info *info, double min_depth, uint32_t max_len, uint32_t local_width,
+                                   double local_ratio, int mark_changed, uint64_t *n_removed) {
+  Clean k(c, info, "unitig_iterate_local_low_depth");
+  uint64_t total = 0;
+  // low_depth_remover.cpp:88-102: until a pass changes nothing, min_depth * 1.1 each time (host double), below kMaxMul
+  while (min_depth < 65535.0) {
+    uint64_t n = 0;
+    if (!k.low_depth(min_depth, max_len, local_width, local_ratio, mark_changed != 0, &n)) break;
+    total += n;
+    min_depth *= 1.1;
   }
   if (n_removed) *n_removed = total;
   return 0;

@@ -35,7 +35,7 @@ BUF_LIB_RECORDS = 40
 BUF_UNITIG_VERTICES = 41
 BUF_UNITIG_SEQ = 42
 BUF_UNITIG_OFFSET = 43
-UNITIG_LOOP, UNITIG_PALINDROME, UNITIG_STANDALONE = 1, 2, 4
+UNITIG_LOOP, UNITIG_PALINDROME, UNITIG_STANDALONE, UNITIG_CHANGED = 1, 2, 4, 8
 # one mhx_unitig_vertex (include/mhx.h)
 UNITIG_VERTEX_DTYPE = np.dtype([("b", np.uint64), ("e", np.uint64), ("rb", np.uint64), ("re", np.uint64), ("total_depth", np.uint64),
                                 ("length", np.uint32), ("flags", np.uint32)])
@@ -146,6 +146,10 @@ SYMBOLS = {
     "mhx_sdbg_unitigs": (C.c_int, [_P, C.POINTER(SdbgIndexInfo), C.POINTER(UnitigResult)]),
     "mhx_unitig_disconnect_weak_links": (C.c_int, [_P, C.POINTER(SdbgIndexInfo), C.c_double, C.POINTER(C.c_uint64)]),
     "mhx_unitig_remove_tips": (C.c_int, [_P, C.POINTER(SdbgIndexInfo), C.c_uint32, C.POINTER(C.c_uint64)]),
+    "mhx_unitig_remove_local_low_depth": (C.c_int, [_P, C.POINTER(SdbgIndexInfo), C.c_double, C.c_uint32, C.c_uint32, C.c_double, C.c_int,
+                                                    C.POINTER(C.c_uint64), C.POINTER(C.c_int)]),
+    "mhx_unitig_iterate_local_low_depth": (C.c_int, [_P, C.POINTER(SdbgIndexInfo), C.c_double, C.c_uint32, C.c_uint32, C.c_double, C.c_int,
+                                                     C.POINTER(C.c_uint64)]),
     "mhx_unitig_finish": (C.c_int, [_P, C.POINTER(SdbgIndexInfo), C.POINTER(UnitigResult)]),
     "mhx_comm_unique_id": (C.c_int, [_P]),
     "mhx_comm_init_rank": (_P, [_P, _P, C.c_int, C.c_int]),
@@ -425,6 +429,23 @@ class Engine:
         n = C.c_uint64(0)
         self._chk(self.lib.mhx_unitig_remove_tips(self.h, C.byref(info), int(max_tip_len), C.byref(n)))
         return int(n.value)
+
+    def unitig_remove_local_low_depth(self, info, min_depth, max_len, local_width=1000, local_ratio=0.2, mark_changed=False):
+        """One RemoveLocalLowDepth pass, with its Refresh when something was deleted (include/mhx.h:
+        mhx_unitig_remove_local_low_depth); returns (vertices deleted, is_changed).  mark_changed: survivors of merges get
+        UNITIG_CHANGED."""
+        n, chg = C.c_uint64(0), C.c_int(0)
+        self._chk(self.lib.mhx_unitig_remove_local_low_depth(self.h, C.byref(info), float(min_depth), int(max_len), int(local_width),
+                                                             float(local_ratio), int(bool(mark_changed)), C.byref(n), C.byref(chg)))
+        return n.value, bool(chg.value)
+
+    def unitig_iterate_local_low_depth(self, info, min_depth, max_len, local_width=1000, local_ratio=0.2, mark_changed=False):
+        """IterateLocalLowDepth: passes at min_depth, 1.1 * min_depth, ... until one changes nothing (include/mhx.h:
+        mhx_unitig_iterate_local_low_depth); returns the vertices deleted in all."""
+        n = C.c_uint64(0)
+        self._chk(self.lib.mhx_unitig_iterate_local_low_depth(self.h, C.byref(info), float(min_depth), int(max_len), int(local_width),
+                                                              float(local_ratio), int(bool(mark_changed)), C.byref(n)))
+        return n.value
 
     def unitig_finish(self, info):
         """Flags, contig text and offsets of the cleaned vertex table (include/mhx.h: mhx_unitig_finish); returns a

@@ -4,9 +4,11 @@ workload family, synth.gen_shard_library), graph by `mhx_core read2sdbg -k 21 -m
 text), and the reference's `megahit_core assemble` on the same graph at -t 1 and -t 16: wall times and the digest of
 .contigs.fa (equal to ours at -t 1); the wall time of mhx_core again --wall-runs times without MHX_PROFILE.  --clean: the same with `--cleaning_rounds 5` and MHX_ASSEMBLE_CLEAN=1 (the weak-link
 and tip rounds on the device: the clean_* kernel groups), the reference's cleaning time summed from its per-step log lines.
+--prune: `--prune_level 2 --min_depth 2 --cleaning_rounds 5` and MHX_ASSEMBLE_PRUNE=1 (what an unmodified `megahit --bubble-level 0`
+asks for; the low-depth passes are the clean_low_depth group, their number its launches), the digests of .contigs.fa and .addi.fa.
 Too slow for the suite.  One JSON line on stdout.
 
-    python tools/unitig_bench.py [--clean] [--reads 10000000] [--ref oracle/_ref/ref_megahit_core] [--ref-threads 1,16] [--workdir DIR]"""
+    python tools/unitig_bench.py [--clean | --prune] [--reads 10000000] [--ref oracle/_ref/ref_megahit_core] [--ref-threads 1,16] [--workdir DIR]"""
 import argparse
 import hashlib
 import json
@@ -42,8 +44,11 @@ def main():
     ap.add_argument("--workdir", default=None)
     ap.add_argument("--wall-runs", type=int, default=5, help="runs of mhx_core assemble without MHX_PROFILE for the wall time")
     ap.add_argument("--clean", action="store_true", help="--cleaning_rounds 5 on the GPU route (MHX_ASSEMBLE_CLEAN=1)")
+    ap.add_argument("--prune", action="store_true", help="--prune_level 2 --min_depth 2 --cleaning_rounds 5 on the GPU route (MHX_ASSEMBLE_PRUNE=1)")
     a = ap.parse_args()
     qual = QUAL[:-1] + ["5"] if a.clean else QUAL
+    if a.prune:
+        qual = ["--bubble_level", "0", "--prune_level", "2", "--min_depth", "2", "--cleaning_rounds", "5"]
     d = a.workdir or tempfile.mkdtemp(prefix="mhx_unitig")
     os.makedirs(d, exist_ok=True)
     res = {"reads": a.reads, "k": a.k, "options": " ".join(qual)}
@@ -52,14 +57,18 @@ def main():
     g = os.path.join(d, "g")
     subprocess.run([MHX_CORE, "read2sdbg", "-k", str(a.k), "-m", "2", "--host_mem", "2e10", "--num_cpu_threads", "16", "--read_lib_file",
                     os.path.join(d, "reads"), "--output_prefix", g], check=True, stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL)
-    env = dict(os.environ, MHX_PROFILE="1", MHX_SERVER="off", MHX_ASSEMBLE_CLEAN="1" if a.clean else "0")
+    env = dict(os.environ, MHX_PROFILE="1", MHX_SERVER="off", MHX_ASSEMBLE_CLEAN="1" if a.clean else "0", MHX_ASSEMBLE_PRUNE="1" if a.prune else "0")
     t0 = time.time()
     p = subprocess.run([MHX_CORE, "assemble", "-s", g, "-o", os.path.join(d, "mine"), "-t", "16"] + qual, env=env, stdout=subprocess.DEVNULL,
                        stderr=subprocess.PIPE, text=True, check=True)
     res["mhx_wall_s"] = round(time.time() - t0, 3)
     res["kernels_ms"] = {m.group(1): float(m.group(2)) for m in re.finditer(r"profile (\S+)\s+\d+ launches\s+([\d.]+) ms", p.stderr)}
-    res["log"] = [l for l in p.stderr.splitlines() if re.search(r"Edges|Tips|unitig graph size|palindrome|Max:|output|disconnected", l)]
+    res["log"] = [l for l in p.stderr.splitlines() if re.search(r"Edges|Tips|unitig graph size|palindrome|Max:|output|disconnected|pruning|low depth", l)]
     res["mhx_digest"] = md5(os.path.join(d, "mine.contigs.fa"))
+    if a.prune:
+        m = re.search(r"profile clean_low_depth\s+(\d+) launches", p.stderr)
+        res["low_depth_passes"] = int(m.group(1)) if m else None
+        res["mhx_addi_digest"] = md5(os.path.join(d, "mine.addi.fa"))
     # the wall time files to files with the profiler off (the events of MHX_PROFILE serialise the launches): every run listed
     env.pop("MHX_PROFILE")
     walls = []
@@ -85,9 +94,17 @@ def main():
             if a.clean:  # "Tips removed: N, time: T" and "Number unitigs disconnected: N, time: T" of every round
                 res["ref_t%d_cleaning_s" % t] = round(sum(float(x) for x in re.findall(r"(?:Tips removed|disconnected): \d+, time: ([\d.]+)", q.stderr)), 3)
                 res["ref_t%d_rounds" % t] = re.findall(r"(?:Tips removed|disconnected): (\d+)", q.stderr)
+            if a.prune:
+                res["ref_t%d_cleaning_s" % t] = round(sum(float(x) for x in re.findall(r"(?:Tips removed|disconnected|excessive pruning): \d+, time: ([\d.]+)",
+                                                                                      q.stderr)), 3)
+                res["ref_t%d_rounds" % t] = re.findall(r"(?:Tips removed|disconnected|excessive pruning): (\d+)", q.stderr)
+                m = re.search(r"local low depth unitigs removed: (\d+), complex bubbles removed: 0, time: ([\d.]+)", q.stderr)
+                res["ref_t%d_low_depth" % t] = [int(m.group(1)), float(m.group(2))] if m else None
             if t == 1:
                 res["ref_t1_digest"] = md5(out + ".contigs.fa")
                 res["digest_equal"] = res["ref_t1_digest"] == res["mhx_digest"]
+                if a.prune:
+                    res["addi_digest_equal"] = md5(out + ".addi.fa") == res["mhx_addi_digest"]
     print(json.dumps(res))
 
 
