@@ -233,7 +233,10 @@ enum mhx_buffer {
   /* the unitig graph of mhx_sdbg_unitigs (below), kept in HBM for the graph-cleaning steps (mhx_unitig_*, below) */
   MHX_BUF_UNITIG_VERTICES = 41, /* mhx_unitig_vertex[n_vertices], the reference's vertex order on one thread */
   MHX_BUF_UNITIG_SEQ = 42,      /* char[n_bases]: every vertex's contig text ('ACGT', before FoldPalindrome), back to back */
-  MHX_BUF_UNITIG_OFFSET = 43    /* uint64[n_vertices + 1]: where vertex v's text starts in MHX_BUF_UNITIG_SEQ */
+  MHX_BUF_UNITIG_OFFSET = 43,   /* uint64[n_vertices + 1]: where vertex v's text starts in MHX_BUF_UNITIG_SEQ */
+  /* the --careful_bubble records of the last mhx_unitig_pop_bubbles call (below), in the order the reference writes them at -t 1 */
+  MHX_BUF_UNITIG_BUBBLE_REC = 44, /* mhx_bubble_record[n_records] */
+  MHX_BUF_UNITIG_BUBBLE_SEQ = 45  /* char[]: the records' text ('ACGT'), back to back */
 };
 /* bytes currently held in a result buffer (0 if absent) */
 uint64_t mhx_buffer_bytes(const mhx_ctx *, int which);
@@ -382,6 +385,7 @@ int mhx_sdbg_unitigs(mhx_ctx *, const mhx_sdbg_index_info *info, mhx_unitig_resu
  * The CLI (`mhx_core assemble`) runs the cleaning rounds only when MHX_ASSEMBLE_CLEAN=1 or MHX_ASSEMBLE_PRUNE=1 is in its
  * environment and only at --bubble_level 0; --prune_level 1 and 2 (with an explicit --min_depth > 0) run here only with
  * MHX_ASSEMBLE_PRUNE=1, which implies the cleaning rounds.  Otherwise such command lines are forwarded to MHX_REF_CORE.
+ * MHX_ASSEMBLE_BUBBLE=1 (further below) implies both and adds the bubble levels 1 and 2 and prune level 3.
  * MHX_ASSEMBLE_REF=1 wins. */
 int mhx_unitig_disconnect_weak_links(mhx_ctx *, const mhx_sdbg_index_info *info, double ratio, uint64_t *n_flagged);
 int mhx_unitig_remove_tips(mhx_ctx *, const mhx_sdbg_index_info *info, uint32_t max_tip_len, uint64_t *n_removed);
@@ -390,6 +394,55 @@ int mhx_unitig_remove_local_low_depth(mhx_ctx *, const mhx_sdbg_index_info *info
 int mhx_unitig_iterate_local_low_depth(mhx_ctx *, const mhx_sdbg_index_info *info, double min_depth, uint32_t max_len, uint32_t local_width,
                                        double local_ratio, int mark_changed, uint64_t *n_removed);
 int mhx_unitig_finish(mhx_ctx *, const mhx_sdbg_index_info *info, mhx_unitig_result *out);
+/* Bubble popping and prune level 3 on the same unitig graph (same validity rules and stale-state errors as the calls above):
+ * with them the cleaning calls cover `assemble --bubble_level 0..2 --prune_level 0..3` (main_assemble.cpp:182-301) but for
+ * InferMinDepth.  The result is the reference's at any -t: a search reads only what the pass never writes and sets only
+ * to-delete flags, so the deleted set is a union and the count the number of distinct vertices in it.
+ *   mhx_unitig_pop_bubbles  BaseBubbleRemover::PopBubbles (assembly/bubble_remover.cpp:58-152), one thread per (vertex, strand)
+ *       node: a node with d >= 2 out-neighbours ("middles"), none longer than max_len, each with in-degree 1 and one
+ *       out-neighbour, all the same node ("right") whose canonical id min(b, rb) is >= the left's and whose in-degree is d, is
+ *       a bubble.  The middles are sorted by average depth (descending; ties: canonical id ascending) and all but the first
+ *       are deleted.  similarity <= 0 is NaiveBubbleRemover (the caller passes max_len = k + 2).  similarity > 0 is
+ *       ComplexBubbleRemover (the caller passes max_len = lround(merge_len * k / similarity)): every (middle[0], middle[j])
+ *       must pass (len_j + k - 1) * similarity <= len_0 + k - 1, the same the other way round, and GetSimilarity >=
+ *       similarity on the two vertices' own texts (mhx_unitig_similarity below), or the bubble stays; when max_len *
+ *       (1 - similarity) < 1 the call returns 0 at once, as the reference does.  Then a Refresh, which marks the survivors of
+ *       merges MHX_UNITIG_CHANGED when mark_changed != 0 (the reference's permanent_rm = false) — skipped when no flag was
+ *       set, where it would change nothing.  *n_removed = vertices deleted.
+ *       careful_threshold >= 0 (`--careful_bubble`: 0.2): a popped bubble leaves records — every deleted middle with average
+ *       depth >= that of middle[0] * careful_threshold and, when there is one, the left and the right vertex — each the
+ *       vertex's text (as in MHX_BUF_UNITIG_SEQ, taken before the Refresh) and average depth.  *n_records = their number;
+ *       MHX_BUF_UNITIG_BUBBLE_REC / _SEQ hold them until the next call, ordered by left vertex, strand 0 then 1, middle.
+ *       A bubble seen from both of its ends or from a palindromic left is counted once and recorded twice (as the reference).
+ *       The text comes from mhx_unitig_finish, which the call runs by itself when a Refresh ran since the last one and it
+ *       has a pair to compare or a record to write.
+ *       Cap: in complex mode max_len + k <= MHX_SIM_MAX_LEN and (max_len + k) * (1 - similarity) < MHX_SIM_MAX_INDEL + 1,
+ *       else an error.
+ *   mhx_unitig_bubble_stats  of the last mhx_unitig_pop_bubbles: out[0] = complex candidates (bubbles that passed the
+ *       structural and length tests), out[1] / out[2] = pairs whose similarity passed / failed, out[3] = mid-run finishes.
+ *   mhx_unitig_remove_low_depth  RemoveLowDepth (low_depth_remover.cpp:104-117): every vertex with average depth < min_depth
+ *       is deleted, then a Refresh (no marks).  Prune level 3.
+ *   mhx_unitig_similarity  GetSimilarity (bubble_remover.cpp:10-54) of two host strings on the device, the kernel the complex
+ *       mode uses: with max_indel = (int)(max(n, m) * (1 - similarity)), 0 when |n - m| > max_indel or max_indel < 1, else
+ *       1 - d / max(n, m) for the edit distance d inside the band of 2 * max_indel + 1 diagonals with the reference's
+ *       boundary conditions, in IEEE double.  Needs no graph.  Strings longer than MHX_SIM_MAX_LEN or a max_indel above
+ *       MHX_SIM_MAX_INDEL are an error (two band rows of 4-byte cells are kept in 32 KB of LDS).
+ * The CLI runs these only with MHX_ASSEMBLE_BUBBLE=1 in its environment (which implies MHX_ASSEMBLE_PRUNE and _CLEAN):
+ * --bubble_level 0..2, --prune_level 0..3 (levels 1..3 with an explicit --min_depth > 0), --careful_bubble or not, and
+ * --merge_len / --merge_similar within the cap at k = MHX_MAX_K.  Everything else is forwarded as before. */
+#define MHX_SIM_MAX_LEN 16384
+#define MHX_SIM_MAX_INDEL 2047
+typedef struct {
+  uint64_t offset;   /* where the text starts in MHX_BUF_UNITIG_BUBBLE_SEQ */
+  uint32_t length;   /* characters: the vertex's length + k */
+  uint32_t vertex;   /* index in the vertex table the pass ran on */
+  double avg_depth;  /* total_depth / length: the record's multiplicity */
+} mhx_bubble_record;
+int mhx_unitig_pop_bubbles(mhx_ctx *, const mhx_sdbg_index_info *info, uint32_t max_len, double similarity, double careful_threshold,
+                           int mark_changed, uint64_t *n_removed, uint64_t *n_records);
+int mhx_unitig_bubble_stats(mhx_ctx *, uint64_t out[4]);
+int mhx_unitig_remove_low_depth(mhx_ctx *, const mhx_sdbg_index_info *info, double min_depth, uint64_t *n_removed);
+int mhx_unitig_similarity(mhx_ctx *, const char *a, uint32_t n, const char *b, uint32_t m, double similarity, double *out);
 /* install an SdBG produced elsewhere (e.g. read back from .sdbg.* files: bucket byte ranges back to back) as the handle's
  * current SdBG; the four tables have 65536 entries (starting byte, items, tips, large multiplicities per bucket) */
 int mhx_sdbg_load_bytes(mhx_ctx *, const uint8_t *bytes, uint64_t n_bytes, const uint64_t *bucket_offset, const uint64_t *bucket_items,

@@ -894,6 +894,31 @@ int mhx_unitig_finish(mhx_ctx *c, const mhx_sdbg_index_info *info, mhx_unitig_re
     mhx::unitig_finish(c, info, out);
   })
 }
+int mhx_unitig_pop_bubbles(mhx_ctx *c, const mhx_sdbg_index_info *info, uint32_t max_len, double similarity, double careful_threshold,
+                           int mark_changed, uint64_t *n_removed, uint64_t *n_records) {
+  MHX_TRY({
+    MHX_HIP(hipSetDevice(c->device));
+    mhx::unitig_pop_bubbles(c, info, max_len, similarity, careful_threshold, mark_changed, n_removed, n_records);
+  })
+}
+int mhx_unitig_bubble_stats(mhx_ctx *c, uint64_t out[4]) {
+  MHX_TRY({
+    if (!out) throw mhx::Error("unitig_bubble_stats: bad arguments");
+    for (int i = 0; i < 4; ++i) out[i] = c->ub_stats[i];
+  })
+}
+int mhx_unitig_remove_low_depth(mhx_ctx *c, const mhx_sdbg_index_info *info, double min_depth, uint64_t *n_removed) {
+  MHX_TRY({
+    MHX_HIP(hipSetDevice(c->device));
+    mhx::unitig_remove_low_depth(c, info, min_depth, n_removed);
+  })
+}
+int mhx_unitig_similarity(mhx_ctx *c, const char *a, uint32_t n, const char *b, uint32_t m, double similarity, double *out) {
+  MHX_TRY({
+    MHX_HIP(hipSetDevice(c->device));
+    mhx::unitig_similarity(c, a, n, b, m, similarity, out);
+  })
+}
 int mhx_sdbg_load_bytes(mhx_ctx *c, const uint8_t *bytes, uint64_t n_bytes, const uint64_t *bucket_offset, const uint64_t *bucket_items,
                         const uint64_t *bucket_tips, const uint64_t *bucket_large) {
   MHX_TRY({

@@ -1213,8 +1213,11 @@ int main_iterate(int argc, char **argv) {
 // with --cleaning_rounds N >= 1 as well: the rounds of RemoveTips and DisconnectWeakLinks on the unitig graph
 // (main_assemble.cpp:182-249 at bubble level 0 and prune level 0) — and, with MHX_ASSEMBLE_PRUNE=1, at --prune_level 1 or 2
 // with an explicit --min_depth > 0 (InferMinDepth is not built): RemoveLocalLowDepth inside the rounds (level 2), the
-// IterateLocalLowDepth after them and the .addi.fa of the changed contigs (main_assemble.cpp:238-301).  Every other option
-// set goes to the reference.
+// IterateLocalLowDepth after them and the .addi.fa of the changed contigs (main_assemble.cpp:238-301) — and, with
+// MHX_ASSEMBLE_BUBBLE=1 (which implies the other two), at --bubble_level 0..2 and --prune_level 0..3: the naive and complex
+// PopBubbles of the rounds, RemoveLowDepth and its pops at prune level 3, the final complex pop after the iteration and the
+// --careful_bubble records in .bubble_seq.fa, when --merge_len / --merge_similar fit the similarity kernel's cap at k =
+// MHX_MAX_K (include/mhx.h: MHX_SIM_MAX_LEN, MHX_SIM_MAX_INDEL).  Every other option set goes to the reference.
 // The SdBG files are read back into HBM, indexed (mhx_sdbg_build_index), trimmed (mhx_sdbg_remove_tips), turned into the
 // unitig graph and its contig text (mhx_sdbg_unitigs), cleaned in place (mhx_unitig_*); the host folds palindromes and
 // writes the ContigWriter files.  The cleaned result is the reference's at -t 1 whatever -t says.
@@ -1236,6 +1239,8 @@ void add_assemble_options(Options &o) {  // main_assemble.cpp:66-101
   o.add("output_standalone", "", true, "");
   o.add("careful_bubble", "", true, "");
 }
+// ComplexBubbleRemover::PopBubbles' max_len (bubble_remover.cpp:155-157): unsigned product, double quotient
+uint32_t complex_max_len(int merge_len, uint32_t k, double sim) { return (uint32_t)lround((uint32_t)merge_len * k / sim); }
 // decided from argv alone, before anything touches HIP (forwarding is an execv)
 bool assemble_on_gpu(int argc, char **argv) {
   if (getenv("MHX_ASSEMBLE_REF") && atoi(getenv("MHX_ASSEMBLE_REF")) != 0) return false;
@@ -1248,6 +1253,19 @@ bool assemble_on_gpu(int argc, char **argv) {
   }
   if (o.get("sdbg_name").empty()) return false;
   const int prune_level = atoi(o.get("prune_level").c_str()), rounds = atoi(o.get("cleaning_rounds").c_str());
+  if (getenv("MHX_ASSEMBLE_BUBBLE") && atoi(getenv("MHX_ASSEMBLE_BUBBLE")) != 0) {  // bubble popping and prune level 3 on the GPU: opt-in
+    const int bubble_level = atoi(o.get("bubble_level").c_str()), merge_len = atoi(o.get("merge_len").c_str());
+    const double sim = atof(o.get("merge_similar").c_str());
+    if (bubble_level < 0 || bubble_level > 2 || prune_level < 0 || prune_level > 3 || rounds < 0) return false;
+    if (prune_level >= 1 && !(atof(o.get("min_depth").c_str()) > 0)) return false;  // InferMinDepth is the reference's
+    if (bubble_level >= 2) {
+      // the similarity kernel's cap, at the largest k there is: k is not known before the graph is read
+      if (merge_len < 0 || !(sim > 0 && sim <= 1)) return false;
+      const double longest = (double)complex_max_len(merge_len, MHX_MAX_K, sim) + MHX_MAX_K;
+      if (longest > MHX_SIM_MAX_LEN || longest * (1 - sim) >= MHX_SIM_MAX_INDEL + 1) return false;
+    }
+    return true;
+  }
   if (atoi(o.get("bubble_level").c_str()) != 0) return false;
   const bool prune = getenv("MHX_ASSEMBLE_PRUNE") && atoi(getenv("MHX_ASSEMBLE_PRUNE")) != 0;  // low-depth pruning on the GPU: opt-in
   if (prune_level != 0)  // levels 1 and 2 with a given minimum depth; the variable implies the cleaning rounds
@@ -1335,11 +1353,39 @@ int main_assemble(int argc, char **argv) {
          (unsigned long long)(hist.empty() ? 0 : hist.rbegin()->first), (unsigned long long)(hist.empty() ? 0 : hist.begin()->first),
          (unsigned long long)n50, (unsigned long long)vtx.size(), (unsigned long long)n_isolated, (unsigned long long)n_looped, (unsigned long long)total);
   };
-  // graph cleaning (main_assemble.cpp:182-249 with bubble level 0 and prune level 0, 1 or 2)
+  // graph cleaning (main_assemble.cpp:170-249)
   const int cleaning_rounds = atoi(o.get("cleaning_rounds").c_str()), prune_level = atoi(o.get("prune_level").c_str());
-  const bool is_final_round = o.get("is_final_round") == "1";
+  const int bubble_level = atoi(o.get("bubble_level").c_str()), merge_len = atoi(o.get("merge_len").c_str());
+  const bool is_final_round = o.get("is_final_round") == "1", careful_bubble = o.get("careful_bubble") == "1";
   const double min_depth = atof(o.get("min_depth").c_str()), low_local_ratio = atof(o.get("low_local_ratio").c_str());
+  const double merge_similar = atof(o.get("merge_similar").c_str());
   const uint32_t local_width = 1000;  // AssemblerOptions::local_width: no command-line option sets it
+  // the --careful_bubble records of every pass, in call order: ContigWriter records with id 0, flag 0 and the average depth
+  std::deque<std::string> bubble_text;
+  std::vector<mhxio::ContigRecord> bubble_recs;
+  uint64_t n_finishes = 0;  // mid-run finishes the pops needed for their text
+  // one PopBubbles call; with_writer: the remover still holds the bubble writer
+  auto pop_bubbles = [&](bool complex_mode, bool mark_changed, bool with_writer) {
+    uint64_t n_removed = 0, n_records = 0;
+    const uint32_t max_len = complex_mode ? complex_max_len(merge_len, f.k, merge_similar) : f.k + 2;
+    CK(mhx_unitig_pop_bubbles(c, &ix, max_len, complex_mode ? merge_similar : 0.0, careful_bubble && with_writer ? 0.2 : -1.0, mark_changed ? 1 : 0,
+                              &n_removed, &n_records));
+    uint64_t st[4] = {0, 0, 0, 0};
+    CK(mhx_unitig_bubble_stats(c, st));
+    n_finishes += st[3];
+    if (complex_mode)  // (not a line of the reference's)
+      info("Complex bubble candidates: %llu, similarity passed: %llu, failed: %llu", (unsigned long long)st[0], (unsigned long long)st[1],
+           (unsigned long long)st[2]);
+    if (n_records) {
+      const std::vector<mhx_bubble_record> recs = fetch<mhx_bubble_record>(c, MHX_BUF_UNITIG_BUBBLE_REC);
+      const std::vector<char> text = fetch<char>(c, MHX_BUF_UNITIG_BUBBLE_SEQ);
+      for (const mhx_bubble_record &r : recs) {
+        bubble_text.emplace_back(text.data() + r.offset, r.length);
+        bubble_recs.push_back(mhxio::ContigRecord{0, 0, r.avg_depth, bubble_text.back().data(), bubble_text.back().size()});
+      }
+    }
+    return n_removed;
+  };
   if (cleaning_rounds > 0) {
     print_stat(fetch<mhx_unitig_vertex>(c, MHX_BUF_UNITIG_VERTICES));
     const double disconnect_ratio = atof(o.get("disconnect_ratio").c_str());
@@ -1352,11 +1398,27 @@ int main_assemble(int argc, char **argv) {
         changed |= n_tips > 0;
         info("Tips removed: %llu, time: %.3f", (unsigned long long)n_tips, t.lap());
       }
+      if (bubble_level >= 1) {
+        const uint64_t n_bubbles = pop_bubbles(false, false, true);
+        info("Number of bubbles removed: %llu, Time elapsed(sec): %.3f", (unsigned long long)n_bubbles, t.lap());
+        changed |= n_bubbles > 0;
+      }
+      if (bubble_level >= 2) {
+        const uint64_t n_bubbles = pop_bubbles(true, false, true);
+        info("Number of complex bubbles removed: %llu, Time elapsed(sec): %.4f", (unsigned long long)n_bubbles, t.lap());
+        changed |= n_bubbles > 0;
+      }
       uint64_t n_disconnected = 0;
       CK(mhx_unitig_disconnect_weak_links(c, &ix, disconnect_ratio, &n_disconnected));
       info("Number unitigs disconnected: %llu, time: %.3f", (unsigned long long)n_disconnected, t.lap());
       changed |= n_disconnected > 0;
-      if (prune_level >= 2) {  // excessive pruning: permanent (no marks); its count does not feed `changed`
+      if (prune_level >= 3) {  // more-excessive pruning: permanent; its count does not feed `changed`
+        uint64_t n_pruned = 0;
+        CK(mhx_unitig_remove_low_depth(c, &ix, min_depth, &n_pruned));
+        n_pruned += pop_bubbles(false, false, true);
+        if (bubble_level >= 2 && merge_len > 0) n_pruned += pop_bubbles(true, false, true);
+        info("Unitigs removed in (more-)excessive pruning: %llu, time: %.3f", (unsigned long long)n_pruned, t.lap());
+      } else if (prune_level >= 2) {  // excessive pruning: permanent (no marks); its count does not feed `changed`
         uint64_t n_pruned = 0;
         CK(mhx_unitig_remove_local_low_depth(c, &ix, min_depth, (uint32_t)max_tip_len, local_width, std::min(low_local_ratio, 0.1), 0, &n_pruned,
                                              nullptr));
@@ -1413,7 +1475,10 @@ int main_assemble(int argc, char **argv) {
   if (prune_level >= 1) {
     uint64_t n_removed = 0;
     CK(mhx_unitig_iterate_local_low_depth(c, &ix, min_depth, (uint32_t)max_tip_len, local_width, low_local_ratio, is_final_round ? 0 : 1, &n_removed));
-    info("Number of local low depth unitigs removed: %llu, complex bubbles removed: 0, time: %.4f", (unsigned long long)n_removed, t.lap());
+    uint64_t n_bubbles = 0;  // the complex remover has lost its writer by now (main_assemble.cpp:282)
+    if (bubble_level >= 2 && merge_len > 0) n_bubbles = pop_bubbles(true, true, false);
+    info("Number of local low depth unitigs removed: %llu, complex bubbles removed: %llu, time: %.4f", (unsigned long long)n_removed,
+         (unsigned long long)n_bubbles, t.lap());
     CK(mhx_unitig_finish(c, &ix, &ur));
     fetch_graph();
     if (!is_final_round) {
@@ -1424,7 +1489,8 @@ int main_assemble(int argc, char **argv) {
     }
     // (the reference computes the changed-only statistics here without printing them: CalcAndPrintStat(graph, false, true))
   }
-  mhxio::write_contigs(prefix + ".bubble_seq.fa", f.k, {}, 1);  // bubble level 0: no bubble
+  mhxio::write_contigs(prefix + ".bubble_seq.fa", f.k, bubble_recs, 1);
+  if (bubble_level >= 1) info("Bubble records: %llu, mid-run finishes for their text and the similarity: %llu", (unsigned long long)bubble_recs.size(), (unsigned long long)n_finishes);
   return finish(c);
 }
 

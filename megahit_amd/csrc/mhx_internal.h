@@ -107,6 +107,9 @@ struct mhx_ctx {
   // (unitig_clean.hip): valid until the SdBG or its index is replaced.  ut_owner: ws "uc_owner" maps every edge to its vertex
   bool ut_ready = false, ut_owner = false;
   uint64_t ut_edges = 0, ut_nv = 0;
+  // MHX_BUF_UNITIG_SEQ / _OFFSET describe the vertex table as it is now (no Refresh ran since they were written)
+  bool ut_text_fresh = false;
+  uint64_t ub_stats[4] = {0, 0, 0, 0};  // the last mhx_unitig_pop_bubbles: candidates, pairs passed, pairs failed, mid-run finishes
   // tuning knobs (mhx_set_option): explicit value, else environment MHX_<NAME>, else the default
   std::map<std::string, long long> options;
   // tuned defaults of this installation: `name = value` lines of mhx_tuning.conf beside libmhx.so (MHX_TUNING_FILE names
@@ -301,6 +304,10 @@ int unitig_remove_local_low_depth(mhx_ctx *c, const mhx_sdbg_index_info *info, d
 int unitig_iterate_local_low_depth(mhx_ctx *c, const mhx_sdbg_index_info *info, double min_depth, uint32_t max_len, uint32_t local_width,
                                    double local_ratio, int mark_changed, uint64_t *n_removed);
 int unitig_finish(mhx_ctx *c, const mhx_sdbg_index_info *info, mhx_unitig_result *out);
+int unitig_remove_low_depth(mhx_ctx *c, const mhx_sdbg_index_info *info, double min_depth, uint64_t *n_removed);
+int unitig_pop_bubbles(mhx_ctx *c, const mhx_sdbg_index_info *info, uint32_t max_len, double similarity, double careful_threshold, int mark_changed,
+                       uint64_t *n_removed, uint64_t *n_records);
+int unitig_similarity(mhx_ctx *c, const char *a, uint32_t n, const char *b, uint32_t m, double sim, double *out);
 int iterate_edges(mhx_ctx *c, uint32_t k, uint32_t step, const uint32_t *ctg_words, uint64_t ctg_n_words, uint64_t n_ctg, const uint64_t *ctg_start,
                   mhx_iterate_result *out);
 int fastx_to_records(mhx_ctx *c, const char *text1, uint64_t n1, const char *text2, uint64_t n2, mhx_fastx_result *out);

@@ -275,7 +275,7 @@ void write_text(mhx_ctx *c, const DevSdbg &g, const Rk *rk, uint64_t nv, uint64_
 int sdbg_unitigs(mhx_ctx *c, const mhx_sdbg_index_info *info, mhx_unitig_result *out) {
   hipStream_t st = c->stream;
   const DevSdbg g = dev_sdbg(c, info, "sdbg_unitigs");
-  c->ut_ready = c->ut_owner = false;
+  c->ut_ready = c->ut_owner = c->ut_text_fresh = false;
   memset(out, 0, sizeof *out);
   auto grid = Ranker::grid;
   EdgeRank er(c, g.n);
@@ -330,7 +330,7 @@ int sdbg_unitigs(mhx_ctx *c, const mhx_sdbg_index_info *info, mhx_unitig_result 
                                   out_head, oh_off, vtx, out_vid, len));
   }
   write_text(c, g, rk, nv, n_loop, len, out_head, oh_off, out_vid, cnt, out);
-  c->ut_ready = true;
+  c->ut_ready = c->ut_text_fresh = true;
   c->ut_edges = n;
   c->ut_nv = nv;
   return 0;

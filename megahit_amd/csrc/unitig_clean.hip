@@ -1,8 +1,11 @@
-// Graph cleaning on the device-resident unitig graph: what `assemble --bubble_level 0 --prune_level 0..2 --cleaning_rounds N`
+// Graph cleaning on the device-resident unitig graph: what `assemble --bubble_level 0..2 --prune_level 0..3 --cleaning_rounds N`
 // does between UnitigGraph::UnitigGraph and the last OutputContigs (reference src/main_assemble.cpp:182-301) —
 //   DisconnectWeakLinks  assembly/weak_link_remover.cpp
 //   RemoveTips           assembly/tip_remover.cpp (on the unitig graph, not the SdBG-level one of sdbg_tips.hip)
 //   RemoveLocalLowDepth, IterateLocalLowDepth  assembly/low_depth_remover.cpp:10-102 (prune levels 1 and 2)
+//   RemoveLowDepth       assembly/low_depth_remover.cpp:104-117 (prune level 3)
+//   PopBubbles           assembly/bubble_remover.cpp (NaiveBubbleRemover, ComplexBubbleRemover with GetSimilarity, the
+//                        --careful_bubble records; bubble levels 1 and 2)
 //   UnitigGraph::Refresh assembly/unitig_graph.cpp:140-355 (RefreshDisconnected, deletion, path and cycle merging, compaction,
 //                        the is_changed mark of Refresh(true))
 // on MHX_BUF_UNITIG_VERTICES (the vertex table mhx_sdbg_unitigs left) and MHX_BUF_SDBG_INVALID.  The result is the
@@ -201,6 +204,278 @@ __global__ __launch_bounds__(256) void k_uc_low_depth(DevSdbg g, DevUg u, double
   if (m && lane_id() == __builtin_ctzll(m)) atomicOr(cnt + 1, 1ull);
 }
 
+// ---- RemoveLowDepth (low_depth_remover.cpp:104-117): every vertex below min_depth, loops included ----
+__global__ __launch_bounds__(256) void k_uc_remove_low_depth(DevUg u, double min_depth, unsigned long long *__restrict__ cnt) {
+  const uint64_t v = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  bool del = false;
+  if (v < u.nv && v_avg(u.vtx[v]) < min_depth) del = !(atomicOr(&u.mark[v], kDel) & kDel);
+  wave_count(del, cnt);
+}
+
+// ---- BaseBubbleRemover::PopBubbles (bubble_remover.cpp:58-152) ----
+// SearchAndPopBubble reads only what the pass never writes (SdBG degrees and neighbours, vertex lengths, total depths, begin and
+// end edges) and writes only to-delete flags, whose fetch-or return value is the count.  So the deleted set is the union over the
+// (vertex, strand) nodes of what each search finds and the count is the number of distinct vertices in it, whatever the order:
+// one thread per node.  A bubble whose left and right are the same vertex is found from both sides and a palindromic left twice
+// from the same end: the second visit sets no new flag — but writes its careful records again, as the reference does.
+//   find   the structural tests and the sort of the middles (average depth descending, canonical id ascending).  Naive mode
+//          (the checker is always true) marks at once; complex mode runs the checker's two length-ratio tests and lists the
+//          node as a candidate.  With careful records or in complex mode the sorted middles and the right vertex are kept per node.
+//   score  complex mode: GetSimilarity of (middle[0], middle[j]) for every candidate, one wavefront per pair (k_uc_similarity).
+//   mark   complex mode: the candidates whose pairs all passed.
+//   records  --careful_bubble: rec_n[node] = middles j >= 1 with avg >= avg(middle[0]) * threshold, + 2 (left, right) when there
+//          is one; a prefix sum over the nodes is the reference's -t 1 order (vertex index, strand 0 then 1, then j).
+struct BubArgs {
+  uint32_t max_len, k;
+  double sim;      // <= 0: naive
+  double careful;  // < 0: no records
+};
+struct BubBuf {
+  uint32_t *mid;    // [4 * nodes] the sorted middles' vertices
+  uint32_t *right;  // [nodes] the right vertex
+  uint32_t *deg;    // [nodes] the bubble's degree; 0: no bubble starts here
+  uint32_t *rec_n;  // [nodes]
+};
+__device__ __forceinline__ uint64_t v_canon(const mhx_unitig_vertex &v) { return v.b < v.rb ? v.b : v.rb; }
+// marks middle[1..] and counts this node's records; returns the flags newly set
+__device__ __forceinline__ unsigned bubble_pop(const DevUg &u, const uint32_t mid[4], int deg, double careful, uint32_t *rec_n) {
+  unsigned newly = 0, recs = 0;
+  const double limit = careful >= 0 ? __dmul_rn(v_avg(u.vtx[mid[0]]), careful) : 0.0;
+  for (int j = 1; j < deg; ++j) {
+    newly += !(atomicOr(&u.mark[mid[j]], kDel) & kDel);
+    if (careful >= 0 && v_avg(u.vtx[mid[j]]) >= limit) ++recs;
+  }
+  if (rec_n) *rec_n = recs ? recs + 2 : 0;
+  return newly;
+}
+__global__ __launch_bounds__(256) void k_uc_bubble_find(DevSdbg g, DevUg u, BubArgs a, BubBuf bb, uint64_t *__restrict__ cand, unsigned long long *__restrict__ cnt) {
+  const uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const bool keep = a.sim > 0 || a.careful >= 0;
+  unsigned newly = 0;
+  int found = 0;  // the degree of the bubble that starts here
+  uint32_t mid[4] = {kNoVtx, kNoVtx, kNoVtx, kNoVtx}, rv = kNoVtx;
+  if (t < 2 * u.nv && !(u.vtx[t >> 1].flags & MHX_UNITIG_LOOP)) {
+    const mhx_unitig_vertex left = u.vtx[t >> 1];
+    uint64_t outs[4], tmp[4];
+    const int deg = outs_of(g, v_end(left, (unsigned)(t & 1)), outs);
+    bool ok = deg > 1;
+    uint64_t nd[4] = {kNull, kNull, kNull, kNull}, right_b = kNull;
+    for (int j = 0; ok && j < deg; ++j) {
+      nd[j] = node_of_edge(u, outs[j]);
+      ok = nd[j] != kNull && u.vtx[nd[j] >> 1].length <= a.max_len;
+    }
+    for (int j = 0; ok && j < deg; ++j) {
+      const mhx_unitig_vertex &m = u.vtx[nd[j] >> 1];
+      const unsigned s = (unsigned)(nd[j] & 1);
+      ok = outs_of(g, v_end(m, s ^ 1), tmp) == 1 && outs_of(g, v_end(m, s), tmp) == 1;  // InDegree, GetNextAdapters
+      if (!ok) break;
+      if (j == 0) {
+        right_b = tmp[0];
+        const uint64_t r = node_of_edge(u, right_b);
+        ok = r != kNull;
+        if (ok) {
+          const mhx_unitig_vertex &rx = u.vtx[r >> 1];
+          rv = (uint32_t)(r >> 1);
+          ok = v_canon(rx) >= v_canon(left) && outs_of(g, v_end(rx, (unsigned)(r & 1) ^ 1), tmp) == deg;
+        }
+      } else {
+        ok = tmp[0] == right_b;
+      }
+    }
+    if (ok) {
+      // std::sort of at most four adapters: an insertion sort with the reference's comparator
+      double avg[4] = {0, 0, 0, 0};
+      uint64_t can[4] = {0, 0, 0, 0};
+      for (int j = 0; j < deg; ++j) {
+        const mhx_unitig_vertex &m = u.vtx[nd[j] >> 1];
+        const double d = v_avg(m);
+        const uint64_t cid = v_canon(m);
+        const uint32_t w = (uint32_t)(nd[j] >> 1);
+        int p = j;
+        while (p > 0 && (d != avg[p - 1] ? d > avg[p - 1] : cid < can[p - 1])) {
+          avg[p] = avg[p - 1];
+          can[p] = can[p - 1];
+          mid[p] = mid[p - 1];
+          --p;
+        }
+        avg[p] = d;
+        can[p] = cid;
+        mid[p] = w;
+      }
+      if (a.sim > 0) {  // ComplexBubbleRemover's checker, the length part (bubble_remover.cpp:164-165)
+        const double l0 = (double)(u.vtx[mid[0]].length + a.k - 1);
+        for (int j = 1; ok && j < deg; ++j) {
+          const double lj = (double)(u.vtx[mid[j]].length + a.k - 1);
+          ok = __dmul_rn(lj, a.sim) <= l0 && __dmul_rn(l0, a.sim) <= lj;
+        }
+      }
+      if (ok) found = deg;
+    }
+  }
+  uint32_t rec_n = 0;
+  if (found && !(a.sim > 0)) newly = bubble_pop(u, mid, found, a.careful, &rec_n);
+  if (keep && t < 2 * u.nv) {
+    bb.deg[t] = (uint32_t)found;
+    bb.rec_n[t] = rec_n;
+    if (found) {
+      for (int j = 0; j < 4; ++j) bb.mid[4 * t + j] = mid[j];
+      bb.right[t] = rv;
+    }
+  }
+  if (a.sim > 0) push_list(found != 0, t, cand, cnt + 1);
+  const unsigned total = wave_sum(newly);
+  if (total && lane_id() == 0) atomicAdd(cnt, (unsigned long long)total);
+}
+
+// ---- GetSimilarity (bubble_remover.cpp:10-54): the banded edit distance of two strings, one wavefront per pair ----
+// Cell c of row i stands for column j = i + c - D (D = max_indel), c in [0, 2D].  The cell above-left (j - 1 of row i - 1) is
+// the same c of the previous row, the cell above (j of row i - 1) is c + 1 of it, and the cell to the left is c - 1 of this row:
+//   t[c]  = min(INF, prev[c] + (a[i-1] != b[j-1]), prev[c+1] + 1 when c < 2D)        every lane on its own
+//   dp[c] = min(t[c], dp[c-1] + 1) = c + min over c' <= c of (t[c'] - c')            a prefix minimum: integer min-plus, exact
+// The cells of a row that the reference computes are contiguous: j = max(i - D, 1) .. min(m, i + D), and j = 0 (value i) to
+// their left while i <= D; every other cell of the row is INF (0x3f3f3f3f) as its std::fill leaves it.  Row 0 is j for j >= 0
+// and 0 below, as its resize leaves it.  Rows of more than 64 cells go in 64-cell chunks with the running minimum carried
+// from chunk to chunk.  The two rows live in LDS: lane l reads words c and c + 1 = consecutive banks, no conflict.
+// Cap: max_indel <= kSimMaxIndel (band of 4095 cells, 2 rows * 4096 * 4 bytes = 32 KB of LDS) and strings of <= kSimMaxLen.
+constexpr int kSimMaxIndel = MHX_SIM_MAX_INDEL, kSimRow = 2 * kSimMaxIndel + 2, kSimInf = 0x3f3f3f3f;
+constexpr uint32_t kSimMaxLen = MHX_SIM_MAX_LEN;
+static_assert(2 * kSimRow * sizeof(int) <= 32768, "the two rows of the band take half of a workgroup's default 64 KB of LDS");
+struct SimPair {
+  uint64_t a, b;  // where the two strings start in the text
+  uint32_t n, m;
+};
+__device__ __forceinline__ int wave_inclusive_min(int v) {
+#pragma unroll
+  for (int d = 1; d < kWave; d <<= 1) {
+    const int o = __shfl_up(v, d, kWave);
+    if (lane_id() >= d) v = o < v ? o : v;
+  }
+  return v;
+}
+__device__ double wave_similarity(const char *__restrict__ sa, int n, const char *__restrict__ sb, int m, double one_minus_sim, int (*row)[kSimRow]) {
+  const int lane = lane_id();
+  const int mx = n > m ? n : m;
+  const int D = (int)__dmul_rn((double)mx, one_minus_sim);
+  if (abs(n - m) > D || D < 1 || D > kSimMaxIndel) return 0.0;  // (beyond the cap: the host refused before the launch)
+  const int W = 2 * D + 1;
+  for (int c = lane; c < W; c += kWave) row[0][c] = c >= D ? c - D : 0;
+  __syncthreads();
+  for (int i = 1; i <= n; ++i) {
+    int *cur = row[i & 1];
+    const int *prev = row[(i & 1) ^ 1];
+    const char ca = sa[i - 1];
+    const int c_lo = i <= D ? D - i : 0, c_hi = (m - i + D < 2 * D) ? m - i + D : 2 * D;
+    int carry = 0x7fffffff;
+    for (int cb = 0; cb < W; cb += kWave) {
+      const int c = cb + lane;
+      const bool valid = c >= c_lo && c <= c_hi;
+      int x = 0x7fffffff;
+      if (valid) {
+        const int j = i + c - D;
+        int tv = i;  // j == 0
+        if (j > 0) {
+          tv = kSimInf;
+          const int dg = prev[c] + (ca != sb[j - 1]);
+          tv = dg < tv ? dg : tv;
+          if (c < 2 * D) {
+            const int up = prev[c + 1] + 1;
+            tv = up < tv ? up : tv;
+          }
+        }
+        x = tv - c;
+      }
+      x = wave_inclusive_min(x);
+      x = carry < x ? carry : x;
+      carry = __shfl(x, kWave - 1, kWave);
+      if (c < W) cur[c] = valid ? x + c : kSimInf;
+    }
+    __syncthreads();
+  }
+  const int d = row[n & 1][m - n + D];
+  return __dsub_rn(1.0, __ddiv_rn((double)d, (double)mx));  // 1 - d * 1.0 / max(n, m)
+}
+// one block of one wavefront per pair (blocks stride over the pairs)
+__global__ __launch_bounds__(64) void k_uc_similarity(const char *__restrict__ text, const SimPair *__restrict__ pairs, uint64_t n_pairs, double one_minus_sim,
+                                                     double *__restrict__ out) {
+  __shared__ int row[2][kSimRow];
+  for (uint64_t p = blockIdx.x; p < n_pairs; p += gridDim.x) {
+    const SimPair q = pairs[p];
+    const double r = q.n == 0xffffffffu ? 2.0 : wave_similarity(text + q.a, (int)q.n, text + q.b, (int)q.m, one_minus_sim, row);  // (n = ~0: no such pair)
+    if (lane_id() == 0) out[p] = r;
+    __syncthreads();
+  }
+}
+// the pairs of the candidates: slot 3 * i + j - 1 is (middle[0], middle[j]) of candidate i, each in its own unique format —
+// the text of mhx_unitig_finish — so the two may lie on opposite strands, as in the reference
+__global__ __launch_bounds__(256) void k_uc_bubble_pairs(BubBuf bb, const uint64_t *__restrict__ cand, uint64_t n_cand, const uint64_t *__restrict__ off,
+                                                       SimPair *__restrict__ pairs) {
+  const uint64_t x = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (x >= 3 * n_cand) return;
+  const uint64_t t = cand[x / 3];
+  const int j = (int)(x % 3) + 1;
+  SimPair q{0, 0, 0xffffffffu, 0};
+  if (j < (int)bb.deg[t]) {
+    const uint32_t va = bb.mid[4 * t], vb = bb.mid[4 * t + j];
+    q = SimPair{off[va], off[vb], (uint32_t)(off[va + 1] - off[va]), (uint32_t)(off[vb + 1] - off[vb])};
+  }
+  pairs[x] = q;
+}
+// cnt[0] += flags newly set; cnt[2] += pairs that passed, cnt[3] += pairs that failed
+__global__ __launch_bounds__(256) void k_uc_bubble_mark(DevUg u, BubArgs a, BubBuf bb, const uint64_t *__restrict__ cand, uint64_t n_cand,
+                                                      const double *__restrict__ score, unsigned long long *__restrict__ cnt) {
+  const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  unsigned newly = 0, pass = 0, fail = 0;
+  if (i < n_cand) {
+    const uint64_t t = cand[i];
+    const int deg = (int)bb.deg[t];
+    // the reference stops at the first failing pair; the later ones are scored here all the same and counted as they fall
+    for (int j = 1; j < deg; ++j) (score[3 * i + j - 1] >= a.sim ? pass : fail) += 1;
+    uint32_t rec_n = 0;
+    if (!fail) {
+      uint32_t mid[4];
+      for (int j = 0; j < 4; ++j) mid[j] = bb.mid[4 * t + j];
+      newly = bubble_pop(u, mid, deg, a.careful, &rec_n);
+    } else {
+      bb.deg[t] = 0;
+    }
+    bb.rec_n[t] = rec_n;
+  }
+  const unsigned tn = wave_sum(newly), tp = wave_sum(pass), tf = wave_sum(fail);
+  if (lane_id() == 0) {
+    if (tn) atomicAdd(cnt, (unsigned long long)tn);
+    if (tp) atomicAdd(cnt + 2, (unsigned long long)tp);
+    if (tf) atomicAdd(cnt + 3, (unsigned long long)tf);
+  }
+}
+// --careful_bubble records (bubble_remover.cpp:109-132) of node t at rec_off[t] ..: the middles that pass, then left, right
+__global__ __launch_bounds__(256) void k_uc_bubble_records(DevUg u, BubArgs a, BubBuf bb, const uint64_t *__restrict__ rec_off, mhx_bubble_record *__restrict__ rec,
+                                                         uint64_t *__restrict__ rec_len) {
+  const uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= 2 * u.nv || !bb.rec_n[t]) return;
+  uint64_t o = rec_off[t];
+  const int deg = (int)bb.deg[t];
+  const double limit = __dmul_rn(v_avg(u.vtx[bb.mid[4 * t]]), a.careful);
+  auto put = [&](uint32_t w) {
+    const mhx_unitig_vertex &vx = u.vtx[w];
+    rec[o] = mhx_bubble_record{0, vx.length + a.k, w, v_avg(vx)};
+    rec_len[o] = (uint64_t)vx.length + a.k;
+    ++o;
+  };
+  for (int j = 1; j < deg; ++j)
+    if (v_avg(u.vtx[bb.mid[4 * t + j]]) >= limit) put(bb.mid[4 * t + j]);
+  put((uint32_t)(t >> 1));
+  put(bb.right[t]);
+}
+__global__ __launch_bounds__(256) void k_uc_bubble_text(const char *__restrict__ text, const uint64_t *__restrict__ off, const uint64_t *__restrict__ rec_pos, uint64_t n_rec,
+                                                      mhx_bubble_record *__restrict__ rec, char *__restrict__ out) {
+  for (uint64_t r = blockIdx.x; r < n_rec; r += gridDim.x) {
+    const uint64_t src = off[rec[r].vertex], dst = rec_pos[r];
+    const uint32_t len = rec[r].length;
+    for (uint32_t i = threadIdx.x; i < len; i += blockDim.x) out[dst + i] = text[src + i];
+    if (threadIdx.x == 0) rec[r].offset = dst;
+  }
+}
+
 // ---- RefreshDisconnected (unitig_graph.cpp:140-208) ----
 // plan: the new ends of every trimmed vertex (navigation on the SdBG as it is: a unitig's inner edges see only each other,
 // whatever other vertices drop); inv[4v ..] = the edges to invalidate.  bad: a navigation that found no edge.
@@ -381,7 +656,9 @@ struct Clean {
 
   static dim3 grid(uint64_t m) { return Ranker::grid(m); }
 
-  Clean(mhx_ctx *c_, const mhx_sdbg_index_info *info, const char *who) : c(c_), st(c_->stream) {
+  const mhx_sdbg_index_info *info;
+
+  Clean(mhx_ctx *c_, const mhx_sdbg_index_info *info_, const char *who) : c(c_), st(c_->stream), info(info_) {
     if (!info) throw Error(std::string(who) + ": no index info");
     if (!c->ut_ready || info->n_items != c->ut_edges) throw Error(std::string(who) + ": run mhx_sdbg_unitigs on this index first");
     g = dev_sdbg(c, info, who);
@@ -421,6 +698,7 @@ struct Clean {
   void refresh(bool set_changed = false) {
     const uint64_t nv = u.nv, n = g.n, nn = 2 * nv;
     if (!nv) return;
+    c->ut_text_fresh = false;
     uint64_t *inv = c->ws("uc_inv", nn * 2 * 8 + 64).as<uint64_t>();
     MHX_HIP(hipMemsetAsync(cnt, 0, 16, st));
     MHX_LAUNCH(c, "clean_disconnect", (double)nv * 96, hipLaunchKernelGGL(k_uc_disc_plan, grid(nv), dim3(256), 0, st, g, u, inv, cnt + 1));
@@ -491,6 +769,100 @@ struct Clean {
     *n_removed = (uint64_t)h[0];
     return h[1] != 0;
   }
+
+  // the text of the vertex table as it is now: MHX_BUF_UNITIG_SEQ / _OFFSET are those of the last finish (or of
+  // mhx_sdbg_unitigs) and stay good until a Refresh runs; a mid-run finish rebuilds them (and clobbers cnt)
+  void need_text() {
+    if (c->ut_text_fresh) return;
+    mhx_unitig_result r;
+    unitig_finish(c, info, &r);
+    ++c->ub_stats[3];
+  }
+  // BaseBubbleRemover::PopBubbles; sim <= 0: NaiveBubbleRemover's checker, else ComplexBubbleRemover's (bubble_remover.cpp:154-170)
+  void pop_bubbles(uint32_t max_len, double sim, double careful, bool mark_changed, uint64_t *n_removed, uint64_t *n_records) {
+    *n_removed = *n_records = 0;
+    for (uint64_t &x : c->ub_stats) x = 0;
+    c->result(MHX_BUF_UNITIG_BUBBLE_REC, 0);
+    c->result(MHX_BUF_UNITIG_BUBBLE_SEQ, 0);
+    const bool complex_mode = sim > 0, want_records = careful >= 0;
+    if (complex_mode && (double)max_len * (1 - sim) < 1) return;  // the reference returns before its Refresh
+    const uint64_t nv = u.nv, nn = 2 * nv;
+    if (!nv) return;
+    if (complex_mode) {
+      const uint64_t longest = (uint64_t)max_len + g.k;
+      if (longest > kSimMaxLen || (double)longest * (1 - sim) >= (double)(kSimMaxIndel + 1))
+        throw Error("unitig_pop_bubbles: max_len and similarity are beyond the cap of the similarity kernel (MHX_SIM_MAX_LEN, MHX_SIM_MAX_INDEL)");
+    }
+    const BubArgs a{max_len, g.k, complex_mode ? sim : 0.0, want_records ? careful : -1.0};
+    BubBuf bb{nullptr, nullptr, nullptr, nullptr};
+    uint64_t *cand = nullptr;
+    if (complex_mode || want_records) {
+      bb.mid = c->ws("ub_mid", nn * 16 + 64).as<uint32_t>();
+      bb.right = c->ws("ub_right", nn * 4 + 64).as<uint32_t>();
+      bb.deg = c->ws("ub_deg", nn * 4 + 64).as<uint32_t>();
+      bb.rec_n = c->ws("ub_rec_n", nn * 4 + 64).as<uint32_t>();
+    }
+    if (complex_mode) cand = c->ws("ub_cand", nn * 8 + 64).as<uint64_t>();
+    MHX_HIP(hipMemsetAsync(cnt, 0, 32, st));
+    MHX_LAUNCH(c, "clean_bubbles", (double)nn * 300, hipLaunchKernelGGL(k_uc_bubble_find, grid(nn), dim3(256), 0, st, g, u, a, bb, cand, cnt));
+    unsigned long long h[4] = {0, 0, 0, 0};
+    MHX_HIP(hipMemcpyAsync(h, cnt, 32, hipMemcpyDeviceToHost, st));
+    MHX_HIP(hipStreamSynchronize(st));
+    uint64_t removed = h[0];
+    const uint64_t n_cand = complex_mode ? h[1] : 0;
+    if (n_cand) {
+      c->ub_stats[0] = n_cand;
+      need_text();
+      const char *text = c->results[MHX_BUF_UNITIG_SEQ].as<char>();
+      const uint64_t *off = c->results[MHX_BUF_UNITIG_OFFSET].as<uint64_t>();
+      const uint64_t n_pairs = 3 * n_cand;
+      SimPair *pairs = c->ws("ub_pairs", n_pairs * sizeof(SimPair) + 64).as<SimPair>();
+      double *score = c->ws("ub_score", n_pairs * 8 + 64).as<double>();
+      MHX_HIP(hipMemsetAsync(cnt, 0, 32, st));
+      hipLaunchKernelGGL(k_uc_bubble_pairs, grid(n_pairs), dim3(256), 0, st, bb, cand, n_cand, off, pairs);
+      const unsigned blocks = (unsigned)std::min<uint64_t>(n_pairs, 1u << 20);
+      MHX_LAUNCH(c, "clean_similarity", (double)n_pairs * 2 * (max_len + g.k),
+                 hipLaunchKernelGGL(k_uc_similarity, dim3(blocks), dim3(64), 0, st, text, pairs, n_pairs, 1 - sim, score));
+      MHX_LAUNCH(c, "clean_bubbles", (double)n_cand * 100,
+                 hipLaunchKernelGGL(k_uc_bubble_mark, grid(n_cand), dim3(256), 0, st, u, a, bb, cand, n_cand, score, cnt));
+      MHX_HIP(hipMemcpyAsync(h, cnt, 32, hipMemcpyDeviceToHost, st));
+      MHX_HIP(hipStreamSynchronize(st));
+      removed = h[0];
+      c->ub_stats[1] = h[2];
+      c->ub_stats[2] = h[3];
+    }
+    if (want_records && removed) {  // (a record needs a popped bubble, and its flags are among this pass's)
+      uint64_t *rec_off = c->ws("ub_rec_off", (nn + 2) * 8).as<uint64_t>();
+      exclusive_scan_u32_u64(c, bb.rec_n, rec_off, nn, rec_off + nn);
+      uint64_t n_rec = 0;
+      MHX_HIP(hipMemcpyAsync(&n_rec, rec_off + nn, 8, hipMemcpyDeviceToHost, st));
+      MHX_HIP(hipStreamSynchronize(st));
+      if (n_rec) {
+        need_text();  // before the Refresh: the records are the vertices as the pass saw them
+        const char *text = c->results[MHX_BUF_UNITIG_SEQ].as<char>();
+        const uint64_t *off = c->results[MHX_BUF_UNITIG_OFFSET].as<uint64_t>();
+        mhx_bubble_record *rec = c->result(MHX_BUF_UNITIG_BUBBLE_REC, n_rec * sizeof(mhx_bubble_record)).as<mhx_bubble_record>();
+        uint64_t *rec_len = c->ws("ub_rec_len", n_rec * 8 + 64).as<uint64_t>();
+        uint64_t *rec_pos = c->ws("ub_rec_pos", (n_rec + 2) * 8).as<uint64_t>();
+        hipLaunchKernelGGL(k_uc_bubble_records, grid(nn), dim3(256), 0, st, u, a, bb, rec_off, rec, rec_len);
+        MHX_HIP(hipGetLastError());
+        exclusive_scan_u64(c, rec_len, rec_pos, n_rec, rec_pos + n_rec);
+        uint64_t n_chars = 0;
+        MHX_HIP(hipMemcpyAsync(&n_chars, rec_pos + n_rec, 8, hipMemcpyDeviceToHost, st));
+        MHX_HIP(hipStreamSynchronize(st));
+        char *out = c->result(MHX_BUF_UNITIG_BUBBLE_SEQ, n_chars).as<char>();
+        MHX_LAUNCH(c, "clean_bubbles", (double)n_chars * 2,
+                   hipLaunchKernelGGL(k_uc_bubble_text, dim3((unsigned)std::min<uint64_t>(n_rec, 1u << 16)), dim3(256), 0, st, text, off, rec_pos, n_rec, rec, out));
+        *n_records = n_rec;
+      }
+    }
+    // The reference refreshes after every pass.  With no flag set a Refresh changes nothing: the flag words are zero between
+    // calls (every Refresh clears them), so nothing is trimmed or deleted, and every vertex is a maximal simple path already
+    // (the constructor and every earlier Refresh leave them so, and no edge changed since), so nothing merges and no
+    // vertex gets the is_changed mark.  low_depth skips it in the same way.
+    if (removed) refresh(mark_changed);
+    *n_removed = removed;
+  }
 };
 
 }  // namespace
@@ -555,7 +927,52 @@ int unitig_finish(mhx_ctx *c, const mhx_sdbg_index_info *info, mhx_unitig_result
   if (k.u.nv)
     MHX_LAUNCH(c, "clean_flags", (double)k.u.nv * 64, hipLaunchKernelGGL(k_uc_final_flags, Clean::grid(k.u.nv), dim3(256), 0, k.st, k.g, k.u.vtx, k.u.nv, k.cnt));
   const uint64_t n_loop = k.read_count();
-  return sdbg_unitig_text(c, info, k.u.nv, n_loop, out);
+  sdbg_unitig_text(c, info, k.u.nv, n_loop, out);
+  c->ut_text_fresh = true;
+  return 0;
+}
+
+int unitig_remove_low_depth(mhx_ctx *c, const mhx_sdbg_index_info *info, double min_depth, uint64_t *n_removed) {
+  Clean k(c, info, "unitig_remove_low_depth");
+  if (n_removed) *n_removed = 0;
+  if (!k.u.nv) return 0;
+  MHX_HIP(hipMemsetAsync(k.cnt, 0, 8, k.st));
+  MHX_LAUNCH(c, "clean_low_depth", (double)k.u.nv * 40,
+             hipLaunchKernelGGL(k_uc_remove_low_depth, Clean::grid(k.u.nv), dim3(256), 0, k.st, k.u, min_depth, k.cnt));
+  const uint64_t n = k.read_count();
+  if (n) k.refresh(false);  // (with no flag set a Refresh changes nothing: see Clean::pop_bubbles)
+  if (n_removed) *n_removed = n;
+  return 0;
+}
+
+int unitig_pop_bubbles(mhx_ctx *c, const mhx_sdbg_index_info *info, uint32_t max_len, double similarity, double careful_threshold, int mark_changed,
+                       uint64_t *n_removed, uint64_t *n_records) {
+  Clean k(c, info, "unitig_pop_bubbles");
+  uint64_t removed = 0, records = 0;
+  k.pop_bubbles(max_len, similarity, careful_threshold, mark_changed != 0, &removed, &records);
+  if (n_removed) *n_removed = removed;
+  if (n_records) *n_records = records;
+  return 0;
+}
+
+int unitig_similarity(mhx_ctx *c, const char *a, uint32_t n, const char *b, uint32_t m, double sim, double *out) {
+  if (!out || (n && !a) || (m && !b)) throw Error("unitig_similarity: bad arguments");
+  if (!(sim > 0 && sim <= 1)) throw Error("unitig_similarity: the similarity must be in (0, 1]");
+  const uint32_t mx = std::max(n, m);
+  if (mx > kSimMaxLen) throw Error("unitig_similarity: a string is longer than MHX_SIM_MAX_LEN");
+  if ((int)((double)mx * (1 - sim)) > kSimMaxIndel) throw Error("unitig_similarity: max_indel is beyond MHX_SIM_MAX_INDEL");
+  hipStream_t st = c->stream;
+  char *text = c->ws("ub_sim_text", (size_t)n + m + 64).as<char>();
+  SimPair *pair = c->ws("ub_pairs", sizeof(SimPair) + 64).as<SimPair>();
+  double *score = c->ws("ub_score", 64).as<double>();
+  const SimPair q{0, n, n, m};
+  if (n) MHX_HIP(hipMemcpyAsync(text, a, n, hipMemcpyHostToDevice, st));
+  if (m) MHX_HIP(hipMemcpyAsync(text + n, b, m, hipMemcpyHostToDevice, st));
+  MHX_HIP(hipMemcpyAsync(pair, &q, sizeof q, hipMemcpyHostToDevice, st));
+  MHX_LAUNCH(c, "clean_similarity", (double)n + m, hipLaunchKernelGGL(k_uc_similarity, dim3(1), dim3(64), 0, st, text, pair, (uint64_t)1, 1 - sim, score));
+  MHX_HIP(hipMemcpyAsync(out, score, 8, hipMemcpyDeviceToHost, st));
+  MHX_HIP(hipStreamSynchronize(st));
+  return 0;
 }
 
 }  // namespace mhx

@@ -35,6 +35,11 @@ BUF_LIB_RECORDS = 40
 BUF_UNITIG_VERTICES = 41
 BUF_UNITIG_SEQ = 42
 BUF_UNITIG_OFFSET = 43
+BUF_UNITIG_BUBBLE_REC = 44
+BUF_UNITIG_BUBBLE_SEQ = 45
+SIM_MAX_LEN, SIM_MAX_INDEL = 16384, 2047
+# one mhx_bubble_record (include/mhx.h)
+BUBBLE_RECORD_DTYPE = np.dtype([("offset", np.uint64), ("length", np.uint32), ("vertex", np.uint32), ("avg_depth", np.float64)])
 UNITIG_LOOP, UNITIG_PALINDROME, UNITIG_STANDALONE, UNITIG_CHANGED = 1, 2, 4, 8
 # one mhx_unitig_vertex (include/mhx.h)
 UNITIG_VERTEX_DTYPE = np.dtype([("b", np.uint64), ("e", np.uint64), ("rb", np.uint64), ("re", np.uint64), ("total_depth", np.uint64),
@@ -151,6 +156,11 @@ SYMBOLS = {
     "mhx_unitig_iterate_local_low_depth": (C.c_int, [_P, C.POINTER(SdbgIndexInfo), C.c_double, C.c_uint32, C.c_uint32, C.c_double, C.c_int,
                                                      C.POINTER(C.c_uint64)]),
     "mhx_unitig_finish": (C.c_int, [_P, C.POINTER(SdbgIndexInfo), C.POINTER(UnitigResult)]),
+    "mhx_unitig_pop_bubbles": (C.c_int, [_P, C.POINTER(SdbgIndexInfo), C.c_uint32, C.c_double, C.c_double, C.c_int, C.POINTER(C.c_uint64),
+                                         C.POINTER(C.c_uint64)]),
+    "mhx_unitig_bubble_stats": (C.c_int, [_P, C.POINTER(C.c_uint64)]),
+    "mhx_unitig_remove_low_depth": (C.c_int, [_P, C.POINTER(SdbgIndexInfo), C.c_double, C.POINTER(C.c_uint64)]),
+    "mhx_unitig_similarity": (C.c_int, [_P, C.c_char_p, C.c_uint32, C.c_char_p, C.c_uint32, C.c_double, C.POINTER(C.c_double)]),
     "mhx_comm_unique_id": (C.c_int, [_P]),
     "mhx_comm_init_rank": (_P, [_P, _P, C.c_int, C.c_int]),
     "mhx_comm_local_group": (C.c_int, [C.c_int, _P, _P]),
@@ -453,6 +463,42 @@ class Engine:
         r = UnitigResult()
         self._chk(self.lib.mhx_unitig_finish(self.h, C.byref(info), C.byref(r)))
         return r
+
+    def unitig_pop_bubbles(self, info, max_len, similarity=0.0, careful_threshold=-1.0, mark_changed=False):
+        """One PopBubbles pass with its Refresh (include/mhx.h: mhx_unitig_pop_bubbles); returns (vertices deleted, careful
+        records).  similarity <= 0: the naive remover (max_len = k + 2); > 0: the complex one (max_len = lround(merge_len * k /
+        similarity)).  careful_threshold >= 0 leaves the --careful_bubble records for unitig_bubble_records()."""
+        n, r = C.c_uint64(0), C.c_uint64(0)
+        self._chk(self.lib.mhx_unitig_pop_bubbles(self.h, C.byref(info), int(max_len), float(similarity), float(careful_threshold),
+                                                  int(bool(mark_changed)), C.byref(n), C.byref(r)))
+        return int(n.value), int(r.value)
+
+    def unitig_bubble_records(self):
+        """-> [(text, average depth, vertex)] of the last unitig_pop_bubbles call, in the reference's -t 1 order."""
+        rec = self.fetch(BUF_UNITIG_BUBBLE_REC, np.uint8).view(BUBBLE_RECORD_DTYPE)
+        seq = self.fetch(BUF_UNITIG_BUBBLE_SEQ, np.uint8).tobytes().decode()
+        return [(seq[int(r["offset"]):int(r["offset"]) + int(r["length"])], float(r["avg_depth"]), int(r["vertex"])) for r in rec]
+
+    def unitig_bubble_stats(self):
+        """-> dict(candidates, passed, failed, finishes) of the last unitig_pop_bubbles call (mhx_unitig_bubble_stats)."""
+        out = (C.c_uint64 * 4)()
+        self._chk(self.lib.mhx_unitig_bubble_stats(self.h, out))
+        return dict(zip(("candidates", "passed", "failed", "finishes"), (int(x) for x in out)))
+
+    def unitig_remove_low_depth(self, info, min_depth):
+        """RemoveLowDepth + Refresh: every vertex with average depth < min_depth goes (include/mhx.h:
+        mhx_unitig_remove_low_depth); returns the vertices deleted."""
+        n = C.c_uint64(0)
+        self._chk(self.lib.mhx_unitig_remove_low_depth(self.h, C.byref(info), float(min_depth), C.byref(n)))
+        return int(n.value)
+
+    def unitig_similarity(self, a, b, similarity):
+        """GetSimilarity of two strings by the device kernel of the complex bubble remover (include/mhx.h:
+        mhx_unitig_similarity); returns the double.  Beyond SIM_MAX_LEN / SIM_MAX_INDEL it raises."""
+        a, b = (x.encode() if isinstance(x, str) else bytes(x) for x in (a, b))
+        out = C.c_double(0)
+        self._chk(self.lib.mhx_unitig_similarity(self.h, a, len(a), b, len(b), float(similarity), C.byref(out)))
+        return out.value
 
     def unitig_contigs(self):
         """-> (vertices as a UNITIG_VERTEX_DTYPE array, list of contig strings) of the last sdbg_unitigs / unitig_finish call."""
