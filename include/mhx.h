@@ -150,7 +150,12 @@ int mhx_set_option(mhx_ctx *, const char *name, long long value);
  *                          s1_skm_passes (0) forces their number; s1_skm_bin_bits (0 = by density: 16..20) the bins; s1_skm_tags (0) 1: the
  *                          kernel of read sets beyond 2^32 bases on any read set (tests); s1_skm_deal (1) 0: every lane expands its own
  *                          record instead of the wavefront's windows being dealt to the lanes (measured 7 % slower); s1_skm_hp (1) 0: the
- *                          windows of one base (poly-A, poly-G) stay in the records instead of being counted beside them (one GPU)
+ *                          windows of one base (poly-A, poly-G) stay in the records instead of being counted beside them (one GPU);
+ *                          s1_skm_split (1): the make kernel puts every record into the range of its bin's low digit (256 ranges of the
+ *                          array), so the sort starts at the second digit: one 16-byte pass fewer (bins of two digits or more; a range
+ *                          that overflows — skewed bins — makes the records again, unsplit); 0: one cursor and all passes;
+ *                          s1_skm_split_stage (2560): records of a workgroup's trip that are ordered by digit in LDS before they leave
+ *                          (at most 2560; a trip that makes more writes them from the registers; tests shrink it)
  *   count_skm (1)          `count` on super-k-mer records (k_skm_make<.., COUNT>, k_count_skm: a record carries one more base either side of its run,
  *                          the table the in / out characters): one GPU, 19 <= k <= 21, min count <= 2; jobs of more than s1_skm_pass_gb of
  *                          records in passes over ranges of bins (mhx_count_self_planned); 0: never; 3: fail instead of falling back;

@@ -177,6 +177,13 @@ struct SortPrep {
   std::function<void(const OnesweepLaunch &)> gen;
   uint64_t gen_slots = 0;  // item slots it walks (> n when it drops the items of filtered-out lv1 buckets)
   bool gen_var = false;    // ... padded to the longest read's count: reads of several lengths (S1GenVarT; the plan text says so)
+  // first sort pass over an array SPLIT by the digit before the plan's first (sort_kernels.h SrcSplit; 16-byte records): the buffer holds
+  // 256 ranges of split_range_cap slots, range d filled with split_fill[d] (device, [256]) records; n is their sum; range d is read by
+  // the units [split_ubase[d], split_ubase[d + 1]) (device, [257]: ceil(fill / kSortSplitUnit) units each), split_units in all.  The histograms
+  // of the plan's passes then start at row hist_first of "sort_pre_hist" (the rows before it belong to the digits the extraction split by)
+  const unsigned long long *split_fill = nullptr, *split_ubase = nullptr;
+  uint64_t split_range_cap = 0, split_units = 0;
+  int hist_first = 0;
 };
 // Sorts n items of `stride` uint32 words held in buf_a (ping-pong with buf_b) by the digit passes
 // (least-significant pass first).  Returns the buffer holding the result.  prep: what the extraction of exactly these
@@ -188,6 +195,9 @@ uint32_t *sort_whole_key(mhx_ctx *c, uint32_t *buf_a, uint32_t *buf_b, uint64_t 
                          const std::vector<SortPass> &passes, SortPrep *prep = nullptr);
 std::vector<SortPass> make_passes(int key_words, int lo_bit, int hi_bit);
 bool sort_takes_generated_first_pass(const mhx_ctx *c, uint64_t n, int stride, const std::vector<SortPass> &passes);
+// true when radix_sort(stride 4, these passes) will read a split array in its first pass (SortPrep::split_fill)
+bool sort_takes_split_first_pass(const mhx_ctx *c, const std::vector<SortPass> &passes);
+constexpr uint64_t kSortSplitUnit = 4096;  // records of a unit of that pass (256 threads x 8 x 2): what split_range_cap is a multiple of
 uint64_t passes_signature(const std::vector<SortPass> &ps);
 // kmsort_emu.hip: sort with the reference's exact (unstable) tie order, one GPU thread per lv1 bucket
 uint32_t *kmsort_exact(mhx_ctx *c, uint32_t *buf_a, uint32_t *buf_b, uint64_t n, int S, int key_words, SortPrep *prep = nullptr);

@@ -7,9 +7,14 @@
 // ONE 16-byte record (its bases, where it starts, how many windows it holds) instead of one 12-byte record per window.
 //   k_skm_make    one thread per aligned block of 8 windows: 17 canonical m-mer hashes from one 64-bit window of the store and its
 //                 reverse complement, the 8 window minima by a suffix / prefix scan, a record per run of equal bins (3.5 windows per
-//                 record at k = 21) -> the record array through one cursor (one atomic per workgroup and trip); the digit histograms of the
-//                 sort passes on the way; windows of ONE base (poly-A, poly-G) counted beside the records; COUNT: a base more either side
-//   radix_sort    two passes over the 16-bit bin (the chained-scan passes of sort.hip on 16-byte records; a third beyond 2^16 bins)
+//                 record at k = 21) -> the record array, SPLIT by the low digit of the bin: 256 ranges, a record goes into the range of its
+//                 digit (per workgroup and trip one reservation per digit, the records ordered by digit in an LDS stage before they
+//                 leave) — the group-by needs the records grouped by bin, in no order inside a bin, so the first sort pass need not be a
+//                 pass over an array this kernel has just written; the digit histograms of the sort passes on the way; windows of ONE
+//                 base (poly-A, poly-G) counted beside the records; COUNT: a base more either side.  (s1_skm_split = 0, a bin of one
+//                 digit, or a range that overflowed — skewed bins: the record array through one cursor, one atomic per workgroup and trip)
+//   radix_sort    ONE pass over the high digit of the 16-bit bin, reading the ranges in order (sort_kernels.h SrcSplit; stable, so its
+//                 output is ordered by the whole bin); a second beyond 2^16 bins; all digits when the records were not split
 //   k_skm_bounds  where each bin starts
 //   k_s1_skm      one workgroup per bin at a time: the windows of a wavefront's 64 records (~225) are dealt to the lanes 64 at a time (a bitmap
 //                 of run heads, six shuffles per window), canonical key (read_to_sdbg_s1.cpp:228-292: the strand of the (k-1)-mer, then
@@ -17,7 +22,7 @@
 //                 non-solid occurrences (:464, inverted: a key of count 1 < m has one record, whose position sits next to the key) and the
 //                 aggregated stage-2 items; several sources per bin (several GPUs: one per sending rank) and the marks as a list there
 //   k_count_skm   the same for `count`: in / out characters in the slot, packed edges out, the windows of flagged keys in a second expansion
-// 6.0 GB of records at 10 M reads instead of 16: the two sort passes and the read of the group-by move 2.7 x fewer bytes.
+// 6.0 GB of records at 10 M reads instead of 16: the sort and the read of the group-by move 2.7 x fewer bytes.
 // Shapes: no mercy, no lv1 bucket filter (the path cuts large jobs into passes over ranges of its OWN bins), reads of one length or of
 // several, min count <= 2, 19 <= k <= 22 (count: 21), positions below 2^36; everything else — and any input with a bin that outgrows what
 // one workgroup should stream (repeats other than homopolymers) — takes the prefix plan (s1_stream.hip).  DESIGN.md 4o.
@@ -54,12 +59,25 @@ __device__ __forceinline__ uint32_t skm_bin_of(uint32_t minh) {  // (the minimum
 // in front of it and the base behind it: the record carries one more base either side of its run (k + windows + 2 <= 31 bases at k <= 21),
 // two flags for a run that starts at the first / ends at the last window of its read ('$' there), and its length in the first word:
 // w0 = position bits 32.. << 28 | bin << 8 | (windows - 1) << 5 | no_prev << 4 | no_next << 3.
-template <int NT, int J, bool VAR, bool COUNT = false>
+// SPLIT: the record array is 256 ranges of range_cap slots, one per value of the bin's LOW digit, and a record goes into the range of its
+// digit, in any order — the first sort pass done where the records are made (the group-by wants the records grouped by bin, nothing more;
+// the next pass reads the ranges in order, sort_kernels.h SrcSplit, and is stable: its output is ordered by the whole bin).  Per trip of a
+// workgroup: the records counted per digit in LDS, ONE reservation per digit that has any on the 256 cursors split_cur[] (thread d for
+// digit d), the records placed into an LDS stage ordered by digit (one returning LDS atomic each), the stage copied out: the records of a
+// digit leave as one run.  A trip with more records than the stage holds (stage_n; uniform) writes them from the registers to the places
+// reserved.  A reservation beyond its range writes nothing and raises bit 1 of *err: the host makes the records again without the split.
+constexpr int kSkmStage = 2560;  // records the stage holds: a trip of 512 x 2 blocks makes 2330 of random sequence (0.284 per window)
+template <int NT, int J, bool VAR, bool COUNT = false, bool SPLIT = false>
 __global__ __launch_bounds__(NT) void k_skm_make(const uint32_t *__restrict__ seq, const uint64_t *__restrict__ start, uint32_t L, uint32_t bpr, uint64_t n_blocks,
                                                  int k, int bin_bits, uint32_t bin_lo, uint32_t bin_hi, int count_items, uint64_t pos_base,
                                                  unsigned long long *__restrict__ hp, uint4 *__restrict__ out, unsigned long long cap,
-                                                 unsigned long long *__restrict__ cursor, uint32_t *__restrict__ err, unsigned long long *__restrict__ digit_hist) {
+                                                 unsigned long long *__restrict__ cursor, uint32_t *__restrict__ err, unsigned long long *__restrict__ digit_hist,
+                                                 unsigned long long range_cap, unsigned long long *__restrict__ split_cur, uint32_t stage_n) {
+  constexpr long long kNoRoom = -0x7FFFFFFFFFFFFFFFll - 1;
   __shared__ uint32_t sm_scan[NT / kWave + 1];
+  __shared__ uint4 stage[SPLIT ? kSkmStage : 1];
+  __shared__ uint32_t dcnt[SPLIT ? 256 : 1], dpos[SPLIT ? 256 : 1];  // per low digit: the trip's records, where the next one goes in the stage
+  __shared__ long long goff[SPLIT ? 256 : 1];                        // ... its place in the array minus its place in the stage (kNoRoom: dropped)
   __shared__ unsigned long long s_base;
   __shared__ uint32_t dh[3][256];  // the digit histograms of the sort passes, taken while the records are made
   __shared__ uint32_t lbin[J * kSkmC][NT];  // a thread's bins, read back by window number when its records leave (no register array indexed by a variable)
@@ -67,6 +85,7 @@ __global__ __launch_bounds__(NT) void k_skm_make(const uint32_t *__restrict__ se
   const int tid = threadIdx.x;
   if (tid < 24) hpl[tid / 12][tid % 12] = 0;
   for (int i = tid; i < 768; i += NT) dh[i >> 8][i & 255] = 0;
+  if (SPLIT && tid < 256) dcnt[tid] = 0;
   __syncthreads();
   const bool third_digit = bin_bits > 16;
   const int M = k + 1 - (kSkmW - 1);
@@ -185,6 +204,88 @@ __global__ __launch_bounds__(NT) void k_skm_make(const uint32_t *__restrict__ se
         }
       }
     }
+    // the record of the run of windows rs .. re of block j; the runs of this thread, in order
+    auto rec_of = [&](int j, int rs, int re, uint32_t run_bin) -> uint4 {
+      const int len = re - rs + 1;
+      const uint64_t p = pos0[j] + (uint64_t)rs;
+      if constexpr (COUNT) {
+        const uint64_t bases = (Wv[j] << (2 * rs)) & (~0ull << (64 - 2 * (K1 + len + 1)));
+        const uint32_t n_blk = bflag[j] >> 2;
+        const uint32_t fl = ((bflag[j] & 1u) && rs == 0 ? 16u : 0u) | ((bflag[j] & 2u) && (uint32_t)(re + 1) == n_blk ? 8u : 0u);
+        return make_uint4((run_bin << 8) | ((uint32_t)(p >> 32) << 28) | ((uint32_t)(len - 1) << 5) | fl, (uint32_t)(bases >> 32), (uint32_t)bases, (uint32_t)p);
+      } else {
+        const uint64_t bases = ((Wv[j] << (2 * rs)) & (~0ull << (64 - 2 * (K1 + len - 1)))) | (uint64_t)(len - 1);
+        return make_uint4((run_bin << 8) | ((uint32_t)(p >> 32) << 28), (uint32_t)(bases >> 32), (uint32_t)bases, (uint32_t)p);
+      }
+    };
+    auto walk = [&](auto &&fn) {
+#pragma unroll
+      for (int j = 0; j < J; ++j) {
+        uint32_t sm = smask[j], em = emask[j];
+        while (sm) {  // (runs are disjoint and in order: the i-th start goes with the i-th end)
+          const int rs = __builtin_ctz(sm), re = __builtin_ctz(em);
+          sm &= sm - 1;
+          em &= em - 1;
+          fn(j, rs, re, lbin[j * kSkmC + rs][tid]);
+        }
+      }
+    };
+    if constexpr (SPLIT) {
+      walk([&](int, int, int, uint32_t run_bin) {
+        atomicAdd(&dcnt[run_bin & 255u], 1u);
+        atomicAdd(&dh[1][(run_bin >> 8) & 255u], 1u);
+        if (third_digit) atomicAdd(&dh[2][run_bin >> 16], 1u);
+      });
+      __syncthreads();
+      // where each digit starts in the stage: a scan over the 256 counts by the first four wavefronts (one barrier; sm_scan is written
+      // again behind the next trip's first barrier)
+      const uint32_t c = tid < 256 ? dcnt[tid] : 0u;
+      const uint32_t inc = wave_inclusive_sum(c);
+      if (tid < 256 && (tid & (kWave - 1)) == kWave - 1) sm_scan[tid / kWave] = inc;
+      __syncthreads();
+      uint32_t total = 0, start = inc - c;
+#pragma unroll
+      for (int i = 0; i < 256 / kWave; ++i) {
+        const uint32_t t = sm_scan[i];
+        if (i < tid / kWave) start += t;
+        total += t;
+      }
+      if (tid < 256) {
+        long long off = kNoRoom;
+        if (c) {
+          const unsigned long long gb = atomicAdd(&split_cur[tid], (unsigned long long)c);
+          if (gb + c <= range_cap) off = (long long)((unsigned long long)tid * range_cap + gb) - (long long)start;
+          else atomicOr(err, 2u);  // (the kernel runs on to its end: the barriers below are met by all, and nothing is stored for this digit)
+          dh[0][tid] += c;
+        }
+        goff[tid] = off;
+        dpos[tid] = start;
+        dcnt[tid] = 0;
+      }
+      __syncthreads();
+      const bool direct = total > stage_n;  // (uniform)
+      walk([&](int j, int rs, int re, uint32_t run_bin) {
+        const uint32_t d = run_bin & 255u;
+        const uint32_t pos = atomicAdd(&dpos[d], 1u);
+        const uint4 rec = rec_of(j, rs, re, run_bin);
+        if (direct) {
+          const long long off = goff[d];
+          if (off != kNoRoom) out[off + (long long)pos] = rec;
+        } else {
+          stage[pos] = rec;
+        }
+      });
+      if (!direct) {
+        __syncthreads();
+        for (uint32_t i = tid; i < total; i += NT) {
+          const uint4 rec = stage[i];
+          const long long off = goff[(rec.x >> 8) & 255u];
+          if (off != kNoRoom) out[off + (long long)i] = rec;
+        }
+      }
+      // (no barrier here: the next trip counts into dcnt, which thread d cleared before the barrier above, and writes goff, dpos and the
+      //  stage behind its own barriers — by then every thread has left this copy)
+    } else {
     uint32_t cnt = 0;
 #pragma unroll
     for (int j = 0; j < J; ++j) cnt += (uint32_t)__builtin_popcount(smask[j]);
@@ -198,29 +299,12 @@ __global__ __launch_bounds__(NT) void k_skm_make(const uint32_t *__restrict__ se
       return;
     }
     unsigned long long at = base + excl;
-#pragma unroll
-    for (int j = 0; j < J; ++j) {
-      uint32_t sm = smask[j], em = emask[j];
-      while (sm) {  // (runs are disjoint and in order: the i-th start goes with the i-th end)
-        const int rs = __builtin_ctz(sm), re = __builtin_ctz(em);
-        sm &= sm - 1;
-        em &= em - 1;
-        const int len = re - rs + 1;
-        const uint32_t run_bin = lbin[j * kSkmC + rs][tid];
-        const uint64_t p = pos0[j] + (uint64_t)rs;
-        if constexpr (COUNT) {
-          const uint64_t bases = (Wv[j] << (2 * rs)) & (~0ull << (64 - 2 * (K1 + len + 1)));
-          const uint32_t n_blk = bflag[j] >> 2;
-          const uint32_t fl = ((bflag[j] & 1u) && rs == 0 ? 16u : 0u) | ((bflag[j] & 2u) && (uint32_t)(re + 1) == n_blk ? 8u : 0u);
-          out[at++] = make_uint4((run_bin << 8) | ((uint32_t)(p >> 32) << 28) | ((uint32_t)(len - 1) << 5) | fl, (uint32_t)(bases >> 32), (uint32_t)bases, (uint32_t)p);
-        } else {
-        const uint64_t bases = ((Wv[j] << (2 * rs)) & (~0ull << (64 - 2 * (K1 + len - 1)))) | (uint64_t)(len - 1);
-        out[at++] = make_uint4((run_bin << 8) | ((uint32_t)(p >> 32) << 28), (uint32_t)(bases >> 32), (uint32_t)bases, (uint32_t)p);
-        }
-        atomicAdd(&dh[0][run_bin & 255u], 1u);
-        atomicAdd(&dh[1][(run_bin >> 8) & 255u], 1u);
-        if (third_digit) atomicAdd(&dh[2][run_bin >> 16], 1u);
-      }
+    walk([&](int j, int rs, int re, uint32_t run_bin) {
+      out[at++] = rec_of(j, rs, re, run_bin);
+      atomicAdd(&dh[0][run_bin & 255u], 1u);
+      atomicAdd(&dh[1][(run_bin >> 8) & 255u], 1u);
+      if (third_digit) atomicAdd(&dh[2][run_bin >> 16], 1u);
+    });
     }
   }
   if constexpr (VAR) {
@@ -1258,17 +1342,24 @@ bool s1_skm_front(mhx_ctx *c, uint32_t k, SkmFront *f, int pass, int n_passes, i
   while (bin_bits < kSkmMaxBinBits && (double)n_win * 0.29 / (double)(1ull << bin_bits) > 8192.0) ++bin_bits;
   if (const long long fb = c->opt("s1_skm_bin_bits", 0)) bin_bits = (int)std::min<long long>(kSkmMaxBinBits, std::max<long long>(8, fb));
   if (bin_bits_agreed > 0) bin_bits = bin_bits_agreed;  // (several GPUs: the ranks made it from the size of the whole job)
-  uint4 *buf_a = c->ws("items_a", cap * 16 + 64).as<uint4>();
-  uint4 *buf_b = c->ws("items_b", cap * 16 + 64).as<uint4>();
-  unsigned long long *cursor = c->ws("skm_cursor", 64).as<unsigned long long>();
-  uint32_t *err = reinterpret_cast<uint32_t *>(cursor + 1);
-  uint32_t *max_bin = err + 1;
-  MHX_HIP(hipMemsetAsync(cursor, 0, 64, st));
   // (bits 0..7 of the first word are zero in every record: all passes may rank with LDS atomics)
   std::vector<SortPass> passes;
   for (int lo = 0; lo < bin_bits; lo += 8) passes.push_back(SortPass{8 + lo, std::min(8, bin_bits - lo), 0, 0, 0});
+  // s1_skm_split: k_skm_make puts every record into the range of its bin's low digit — the first sort pass done where the records are made —
+  // and the sort starts at the second digit, reading the ranges in order.  Needs a second pass (the group-by cannot read an array with holes);
+  // a range that overflows (a skewed input: the ranges hold the even share of hash-uniform bins and the array's slack) makes the records again, unsplit
+  const std::vector<SortPass> passes_rest(passes.begin() + (passes.empty() ? 0 : 1), passes.end());
+  bool split = c->opt("s1_skm_split", 1) != 0 && passes.size() >= 2 && sort_takes_split_first_pass(c, passes_rest);
+  const uint64_t cap_split = std::max<uint64_t>(cap, 1u << 20), range_cap = cap_split / 256 / kSortSplitUnit * kSortSplitUnit;
+  const uint64_t cap_alloc = split ? cap_split : cap;
+  uint4 *buf_a = c->ws("items_a", cap_alloc * 16 + 64).as<uint4>();
+  uint4 *buf_b = c->ws("items_b", cap_alloc * 16 + 64).as<uint4>();
+  unsigned long long *cursor = c->ws("skm_cursor", 64).as<unsigned long long>();
+  uint32_t *err = reinterpret_cast<uint32_t *>(cursor + 1);
+  uint32_t *max_bin = err + 1;
+  unsigned long long *split_cur = split ? c->ws("skm_split_cursors", (256 + 257) * 8).as<unsigned long long>() : nullptr;
+  const uint32_t stage_n = (uint32_t)std::min<long long>(std::max<long long>(c->opt("s1_skm_split_stage", kSkmStage), 0), kSkmStage);
   unsigned long long *pre_hist = c->ws("sort_pre_hist", (size_t)kMaxFusedPasses * 256 * 8).as<unsigned long long>();
-  MHX_HIP(hipMemsetAsync(pre_hist, 0, (size_t)3 * 256 * 8, st));
   constexpr int NT = 512, J = 2;
   const uint64_t cus = c->n_cus > 0 ? (uint64_t)c->n_cus : 256;
   const unsigned grid = (unsigned)std::min<uint64_t>(div_ceil(n_blocks, (uint64_t)NT * J), cus * 8);
@@ -1276,30 +1367,49 @@ bool s1_skm_front(mhx_ctx *c, uint32_t k, SkmFront *f, int pass, int n_passes, i
   const uint32_t bin_lo = (uint32_t)((uint64_t)n_bins * pass / n_passes), bin_hi = (uint32_t)((uint64_t)n_bins * (pass + 1) / n_passes);
   // homopolymer windows are counted beside the records on one GPU (several GPUs: they stay in the records; a job with many gives the path up)
   unsigned long long *hp = nullptr;
-  if (!c->global_bases && c->opt("s1_skm_hp", 1)) {
-    hp = c->ws("skm_hp", 512).as<unsigned long long>();  // [0..3] stage 1: windows per class, a position each; [8 + 16 class + ..] count: windows, bases in front, bases behind
-    if (pass == 0) {
-      unsigned long long init[48] = {0};
-      init[2] = init[3] = ~0ull;
-      MHX_HIP(hipMemcpyAsync(hp, init, sizeof init, hipMemcpyHostToDevice, st));
-      MHX_HIP(hipStreamSynchronize(st));  // (init is a stack variable)
-    }
-  }
-#define MHX_MAKE(VARV, COUNTV)                                                                                                                                   \
-  hipLaunchKernelGGL((k_skm_make<NT, J, VARV, COUNTV>), dim3(grid), dim3(NT), 0, st, s.words.as<uint32_t>(), s.start.as<uint64_t>(), L, bpr, n_blocks, (int)k, \
-                     bin_bits, bin_lo, bin_hi, pass == 0 ? 1 : 0, c->pos_base, hp, buf_a, (unsigned long long)cap, cursor, err, pre_hist)
-  MHX_LAUNCH(c, for_count ? "count_skm_make" : "s1_skm_make", (double)s.n_bases / 4 + (double)n_win * 16 / 3.5, {
-    if (var && for_count) MHX_MAKE(true, true);
-    else if (var) MHX_MAKE(true, false);
-    else if (for_count) MHX_MAKE(false, true);
-    else MHX_MAKE(false, false);
-  });
-#undef MHX_MAKE
+  if (!c->global_bases && c->opt("s1_skm_hp", 1)) hp = c->ws("skm_hp", 512).as<unsigned long long>();  // [0..3] stage 1: windows per class, a position each; [8 + 16 class + ..] count: windows, bases in front, bases behind
+  unsigned long long hp_init[48] = {0};
+  hp_init[2] = hp_init[3] = ~0ull;
   unsigned long long h[4] = {0, 0, 0, 0};
-  std::vector<unsigned long long> h_dh(passes.size() * 256);
-  MHX_HIP(hipMemcpyAsync(h, cursor, 32, hipMemcpyDeviceToHost, st));
-  MHX_HIP(hipMemcpyAsync(h_dh.data(), pre_hist, h_dh.size() * 8, hipMemcpyDeviceToHost, st));
-  MHX_HIP(hipStreamSynchronize(st));
+  std::vector<unsigned long long> h_dh(passes.size() * 256), h_fill(256);
+#define MHX_MAKE(VARV, COUNTV, SPLITV)                                                                                                                                   \
+  hipLaunchKernelGGL((k_skm_make<NT, J, VARV, COUNTV, SPLITV>), dim3(grid), dim3(NT), 0, st, s.words.as<uint32_t>(), s.start.as<uint64_t>(), L, bpr, n_blocks, (int)k, \
+                     bin_bits, bin_lo, bin_hi, pass == 0 ? 1 : 0, c->pos_base, hp, buf_a, (unsigned long long)cap, cursor, err, pre_hist,                            \
+                     (unsigned long long)range_cap, split_cur, stage_n)
+  // everything the kernel counts starts from zero — also when the records are made a second time
+  auto make = [&](bool split_now) {
+    MHX_HIP(hipMemsetAsync(cursor, 0, 64, st));
+    MHX_HIP(hipMemsetAsync(pre_hist, 0, (size_t)3 * 256 * 8, st));
+    if (split_now) MHX_HIP(hipMemsetAsync(split_cur, 0, 256 * 8, st));
+    if (hp && pass == 0) MHX_HIP(hipMemcpyAsync(hp, hp_init, sizeof hp_init, hipMemcpyHostToDevice, st));
+    MHX_LAUNCH(c, for_count ? "count_skm_make" : "s1_skm_make", (double)s.n_bases / 4 + (double)n_win * 16 / 3.5, {
+      if (split_now) {
+        if (var && for_count) MHX_MAKE(true, true, true);
+        else if (var) MHX_MAKE(true, false, true);
+        else if (for_count) MHX_MAKE(false, true, true);
+        else MHX_MAKE(false, false, true);
+      } else {
+        if (var && for_count) MHX_MAKE(true, true, false);
+        else if (var) MHX_MAKE(true, false, false);
+        else if (for_count) MHX_MAKE(false, true, false);
+        else MHX_MAKE(false, false, false);
+      }
+    });
+    MHX_HIP(hipMemcpyAsync(h, cursor, 32, hipMemcpyDeviceToHost, st));
+    MHX_HIP(hipMemcpyAsync(h_dh.data(), pre_hist, h_dh.size() * 8, hipMemcpyDeviceToHost, st));
+    if (split_now) MHX_HIP(hipMemcpyAsync(h_fill.data(), split_cur, 256 * 8, hipMemcpyDeviceToHost, st));
+    MHX_HIP(hipStreamSynchronize(st));
+  };
+  make(split);
+  if (split && ((uint32_t)h[1] & 2u)) {  // a range overflowed: the records again through the one cursor, and all passes
+    split = false;
+    make(false);
+  }
+#undef MHX_MAKE
+  if (split) {  // (no cursor of all records: they are what the ranges hold)
+    h[0] = 0;
+    for (int d = 0; d < 256; ++d) h[0] += h_fill[d];
+  }
   f->n_records = 0;
   f->hp = hp;
   if ((uint32_t)h[1] != 0 || h[0] > cap) return false;
@@ -1325,12 +1435,24 @@ bool s1_skm_front(mhx_ctx *c, uint32_t k, SkmFront *f, int pass, int n_passes, i
       return false;
     }
   }
+  const std::vector<SortPass> &sort_passes = split ? passes_rest : passes;
   SortPrep prep;  // (radix_sort: no histogram read of its own)
   prep.buf = buf_a;
   prep.n = n;
-  prep.hist_passes = (int)passes.size();
-  prep.hist_sig = passes_signature(passes);
-  uint32_t *sorted = radix_sort(c, reinterpret_cast<uint32_t *>(buf_a), reinterpret_cast<uint32_t *>(buf_b), n, 4, 1, passes, &prep);
+  prep.hist_passes = (int)sort_passes.size();
+  prep.hist_sig = passes_signature(sort_passes);
+  std::vector<unsigned long long> h_ubase(257, 0);  // (alive until the sort has run: the copy is asynchronous)
+  if (split) {  // the units of the pass: every range rounded up to whole units, the room behind a range's records is not visited
+    for (int d = 0; d < 256; ++d) h_ubase[d + 1] = h_ubase[d] + div_ceil((uint64_t)h_fill[d], kSortSplitUnit);
+    unsigned long long *ubase = split_cur + 256;
+    MHX_HIP(hipMemcpyAsync(ubase, h_ubase.data(), 257 * 8, hipMemcpyHostToDevice, st));
+    prep.split_fill = split_cur;
+    prep.split_ubase = ubase;
+    prep.split_units = h_ubase[256];
+    prep.split_range_cap = range_cap;
+    prep.hist_first = 1;
+  }
+  uint32_t *sorted = radix_sort(c, reinterpret_cast<uint32_t *>(buf_a), reinterpret_cast<uint32_t *>(buf_b), n, 4, 1, sort_passes, &prep);
   uint64_t *bounds = c->ws("s1_bucket_bounds", ((size_t)n_bins + 1) * 8 + 64).as<uint64_t>();
   MHX_LAUNCH(c, "s1_skm_bounds", (double)n_bins * 8 * 30,
              hipLaunchKernelGGL(k_skm_bounds, dim3((n_bins + 1 + 255) / 256), dim3(256), 0, st, reinterpret_cast<const uint4 *>(sorted), n, n_bins, bounds, max_bin));
@@ -1341,7 +1463,7 @@ bool s1_skm_front(mhx_ctx *c, uint32_t k, SkmFront *f, int pass, int n_passes, i
   f->src[0] = reinterpret_cast<const uint4 *>(sorted);
   f->src_bounds[0] = bounds;
   f->spare = sorted == reinterpret_cast<uint32_t *>(buf_a) ? reinterpret_cast<uint32_t *>(buf_b) : reinterpret_cast<uint32_t *>(buf_a);
-  f->spare_bytes = cap * 16;
+  f->spare_bytes = cap_alloc * 16;  // (the whole buffer: the workgroups' output regions are cut from it, and a small job's are thin)
   f->n_records = n;
   f->n_windows = n_win;
   if (pass == 0) f->n_items = var ? h[3] : s.n_seqs * (uint64_t)(L - k + (for_count ? 0 : 4));

@@ -283,6 +283,7 @@ static SortEnv sort_env() {
 // a generated first pass that this call does not run would leave the buffer without records: never sort that
 static void refuse_unconsumed_generator(const SortPrep &prep, const char *who) {
   if (prep.gen) throw Error(std::string(who) + ": the records of this buffer are to be made by a generated first pass, which this sort path cannot run");
+  if (prep.split_fill) throw Error(std::string(who) + ": the records of this buffer lie in ranges split by an earlier digit, which this sort path cannot read");
 }
 
 // chained-scan sort (8/12/16-byte records, <= 8 passes); MHX_SORT=classic selects the histogram + scan + scatter passes
@@ -293,9 +294,14 @@ static uint32_t *radix_sort_onesweep(mhx_ctx *c, uint32_t *a, uint32_t *b, uint6
   const bool prep_fits = prep.buf == (const void *)a && prep.n == n;
   // a generated first pass (s1.hip): valid for exactly this buffer, item count and unit shape
   const bool gen = prep.gen && prep_fits && S == 3 && NI == 8 && UT == 3;
-  if (!gen) refuse_unconsumed_generator(prep, "radix sort (chained scan)");
-  // (item slots the generator walks — more than n when it drops the items of filtered-out lv1 buckets)
-  const uint64_t gen_slots = gen ? std::max<uint64_t>(prep.gen_slots, n) : n;
+  // ... or loaded from an array split by an earlier digit (s1_skm.hip): 16-byte records, this unit shape, unit-wide runs
+  constexpr bool kCanSplit = S == 4 && NI == 8 && UT == 2;
+  static_assert(!kCanSplit || (uint64_t)kSortThreads * NI * UT == kSortSplitUnit, "a unit of the split pass");
+  const bool split = kCanSplit && !prep.gen && prep.split_fill && prep.split_ubase && prep_fits && c->opt("sort_unit_runs", 1) != 0 &&
+                     prep.split_range_cap > 0 && prep.split_range_cap % kSortSplitUnit == 0;
+  if (!gen && !split) refuse_unconsumed_generator(prep, "radix sort (chained scan)");
+  // (item slots the first pass walks — more than n when the generator drops the items of filtered-out lv1 buckets, or the last unit of a range is not full)
+  const uint64_t gen_slots = gen ? std::max<uint64_t>(prep.gen_slots, n) : (split ? prep.split_units * kSortSplitUnit : n);
   // Per-XCD tickets (see k_radix_onesweep): a unit may wait for a unit whose block id is up to 127 higher, so the scheme needs
   // the whole 8-XCD part with a couple of hundred workgroups resident at once (MI355X in SPX mode: 256 CUs x 3-4 workgroups).
   // On a partition (CPX: 32 CUs, one XCD) or an unknown device the single ticket counter is used: its look-back only ever
@@ -330,7 +336,10 @@ static uint32_t *radix_sort_onesweep(mhx_ctx *c, uint32_t *a, uint32_t *b, uint6
   // extraction may have taken the digit histograms while it produced the records (s1.hip): then no read at all
   const bool pre = prep_fits && prep.hist_passes == P && P > 0 && P <= kMaxFusedPasses && prep.hist_sig == passes_signature(passes);
   if (gen && !pre) throw Error("radix sort: a generated first pass needs the digit histograms of the plan (pre-hist)");
-  if (pre) MHX_HIP(hipMemcpyAsync(gh, c->work["sort_pre_hist"].p, (size_t)P * 256 * 8, hipMemcpyDeviceToDevice, st));
+  if (split && !pre) throw Error("radix sort: a split first pass needs the digit histograms of the plan (pre-hist)");
+  if (pre)
+    MHX_HIP(hipMemcpyAsync(gh, static_cast<const unsigned long long *>(c->work["sort_pre_hist"].p) + (size_t)prep.hist_first * 256, (size_t)P * 256 * 8,
+                           hipMemcpyDeviceToDevice, st));
   for (int p0 = 0; p0 < P && !pre; p0 += kMaxFusedPasses) {  // one read of the input per 16 passes
     DigitSpecs specs;
     specs.n = std::min(kMaxFusedPasses, P - p0);
@@ -354,6 +363,19 @@ static uint32_t *radix_sort_onesweep(mhx_ctx *c, uint32_t *a, uint32_t *b, uint6
       MHX_LAUNCH(c, nm_gen.c_str(), bytes,
                  prep.gen(OnesweepLaunch{(unsigned)n_units_gen, st, b, gen_slots, all[p], nb, starts + p * 256, status, tickets + p * 8,
                                     tickets + kErrSlot, (unsigned long long)(p + 1), xcd_units, unit_runs ? 1 : 0, wi}));
+    } else if (p == 0 && split) {
+      if constexpr (kCanSplit) {
+#define MHX_US(RANKV, WIV)                                                                                                                        \
+  hipLaunchKernelGGL((k_radix_onesweep_u<S, NI, UT, SrcSplit<S>, RANKV, WIV>), dim3((unsigned)n_units_gen), dim3(kSortThreads), 0, st,            \
+                     SrcSplit<S>{a, prep.split_fill, prep.split_ubase, prep.split_range_cap}, b, gen_slots, all[p], nb, starts + p * 256, status, tickets + p * 8, \
+                     tickets + kErrSlot, (unsigned long long)(p + 1), xcd_units)
+        MHX_LAUNCH(c, nm_scat.c_str(), 2 * bytes, {
+          if (wi == 0 && rank_uniform && all[p].prev_mask) MHX_US(2, 0);
+          else if (wi == 0) MHX_US(0, 0);
+          else MHX_US(0, -1);
+        });
+#undef MHX_US
+      }
     } else if (unit_runs) {
       if constexpr (kHasUnitRuns) {
 #define MHX_U(RANKV, WIV)                                                                                                                      \
@@ -684,6 +706,13 @@ bool sort_takes_generated_first_pass(const mhx_ctx *c, uint64_t n, int stride, c
   if ((!env.shape.empty() && env.shape != "8x3") || (env.items && env.items != default_items<3>())) return false;
   return stride == 3 && n > 0 && passes.size() <= (size_t)kMaxChainedPasses && passes.size() <= (size_t)kMaxFusedPasses &&
          div_ceil(n, (uint64_t)kSortThreads * 8) < (1ull << 31);
+}
+
+bool sort_takes_split_first_pass(const mhx_ctx *c, const std::vector<SortPass> &passes) {
+  const SortEnv env = sort_env();  // (the same per-call decision radix_sort_impl2 takes for 16-byte records)
+  if (env.classic || c->opt("sort_unit_runs", 1) == 0) return false;
+  if ((!env.shape.empty() && env.shape != "8x2") || (env.items && env.items != default_items<4>())) return false;
+  return !passes.empty() && passes.size() <= (size_t)kMaxChainedPasses && passes.size() <= (size_t)kMaxFusedPasses;
 }
 
 uint32_t *radix_sort(mhx_ctx *c, uint32_t *a, uint32_t *b, uint64_t n, int stride, int key_words,

@@ -115,6 +115,57 @@ struct SrcArray {
   }
 };
 // ... or a generator (s1.hip: S1Gen makes the stage-1 records straight from the packed reads in the first pass)
+// ... or an array SPLIT by an earlier digit where its records were made (s1_skm.hip k_skm_make<.., SPLIT>): 256 ranges of range_cap item
+// slots each, range d filled from its start with the fill[d] records whose earlier digit is d, in any order.  The pass walks the ranges
+// in order — stable over them, so its output is ordered by (this digit, the earlier digit) — in units that never straddle two ranges:
+// range d takes the units [ubase[d], ubase[d + 1]) = ceil(fill[d] / unit) of them, so the room a range has left costs no unit (the array
+// carries a quarter of slack).  The item slots of a range's last unit behind its fill are declined (Src::kMayDrop): no load is issued
+// for them, and their first word gets bits that no record carries (bits 0..2 of a super-k-mer record's first word are zero, with or
+// without the flags of `count`).
+template <int S>
+struct SrcSplit {
+  const uint32_t *in;
+  const unsigned long long *fill;   // [256] records in each range
+  const unsigned long long *ubase;  // [257] units in front of each range; [256] = all units that hold records
+  uint64_t range_cap;
+  static constexpr bool kMayDrop = true;
+  __device__ __forceinline__ bool is_record(const Rec<S> &r) const { return (r.w[0] & 7u) == 0u; }
+  template <int NI>
+  __device__ __forceinline__ uint64_t index(uint64_t tile_base, int w, int lane, int j) const {
+    return tile_base + (uint64_t)(w * (kWave * NI) + j * kWave + lane);
+  }
+  template <int NI, int UT>
+  __device__ __forceinline__ void get_unit(uint64_t unit_base, int w, int lane, uint64_t n, Rec<S> (&rec)[UT][NI]) const {
+    constexpr uint64_t kUnit = (uint64_t)kSortThreads * NI * UT;
+    const uint64_t u = unit_base / kUnit;
+    // the range of this unit: every wavefront looks at all 256 ranges at once (lane l at l, l + 64, ..), one round trip
+    uint64_t first = 0, end = 0;  // where the unit's first slot lies in the array, and where its range's records end
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      const int d = q * kWave + lane;
+      const uint64_t lo = ubase[d], hi = ubase[d + 1];
+      const uint64_t m = __ballot(lo <= u && u < hi);
+      if (m) {  // (uniform; at most one range holds the unit)
+        const int src = __builtin_ctzll(m);
+        const uint64_t dd = (uint64_t)(q * kWave + src);
+        const uint64_t lo_d = (uint64_t)__shfl((long long)lo, src, kWave);
+        uint64_t filled = fill[dd];
+        if (filled > range_cap) filled = range_cap;
+        first = dd * range_cap + (u - lo_d) * kUnit;
+        end = dd * range_cap + filled;
+      }
+    }
+#pragma unroll
+    for (int t = 0; t < UT; ++t)
+#pragma unroll
+      for (int j = 0; j < NI; ++j) {
+        const uint64_t gi = first + (uint64_t)t * (kSortThreads * NI) + (uint64_t)(w * (kWave * NI) + j * kWave + lane);
+#pragma unroll
+        for (int i = 0; i < S; ++i) rec[t][j].w[i] = 0xFFFFFFFFu;
+        if (gi < end) load_rec<S>(in + gi * S, rec[t][j]);
+      }
+  }
+};
 
 constexpr unsigned long long kStValMask = (1ull << 56) - 1;
 

@@ -46,6 +46,10 @@ def main():
             opts["s1_skm_deal"] = 0
         if rng.random() < 0.15:
             opts["s1_skm_max_bin"] = int(rng.choice([8, 500]))
+        if rng.random() < 0.3:
+            opts["s1_skm_split"] = 0
+        if rng.random() < 0.3:
+            opts["s1_skm_split_stage"] = int(rng.choice([0, 64, 700]))
 
         def load(r, e):
             pkg = ob.Package(shards[r], reverse=True)
