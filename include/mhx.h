@@ -45,7 +45,8 @@ int mhx_device_count(void);
  * gfx950 code object is usable — there is no CPU fallback. */
 mhx_ctx *mhx_create(int device);
 void mhx_destroy(mhx_ctx *);
-/* release cached device workspaces (they are otherwise kept between calls) */
+/* release cached device workspaces (they are otherwise kept between calls).  A bucket filter is switched off with its tables; the
+   aggregated stage-2 items of the last stage 1 stay: the next stage 2 reads them. */
 int mhx_trim(mhx_ctx *);
 /* forget inputs, results, partition, filters and options, keep the device buffers: the next job starts as on a new
    handle without re-allocating (what `mhx_core --serve` does between two sub-programs) */
@@ -580,6 +581,11 @@ int mhx_comm_size(const mhx_comm *);
 int mhx_comm_barrier(mhx_comm *);
 /* payload bytes this rank has handed to OTHER ranks through the item / record exchanges since the last reset (what crosses xGMI) */
 uint64_t mhx_comm_bytes_sent(mhx_comm *, int reset);
+/* Device memory of the planned stages of this rank's mhx_dist_* calls so far, in call order; returns their number and, for
+   0 <= i < that number, fills record i: the stage (enum mhx_stage), the bytes libmhx held in this process when the stage's plan
+   was made, their peak until its last pass was done (mhx_alloc_peak: process-wide, so ranks that are threads of one process
+   count together) and the free bytes the plan was made with.  clear != 0 forgets the records after reading.  Any pointer may be NULL. */
+int mhx_dist_plan_memory(mhx_comm *, int i, int *stage, uint64_t *held_at_plan, uint64_t *peak, uint64_t *budget, int clear);
 int mhx_comm_all_reduce_u64(mhx_comm *, uint64_t *values, uint64_t n, int is_max /* else sum */);
 /* agree on the bucket partition (balance_stage = 0: equal ranges; else an enum mhx_stage whose all-reduced lv1 bucket
  * histogram balances the ranges) and on the global read layout (rank r's bases at r * stride); sets dist_sparse_marks */
@@ -613,8 +619,16 @@ uint64_t mhx_device_free_bytes(mhx_ctx *);  /* free HBM on the handle's device r
 int mhx_bucket_histogram(mhx_ctx *, int stage /* enum mhx_stage */, uint32_t k, uint32_t min_count, uint64_t *hist /* 65536 */);
 /* Device bytes a bucket-range pass of `stage` over n_items kept items needs for its items (sort buffers, staging, status
  * words), the stage's fixed state aside — for the sequences loaded now (stage 1 on fixed-length reads makes its records in
- * the first sort pass and needs two 12-byte buffers; the general path three item buffers).  0 on error. */
+ * the first sort pass and needs two 12-byte buffers; the general path three item buffers).  The lean routes count what they
+ * hold besides: status words over all item slots, the giant buckets' tables, and the outputs of the kept buckets at their bound
+ * (aggregated stage-2 items, solid edges); the answer for n_items = 0 is the part that does not grow with the items.  The
+ * allocator's headroom (a 16th) is the caller's to add.  0 on error. */
 uint64_t mhx_stage_pass_bytes(mhx_ctx *, int stage, uint32_t k, uint32_t min_count, uint64_t n_items);
+/* Device bytes `stage` holds besides its fixed state when it runs ONCE over everything, no filter set, where that run has a leaner
+ * route than a bucket-range pass (stage 2 from a count of the (k+1)-mers: the route is switched off under a filter, so this figure
+ * decides only whether one run fits; the ranges of several passes are sized with mhx_stage_pass_bytes).  n_items: the caller's
+ * estimate of the stage's per-occurrence items.  0: no such route, ask mhx_stage_pass_bytes. */
+uint64_t mhx_stage_once_bytes(mhx_ctx *, int stage, uint32_t k, uint32_t min_count, uint64_t n_items);
 int mhx_set_bucket_filter(mhx_ctx *, const uint8_t *keep, uint64_t expected_items, uint64_t batch_bytes, int accumulate);
 
 /* ---- measurement ---- */
@@ -627,6 +641,10 @@ typedef struct {
 /* host seconds this process spent in hipMalloc / hipFree for libmhx's device buffers, bytes and calls of hipMalloc
    (process-wide; any pointer may be NULL).  A process started right behind another GPU process waits there. */
 void mhx_alloc_stats(double *malloc_s, double *free_s, uint64_t *bytes, uint64_t *calls);
+/* device bytes libmhx's buffers of this process hold right now and their high-water mark (process-wide, every handle and
+   rank thread together; any pointer may be NULL).  reset_peak != 0 sets the mark to the bytes held now, after reading it:
+   what a memory plan is held to (mhx_core's "Device memory of <stage>" lines). */
+void mhx_alloc_peak(uint64_t *held_now, uint64_t *peak, int reset_peak);
 int mhx_profile_enable(mhx_ctx *, int on);
 int mhx_profile_reset(mhx_ctx *);
 /* returns number of distinct kernels; fills up to cap entries */

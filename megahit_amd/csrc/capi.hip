@@ -26,6 +26,14 @@ void set_error(const char *fmt, ...) {
 // host time spent inside hipMalloc / hipFree by this process (mhx_alloc_stats): a process that starts while the driver
 // still reclaims the device memory of its predecessor waits HERE, not in its kernels
 static std::atomic<uint64_t> g_alloc_ns{0}, g_alloc_bytes{0}, g_alloc_calls{0}, g_free_ns{0};
+// device bytes this process holds now and their high-water mark (mhx_alloc_peak): what a memory plan is held to
+static std::atomic<uint64_t> g_held_bytes{0}, g_peak_bytes{0};
+static void note_held(uint64_t add) {
+  const uint64_t now = g_held_bytes.fetch_add(add) + add;
+  uint64_t peak = g_peak_bytes.load();
+  while (peak < now && !g_peak_bytes.compare_exchange_weak(peak, now)) {
+  }
+}
 static uint64_t now_ns() { return (uint64_t)std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
 
 void DevBuf::reserve(size_t bytes) {
@@ -33,6 +41,7 @@ void DevBuf::reserve(size_t bytes) {
   if (cap >= bytes && p) return;
   if (p && cap) {
     const uint64_t t0 = now_ns();
+    g_held_bytes -= cap;
     (void)hipFree(p);
     g_free_ns += now_ns() - t0;
   }
@@ -48,7 +57,10 @@ void DevBuf::reserve(size_t bytes) {
   }
   g_alloc_ns += now_ns() - t0;
   g_alloc_calls += 1;
-  if (e == hipSuccess) g_alloc_bytes += want;
+  if (e == hipSuccess) {
+    g_alloc_bytes += want;
+    note_held(want);
+  }
   if (e != hipSuccess) {
     p = nullptr;
     char b[256];
@@ -60,6 +72,7 @@ void DevBuf::reserve(size_t bytes) {
 void DevBuf::release() {
   if (p && cap) {
     const uint64_t t0 = now_ns();
+    g_held_bytes -= cap;
     (void)hipFree(p);
     g_free_ns += now_ns() - t0;
   }
@@ -542,8 +555,17 @@ mhx_ctx *mhx_create(int device) {
 int mhx_trim(mhx_ctx *c) {
   MHX_TRY({
     MHX_HIP(hipStreamSynchronize(c->stream));
-    for (auto &kv : c->work) kv.second.release();
-    c->work.clear();
+    // (stage 1's aggregated stage-2 items are state that the next stage 2 reads, not scratch: they stay while they are valid; a bucket
+    // filter's tables go, and the filter with them)
+    for (auto it = c->work.begin(); it != c->work.end();) {
+      if (c->agg_valid && it->first == "s2_agg_items") {
+        ++it;
+        continue;
+      }
+      it->second.release();
+      it = c->work.erase(it);
+    }
+    c->filter_on = c->accumulate = false;
     // the unitig graph's cleaning state (owner map, flags, the edge ranking the owner map comes from) lives in workspaces
     c->ut_ready = c->ut_owner = false;
     // the sorted-items view aliases a workspace
@@ -1135,15 +1157,22 @@ void mhx_alloc_stats(double *malloc_s, double *free_s, uint64_t *bytes, uint64_t
   if (calls) *calls = mhx::g_alloc_calls.load();
 }
 
+void mhx_alloc_peak(uint64_t *held_now, uint64_t *peak, int reset_peak) {
+  const uint64_t held = mhx::g_held_bytes.load();
+  if (held_now) *held_now = held;
+  if (peak) *peak = mhx::g_peak_bytes.load();
+  if (reset_peak) mhx::g_peak_bytes.store(held);
+}
+
 uint64_t mhx_device_free_bytes(mhx_ctx *c) {
   size_t free_b = 0, total_b = 0;
   if (hipSetDevice(c->device) != hipSuccess || hipMemGetInfo(&free_b, &total_b) != hipSuccess) return 0;
   return (uint64_t)free_b;
 }
+static uint64_t giant_partial_bytes(uint64_t n_items) { return std::max<uint64_t>(2u << 20, n_items / 64) * 16; }
 uint64_t mhx_stage_pass_bytes(mhx_ctx *c, int stage, uint32_t k, uint32_t min_count, uint64_t n_items) {
   // what a pass over n_items (kept) items of `stage` holds on the device besides the stage's fixed state
   try {
-    (void)min_count;
     // (the question is about a filtered pass: asked with the filter fields set, restored whatever happens)
     struct AsFilteredPass {
       mhx_ctx *c;
@@ -1162,24 +1191,39 @@ uint64_t mhx_stage_pass_bytes(mhx_ctx *c, int stage, uint32_t k, uint32_t min_co
       const AsFilteredPass filtered(c, n_items);
       const bool gen = mhx::s1_filter_in_gen_applies(c, k);
       // the generating first pass: two 12-byte record buffers, nothing staged, nothing split; its status words walk ALL item slots
-      if (gen) return n_items * 24 + n_items / 2 + (c->seqs.n_bases + 4 * c->seqs.n_seqs) / 3;
+      // + the partial sums of the giant buckets' slices (s1.hip S1Giant: max(2 M, items / 64) entries of 16 bytes) and, k <= 22 with a min
+      // count >= 2, the aggregated stage-2 items of the kept buckets at their bound (two 8-byte items per solid run of >= min_count records)
+      if (gen)
+        return n_items * 24 + n_items / 2 + (c->seqs.n_bases + 4 * c->seqs.n_seqs) / 3 + giant_partial_bytes(n_items) +
+               (k <= 22 && min_count >= 2 ? n_items * 16 / min_count : 0);
       return n_items * (3 * (uint64_t)mhx::s1_stride(k, mhx::s1_compact(c, k, 0)) * 4 + 1);
     }
     if (stage == MHX_STAGE_COUNT && c->seqs.n_seqs) {
       const AsFilteredPass filtered(c, n_items);
       // count on the stage-1 design: two 12-byte record buffers (the solid edges and the events live in the spare one)
       if (mhx::count_stream_applies(c, k, min_count, false) && (2 * (k + 1) + 16 + 31) / 32 <= 3)
-        return n_items * 24 + n_items / 2 + c->seqs.n_bases / 3;
+        // + the giant buckets' partial sums and listed keys (count.hip: 4096 giants x kGiantFlagged keys of 8 bytes = 32 MiB) and the solid
+        // edges of the kept buckets at their bound, one per min_count records, in two work buffers and the result
+        return n_items * 24 + n_items / 2 + c->seqs.n_bases / 3 + giant_partial_bytes(n_items) + (32ull << 20) +
+               3 * (n_items / (min_count ? min_count : 1)) * (uint64_t)((2 * (k + 1) + 16 + 31) / 32) * 4;
     }
-    // stage 2 from a count of the (k+1)-mers (s2.hip s2_agg_from_count): two 12-byte record buffers per edge occurrence — about one per
-    // base, where the caller's item estimate (per-occurrence items) is ~2.2 per base — and the few aggregated items behind them
-    if (stage == MHX_STAGE_S2 && c->seqs.n_seqs && mhx::s2_agg_from_count_applies(c, k, min_count)) return n_items * 13;
+    // (stage 2 from a count of the (k+1)-mers does not run under a bucket filter: mhx_stage_once_bytes)
     uint64_t ib = 16;
     if (stage == MHX_STAGE_S1_MERCY) ib = (uint64_t)mhx::s1_stride(k, false) * 4;
     else if (stage == MHX_STAGE_COUNT) ib = (uint64_t)mhx::count_stride(k) * 4;
     else if (stage == MHX_STAGE_SEQ2SDBG) ib = (uint64_t)mhx::seq2sdbg_stride(k) * 4;
     else if (stage == MHX_STAGE_S2) ib = (uint64_t)mhx::s2_stride(k) * 4;
     return n_items * (3 * ib + 1);  // 2 sort buffers + the filtered copy (+ status words)
+  } catch (...) {
+    return 0;
+  }
+}
+uint64_t mhx_stage_once_bytes(mhx_ctx *c, int stage, uint32_t k, uint32_t min_count, uint64_t n_items) {
+  try {
+    // stage 2 from a count of the (k+1)-mers (s2.hip s2_agg_from_count): two 12-byte record buffers per edge occurrence — about one per
+    // base, where the caller's item estimate (per-occurrence items) is ~2.2 per base — and the few aggregated items behind them
+    if (stage == MHX_STAGE_S2 && c->seqs.n_seqs && !c->filter_on && mhx::s2_agg_from_count_applies(c, k, min_count)) return n_items * 13;
+    return 0;
   } catch (...) {
     return 0;
   }

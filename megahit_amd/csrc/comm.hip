@@ -146,6 +146,9 @@ struct mhx_comm {
   // payload bytes this rank handed to OTHER ranks in all_to_all_v since the last reset (mhx_comm_bytes_sent: the tests bound the
   // bytes per foreign record with it, the bench prints it per step)
   uint64_t bytes_sent = 0;
+  // what every planned stage of this rank's driver calls held on the device (mhx_dist_plan_memory): per stage 4 values —
+  // enum mhx_stage, bytes held when the plan was made, their peak until the stage's last pass was done, the free bytes planned with
+  std::vector<uint64_t> plan_memory;
 
   // ---- collectives on small host vectors ----
   void all_reduce(std::vector<uint64_t> &v, bool is_max) {
@@ -526,7 +529,26 @@ struct DistPasses {
   std::vector<std::vector<uint8_t>> keep;   // [pass][bucket]
   std::vector<uint64_t> expected;           // [pass]: local items in the kept buckets
 };
+static DistPasses plan_dist_passes_of(mhx_ctx *c, mhx_comm *cm, int stage, uint32_t k, uint32_t m, size_t item_bytes);
+// The plan, and the start of the stage's record in cm->plan_memory.  The counter is the process's: ranks that are threads of one
+// process wait for each other, one of them restarts the peak, and the record holds all of them together.
 static DistPasses plan_dist_passes(mhx_ctx *c, mhx_comm *cm, int stage, uint32_t k, uint32_t m, size_t item_bytes) {
+  if (cm->grp) cm->barrier();
+  uint64_t held = 0;
+  mhx_alloc_peak(&held, nullptr, !cm->grp || cm->rank == 0);
+  if (cm->grp) cm->barrier();
+  double budget = (double)mhx_device_free_bytes(c);
+  if (const char *e = getenv("MHX_FREE_BYTES")) budget = atof(e);
+  const uint64_t rec[4] = {(uint64_t)stage, held, held, (uint64_t)budget};
+  cm->plan_memory.insert(cm->plan_memory.end(), rec, rec + 4);
+  return plan_dist_passes_of(c, cm, stage, k, m, item_bytes);
+}
+// the stage's passes are done on every rank: its record gets the peak
+static void close_plan_memory(mhx_comm *cm) {
+  if (cm->grp) cm->barrier();
+  if (cm->plan_memory.size() >= 4) mhx_alloc_peak(nullptr, &cm->plan_memory[cm->plan_memory.size() - 2], 0);
+}
+static DistPasses plan_dist_passes_of(mhx_ctx *c, mhx_comm *cm, int stage, uint32_t k, uint32_t m, size_t item_bytes) {
   DistPasses dp;
   // bytes per item a pass needs on a rank: the extracted copy + the send copy / sorted copy + receive buffer + its sort twin
   const double per_item = 4.0 * (double)item_bytes + 1.0;
@@ -721,6 +743,19 @@ uint64_t mhx_comm_bytes_sent(mhx_comm *cm, int reset) {
   if (reset) cm->bytes_sent = 0;
   return v;
 }
+int mhx_dist_plan_memory(mhx_comm *cm, int i, int *stage, uint64_t *held_at_plan, uint64_t *peak, uint64_t *budget, int clear) {
+  if (!cm) return 0;
+  const int n = (int)(cm->plan_memory.size() / 4);
+  if (i >= 0 && i < n) {
+    const uint64_t *r = &cm->plan_memory[(size_t)i * 4];
+    if (stage) *stage = (int)r[0];
+    if (held_at_plan) *held_at_plan = r[1];
+    if (peak) *peak = r[2];
+    if (budget) *budget = r[3];
+  }
+  if (clear) cm->plan_memory.clear();
+  return n;
+}
 int mhx_comm_all_reduce_u64(mhx_comm *cm, uint64_t *values, uint64_t n, int is_max) {
   MHX_TRYC({
     std::vector<uint64_t> v(values, values + n);
@@ -826,6 +861,7 @@ int mhx_dist_read2sdbg(mhx_ctx *c, mhx_comm *cm, uint32_t k, uint32_t min_count,
         r1 = rp;
       }
       mhx::clear_pass(c, dp);
+      mhx::close_plan_memory(cm);
       c->s1_density = 0;
       r1.n_items = n_items_all;
       // the marks of the NON-solid (k+1)-mer occurrences of the owned buckets -> the ranks that hold those reads, which
@@ -852,6 +888,7 @@ int mhx_dist_read2sdbg(mhx_ctx *c, mhx_comm *cm, uint32_t k, uint32_t min_count,
         mhx::add_result(r2, rp);
       }
       mhx::clear_pass(c, dp);
+      mhx::close_plan_memory(cm);
       if (dp.n > 1) mhx::sdbg_publish_accumulated(c);
     }
     if (out1) *out1 = r1;
@@ -900,6 +937,7 @@ int mhx_dist_count(mhx_ctx *c, mhx_comm *cm, uint32_t k, uint32_t min_count, mhx
       r.words_per_edge = rp.words_per_edge;
     }
     mhx::clear_pass(c, dp);
+    mhx::close_plan_memory(cm);
     c->s1_density = 0;
     if (dp.n > 1) {
       std::swap(c->results[MHX_BUF_EDGES].p, c->work["acc_edges"].p);
@@ -970,6 +1008,7 @@ int mhx_dist_seq2sdbg(mhx_ctx *c, mhx_comm *cm, uint32_t k, mhx_sdbg_result *out
       mhx::add_result(r, rp);
     }
     mhx::clear_pass(c, dp);
+    mhx::close_plan_memory(cm);
     if (dp.n > 1) mhx::sdbg_publish_accumulated(c);
     c->global_bases = saved;
     if (out) *out = r;

@@ -402,21 +402,79 @@ struct BucketRange {
   uint32_t lo, hi;
   uint64_t n_items;
 };
+// What a planned stage held on the device (mhx_alloc_peak): the bytes held when its plan was made, the peak until its last pass was
+// done, and the free bytes the plan was made with — the budget the plan is held to (tests/test_gpu_memory_plan.py).
+struct PlanMemory {
+  uint64_t held = 0;
+  double budget = 0;
+} g_plan_memory;
+void note_plan_memory(double free_bytes) {
+  mhx_alloc_peak(&g_plan_memory.held, nullptr, 1);
+  g_plan_memory.budget = free_bytes;
+}
+// The staging of a stage that extracts over batches of reads (the lv1 histogram of such a stage, and its filtered passes: one batch of
+// items and its keep/drop split) is sized by the budget too: a 32nd of the free bytes each, 1 GiB at the most — 1/15 of the free bytes
+// with the allocator's headroom, out of the fifth the plan leaves free.
+uint64_t plan_batch_bytes() { return (uint64_t)std::min(std::max(g_plan_memory.budget / 32.0, 1048576.0), 1073741824.0); }
+const char *stage_name(int stage) {
+  switch (stage) {
+    case MHX_STAGE_S1: return "stage 1";
+    case MHX_STAGE_S1_MERCY: return "stage 1 (mercy)";
+    case MHX_STAGE_S2: return "stage 2";
+    case MHX_STAGE_COUNT: return "count";
+    case MHX_STAGE_SEQ2SDBG: return "seq2sdbg";
+  }
+  return "stage";
+}
+void report_plan_memory(int stage) {
+  uint64_t peak = 0;
+  mhx_alloc_peak(nullptr, &peak, 0);
+  info("Device memory of %s: %llu bytes held when planned, peak %llu bytes, budget %.0f", stage_name(stage), (unsigned long long)g_plan_memory.held,
+       (unsigned long long)peak, g_plan_memory.budget);
+}
+// the same for the stages of a rank driver call (mhx_dist_plan_memory: the ranks of this process together)
+void report_rank_memory(mhx_comm *cm) {
+  int stage = 0;
+  uint64_t held = 0, peak = 0, budget = 0;
+  const int n = mhx_dist_plan_memory(cm, -1, nullptr, nullptr, nullptr, nullptr, 0);
+  for (int i = 0; i < n; ++i) {
+    mhx_dist_plan_memory(cm, i, &stage, &held, &peak, &budget, i + 1 == n);
+    info("Device memory of %s: %llu bytes held when planned, peak %llu bytes, budget %llu", stage_name(stage), (unsigned long long)held,
+         (unsigned long long)peak, (unsigned long long)budget);
+  }
+}
 // fixed_bytes: device state of the stage that does not shrink with the bucket range (stage 1: the 1 B/base mark map, the
 // bitmap and the aggregated stage-2 items; count: first_0_out / last_0_in; all: sort status words ~ items / 3)
 std::vector<BucketRange> plan_ranges(mhx_ctx *c, int stage, uint32_t k, uint32_t m, size_t item_bytes, double items_upper_bound,
                                      double fixed_bytes = 0) {
   uint64_t max_items = 0;
+  double free_bytes = (double)mhx_device_free_bytes(c);
+  if (const char *e = getenv("MHX_FREE_BYTES")) free_bytes = atof(e);  // tests: make the automatic plan fire on a small input
+  note_plan_memory(free_bytes);
   if (const char *e = getenv("MHX_MAX_ITEMS")) max_items = strtoull(e, nullptr, 10);
   else {
-    double free_bytes = (double)mhx_device_free_bytes(c);
-    if (const char *e = getenv("MHX_FREE_BYTES")) free_bytes = atof(e);  // tests: make the automatic plan fire on a small input
-    const double avail = free_bytes * 0.8 - fixed_bytes;
-    if (avail <= 0) fatal("not enough free device memory for the fixed state of this stage (%.1f GB free, %.1f GB needed)", free_bytes / 1e9,
-                          fixed_bytes / 1e9);
+    // What the figures leave out is taken off here: the part of the library's figure that does not grow with the items (status words
+    // over all item slots, the giant buckets' tables: its answer for no items), the staging of the batched extraction (one batch of items
+    // and its split) and the allocator's headroom (DevBuf::reserve: bytes + bytes / 16) on both and on every item buffer below.
+    const double lib_fixed = (double)mhx_stage_pass_bytes(c, stage, k, m, 0);
+    const double headroom = 17.0 / 16.0;
+    if (free_bytes * 0.8 - fixed_bytes <= 0)
+      fatal("not enough free device memory for the fixed state of this stage (%.1f GB free, %.1f GB needed)", free_bytes / 1e9, fixed_bytes / 1e9);
+    double avail = free_bytes * 0.8 - fixed_bytes - (lib_fixed + 2.0 * (double)plan_batch_bytes()) * headroom;
+    // (tables of a fixed size — tens of MB — against a free memory of a few MB, as the tests fake it: the passes are planned with a
+    //  twelfth of it, and the stage will hold more than was free)
+    if (avail < free_bytes / 12.0) {
+      info("WARNING: the workspaces of a fixed size of this stage (%.0f MB) leave less than a twelfth of the free device memory (%.0f MB) for its items: planning with that twelfth",
+           lib_fixed * headroom / 1e6, free_bytes / 1e6);
+      avail = free_bytes / 12.0;
+    }
+    // A route that serves only the whole job at once decides only whether one run fits: a plan of several passes sets the bucket
+    // filter, which switches such a route off, so its ranges are sized with the figure of a filtered pass below.
+    const uint64_t once_bytes = mhx_stage_once_bytes(c, stage, k, m, (uint64_t)items_upper_bound);
+    if (once_bytes && (double)once_bytes * headroom <= avail) return {{0, MHX_NUM_BUCKETS, 0}};
     // 2 sort buffers + filtered copy (+ status words); the library knows better where a stage has a leaner path
     const uint64_t probe = 1ull << 30, lib_bytes = mhx_stage_pass_bytes(c, stage, k, m, probe);
-    const double per_item = lib_bytes ? (double)lib_bytes / (double)probe : 3.0 * (double)item_bytes + 1.0;
+    const double per_item = headroom * (lib_bytes ? ((double)lib_bytes - lib_fixed) / (double)probe : 3.0 * (double)item_bytes + 1.0);
     const double fit = avail / per_item;
     // Plan by TIME as well as by space (round 6).  On this driver hipMalloc costs per BYTE mapped, not per call (tools/micro/alloc_probe:
     // 200 GB in one call 3.4 s, in 40 calls 4.4 s; between 3 and 30 ms per GB from box to box and process to process), while one more
@@ -453,6 +511,7 @@ std::vector<BucketRange> plan_ranges(mhx_ctx *c, int stage, uint32_t k, uint32_t
   }
   if (!max_items) return {{0, MHX_NUM_BUCKETS, 0}};
   std::vector<uint64_t> hist(MHX_NUM_BUCKETS);
+  CK(mhx_set_bucket_filter(c, nullptr, 0, plan_batch_bytes(), 0));  // (no filter: the batch size alone)
   CK(mhx_bucket_histogram(c, stage, k, m, hist.data()));
   std::vector<BucketRange> out;
   uint32_t lo = 0;
@@ -477,7 +536,7 @@ void set_range(mhx_ctx *c, const std::vector<BucketRange> &ranges, size_t i, boo
   if (ranges.size() == 1) return;  // everything at once: no filter
   std::vector<uint8_t> keep(MHX_NUM_BUCKETS, 0);
   for (uint32_t b = ranges[i].lo; b < ranges[i].hi; ++b) keep[b] = 1;
-  CK(mhx_set_bucket_filter(c, keep.data(), ranges[i].n_items, 0, accumulate && i > 0 ? 1 : 0));
+  CK(mhx_set_bucket_filter(c, keep.data(), ranges[i].n_items, plan_batch_bytes(), accumulate && i > 0 ? 1 : 0));
 }
 void clear_range(mhx_ctx *c, const std::vector<BucketRange> &ranges) {
   if (ranges.size() > 1) CK(mhx_set_bucket_filter(c, nullptr, 0, 0, 0));
@@ -596,6 +655,7 @@ int main_kmer_count(int argc, char **argv) {
       CKT(mhx_load_bin_records(c, lib.data + w0, w1 - w0, hi - lo, 1));
       CKT(mhx_dist_setup(c, cm, MHX_STAGE_COUNT, k, m));
       CKT(mhx_dist_count(c, cm, k, m, &res[r]));
+      if (r == 0) report_rank_memory(cm);
       if (r == 0) plan_text = mhx_last_s1_plan(c);
       edges[r] = fetch_t<uint32_t>(c, MHX_BUF_EDGES);
       bc[r] = fetch_t<uint64_t>(c, MHX_BUF_BUCKET_COUNT);
@@ -645,6 +705,7 @@ int main_kmer_count(int argc, char **argv) {
     self_planned = true;
     mhx_set_option(c, "count_skm", 3);
     ranges = {{0, MHX_NUM_BUCKETS, 0}};
+    note_plan_memory((double)mhx_device_free_bytes(c));
   } else {
     ranges = plan_ranges(c, MHX_STAGE_COUNT, k, m, count_item_bytes, (double)mhx_num_bases(c), 12.0 * (double)mhx_num_sequences(c));
   }
@@ -683,6 +744,7 @@ int main_kmer_count(int argc, char **argv) {
     r.words_per_edge = pr.words_per_edge;
   }
   clear_range(c, ranges);
+  report_plan_memory(MHX_STAGE_COUNT);
   info("GPU count: %llu items, %llu distinct, %llu solid. Time elapsed: %.4f", (unsigned long long)r.n_items,
        (unsigned long long)r.n_distinct, (unsigned long long)r.n_edges, t.lap());
   info("Count plan: %s", mhx_last_s1_plan(c));
@@ -741,6 +803,7 @@ int main_read2sdbg(int argc, char **argv) {
       CKT(mhx_dist_setup(c, cm, m > 1 ? (mercy_mode ? MHX_STAGE_S1_MERCY : MHX_STAGE_S1) : MHX_STAGE_S2, k, m));
       mhx_sdbg_result r2{};
       CKT(mhx_dist_read2sdbg(c, cm, k, m, mercy_mode, &r1[r], &r2, &nm[r]));
+      if (r == 0) report_rank_memory(cm);
       if (m > 1) hist[r] = fetch_t<int64_t>(c, MHX_BUF_MUL_HIST);
       if (r == 0) plan_text = mhx_last_s1_plan(c);
       part[r].add(fetch_t<uint8_t>(c, MHX_BUF_SDBG_BYTES), fetch_t<uint64_t>(c, MHX_BUF_BUCKET_OFFSET), fetch_t<uint64_t>(c, MHX_BUF_BUCKET_COUNT),
@@ -790,6 +853,7 @@ int main_read2sdbg(int argc, char **argv) {
     if (!getenv("MHX_MAX_ITEMS") && !getenv("MHX_FREE_BYTES") && mhx_s1_self_planned(c, k, m, mercy_mode) == 1) {
       const long long before = mhx_get_option(c, "s1_skm", 1);
       mhx_set_option(c, "s1_skm", 3);
+      note_plan_memory((double)mhx_device_free_bytes(c));
       s1_done = mhx_read2sdbg_s1(c, k, m, mercy_mode, &r1) == 0;
       if (!s1_done) info("Stage 1 on super-k-mer records: %s; planning lv1 bucket ranges instead", mhx_last_error());
       mhx_set_option(c, "s1_skm", s1_done ? before : 0);
@@ -807,6 +871,7 @@ int main_read2sdbg(int argc, char **argv) {
       clear_range(c, ranges);
       r1.n_items = n1;
     }
+    report_plan_memory(mercy_mode ? MHX_STAGE_S1_MERCY : MHX_STAGE_S1);
     auto hist = fetch<int64_t>(c, MHX_BUF_MUL_HIST);
     int64_t n_solid_edges = 0;
     for (uint32_t i = m; i <= 65535; ++i) n_solid_edges += hist[i];
@@ -834,6 +899,7 @@ int main_read2sdbg(int argc, char **argv) {
     acc.add(c, pr);
   }
   clear_range(c, ranges2);
+  report_plan_memory(MHX_STAGE_S2);
   info("Stage 2 done (%llu items). Time elapsed: %.4f", (unsigned long long)acc.r.n_items, t.lap());
   acc.write(out, k, out_files(n_threads));
   info("Postprocess done. Time elapsed: %.4f", t.lap());
@@ -938,6 +1004,7 @@ int main_seq2sdbg(int argc, char **argv) {
       CKT(mhx_dist_setup(c, cm, MHX_STAGE_SEQ2SDBG, k, 0));
       mhx_sdbg_result r2{};
       CKT(mhx_dist_seq2sdbg(c, cm, k, &r2));
+      if (r == 0) report_rank_memory(cm);
       part[r].add(fetch_t<uint8_t>(c, MHX_BUF_SDBG_BYTES), fetch_t<uint64_t>(c, MHX_BUF_BUCKET_OFFSET), fetch_t<uint64_t>(c, MHX_BUF_BUCKET_COUNT),
                   fetch_t<uint64_t>(c, MHX_BUF_BUCKET_TIPS), fetch_t<uint64_t>(c, MHX_BUF_BUCKET_LARGE), fetch_t<uint64_t>(c, MHX_BUF_W_COUNT), r2);
     });
@@ -1031,6 +1098,7 @@ int main_seq2sdbg(int argc, char **argv) {
     acc.add(c, pr);
   }
   clear_range(c, ranges);
+  report_plan_memory(MHX_STAGE_SEQ2SDBG);
   info("GPU seq2sdbg done (%llu items). Time elapsed: %.4f", (unsigned long long)acc.r.n_items, t.lap());
   acc.write(out, k, out_files(n_threads));
   info("Postprocess done. Time elapsed: %.4f", t.lap());

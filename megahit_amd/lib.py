@@ -169,6 +169,7 @@ SYMBOLS = {
     "mhx_comm_size": (C.c_int, [_P]),
     "mhx_comm_barrier": (C.c_int, [_P]),
     "mhx_comm_bytes_sent": (C.c_uint64, [_P, C.c_int]),
+    "mhx_dist_plan_memory": (C.c_int, [_P, C.c_int, _P, _P, _P, _P, C.c_int]),
     "mhx_comm_all_reduce_u64": (C.c_int, [_P, _P, C.c_uint64, C.c_int]),
     "mhx_dist_setup": (C.c_int, [_P, _P, C.c_int, C.c_uint32, C.c_uint32]),
     "mhx_dist_read2sdbg": (C.c_int, [_P, _P, C.c_uint32, C.c_uint32, C.c_int, C.POINTER(S1Result), C.POINTER(SdbgResult), _P]),
@@ -179,7 +180,9 @@ SYMBOLS = {
     "mhx_bucket_histogram": (C.c_int, [_P, C.c_int, C.c_uint32, C.c_uint32, _P]),
     "mhx_set_bucket_filter": (C.c_int, [_P, _P, C.c_uint64, C.c_uint64, C.c_int]),
     "mhx_stage_pass_bytes": (C.c_uint64, [_P, C.c_int, C.c_uint32, C.c_uint32, C.c_uint64]),
+    "mhx_stage_once_bytes": (C.c_uint64, [_P, C.c_int, C.c_uint32, C.c_uint32, C.c_uint64]),
     "mhx_alloc_stats": (None, [_P, _P, _P, _P]),
+    "mhx_alloc_peak": (None, [_P, _P, C.c_int]),
     "mhx_comm_init_hosted": (_P, [_P, C.c_int, C.c_int, _P]),
     "mhx_reset": (C.c_int, [_P]),
     "mhx_last_s1_plan": (C.c_char_p, [_P]),
@@ -400,6 +403,22 @@ class Engine:
 
     def trim(self):
         self._chk(self.lib.mhx_trim(self.h))
+
+    def alloc_peak(self, reset=False):
+        """-> (device bytes the library's buffers of this process hold now, their high-water mark); reset: the mark restarts
+        at the bytes held now (mhx_alloc_peak; process-wide, not per handle)"""
+        held, peak = C.c_uint64(0), C.c_uint64(0)
+        self.lib.mhx_alloc_peak(C.byref(held), C.byref(peak), int(reset))
+        return int(held.value), int(peak.value)
+
+    def stage_pass_bytes(self, stage, k, m, n_items):
+        """device bytes the memory plan assumes for a pass of `stage` over n_items kept items (mhx_stage_pass_bytes)"""
+        return int(self.lib.mhx_stage_pass_bytes(self.h, stage, k, m, int(n_items)))
+
+    def stage_once_bytes(self, stage, k, m, n_items):
+        """device bytes the memory plan assumes for one unfiltered run of `stage` where that has a leaner route; 0: none
+        (mhx_stage_once_bytes)"""
+        return int(self.lib.mhx_stage_once_bytes(self.h, stage, k, m, int(n_items)))
 
     def fastx_to_records(self, text1, text2=None):
         """FASTA/FASTQ text -> read-library records on the GPU; returns (FastxResult, uint32 records or None)."""
