@@ -156,7 +156,8 @@ int mhx_set_option(mhx_ctx *, const char *name, long long value);
  *                          array), so the sort starts at the second digit: one 16-byte pass fewer (bins of two digits or more; a range
  *                          that overflows — skewed bins — makes the records again, unsplit); 0: one cursor and all passes;
  *                          s1_skm_split_stage (2560): records of a workgroup's trip that are ordered by digit in LDS before they leave
- *                          (at most 2560; a trip that makes more writes them from the registers; tests shrink it)
+ *                          (at most 2560; a trip that makes more writes them from the registers; tests shrink it);
+ *                          s1_skm_make_grid (0 = 8 per CU): workgroups of the make kernel (tests: few workgroups, several trips each)
  *   count_skm (1)          `count` on super-k-mer records (k_skm_make<.., COUNT>, k_count_skm: a record carries one more base either side of its run,
  *                          the table the in / out characters): one GPU, 19 <= k <= 21, min count <= 2; jobs of more than s1_skm_pass_gb of
  *                          records in passes over ranges of bins (mhx_count_self_planned); 0: never; 3: fail instead of falling back;

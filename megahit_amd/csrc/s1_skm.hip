@@ -99,21 +99,38 @@ __global__ __launch_bounds__(NT) void k_skm_make(const uint32_t *__restrict__ se
   // and published as the one or two keys they are by k_skm_hp_publish.
   uint32_t hp_n[2] = {0, 0};
   unsigned long long hp_p[2] = {~0ull, ~0ull};
-  for (uint64_t it = blockIdx.x; it * (uint64_t)(NT * J) < n_blocks; it += gridDim.x) {
-    uint64_t Wv[J], pos0[J];
-    uint32_t smask[J], emask[J];  // per block: the windows that start a run of this pass's bins, and those that end one
-    uint32_t bflag[J];            // COUNT: bit 0 the block's first window is its read's first, bit 1 its last window is the read's last, bits 2.. its windows
+  // Which read a block belongs to and which of its blocks it is — b / bpr, b % bpr — is divided out ONCE per thread: from trip to trip b
+  // grows by gridDim.x * NT * J, from one block of a thread to its next by NT, so quotient and remainder move by those steps' own
+  // (uniform) quotients and remainders and one carry (a 64-bit division per block was a quarter of the kernel's vector instructions)
+  const uint64_t step_trip = (uint64_t)gridDim.x * (uint64_t)(NT * J);
+  const uint64_t trip_r = step_trip / bpr;
+  const uint32_t trip_q = (uint32_t)(step_trip - trip_r * bpr), next_r = (uint32_t)NT / bpr, next_q = (uint32_t)NT % bpr;
+  uint64_t blk_r = ((uint64_t)blockIdx.x * (uint64_t)(NT * J) + tid) / bpr;  // of the thread's first block of the trip
+  uint32_t blk_q = (uint32_t)((uint64_t)blockIdx.x * (uint64_t)(NT * J) + tid - blk_r * bpr);
+  // The words of the store a trip's blocks look at are asked for TOGETHER at the head of the trip: the J loads of a thread are in flight
+  // at once instead of one after the other, each waited for before the next block's address is worked out (a block beyond its read's
+  // last window: fq0 = fnwin = 0)
+  uint64_t fa[J];
+  uint32_t fq0[J], fnwin[J], fc[J][COUNT ? 4 : 3];
+  auto fetch = [&](uint64_t it2) {  // (called once per trip, in the order of the trips)
+    uint64_t r = blk_r;
+    uint32_t q = blk_q;
 #pragma unroll
     for (int j = 0; j < J; ++j) {
-      const uint64_t b = it * (uint64_t)(NT * J) + (uint64_t)j * NT + tid;
-      smask[j] = 0;
-      emask[j] = 0;
-      bflag[j] = 0;
-      Wv[j] = 0;
-      pos0[j] = 0;
+      const uint64_t b = it2 * (uint64_t)(NT * J) + (uint64_t)j * NT + tid;
+      fa[j] = 0;
+      fq0[j] = 0;
+      fnwin[j] = 0;
+      if (j > 0) {
+        r += next_r;
+        q += next_q;
+        if (q >= bpr) {
+          q -= bpr;
+          ++r;
+        }
+      }
       if (b < n_blocks) {
-        const uint64_t r = b / bpr;
-        const uint32_t q0 = (uint32_t)(b - r * bpr) * kSkmC;
+        const uint32_t q0 = q * kSkmC;
         uint64_t base;
         uint32_t nwin;
         if constexpr (VAR) {
@@ -126,10 +143,44 @@ __global__ __launch_bounds__(NT) void k_skm_make(const uint32_t *__restrict__ se
           nwin = L - k;
         }
         if (q0 < nwin) {
-          const uint64_t a = base + q0;
-          const uint64_t wi = a >> 4;
+          fa[j] = base + q0;
+          fq0[j] = q0;
+          fnwin[j] = nwin;
+        }
+      }
+      // (no branch around the loads — the words of all J blocks are asked for before the first is waited for; a block without windows
+      //  looks at the first words of the store, which a job on this path has)
+      const uint64_t wi = fa[j] >> 4;
+      fc[j][0] = seq[wi];
+      fc[j][1] = seq[wi + 1];
+      fc[j][2] = seq[wi + 2];
+      if constexpr (COUNT) fc[j][3] = seq[(fa[j] > 0 ? fa[j] - 1 : 0) >> 4];  // (the word of the base in front of the block)
+    }
+    blk_r += trip_r;
+    blk_q += trip_q;
+    if (blk_q >= bpr) {
+      blk_q -= bpr;
+      ++blk_r;
+    }
+  };
+  for (uint64_t it = blockIdx.x; it * (uint64_t)(NT * J) < n_blocks; it += gridDim.x) {
+    uint64_t Wv[J], pos0[J];
+    uint32_t smask[J], emask[J];  // per block: the windows that start a run of this pass's bins, and those that end one
+    uint32_t bflag[J];            // COUNT: bit 0 the block's first window is its read's first, bit 1 its last window is the read's last, bits 2.. its windows
+    fetch(it);
+#pragma unroll
+    for (int j = 0; j < J; ++j) {
+      smask[j] = 0;
+      emask[j] = 0;
+      bflag[j] = 0;
+      Wv[j] = 0;
+      pos0[j] = 0;
+      {
+        const uint32_t q0 = fq0[j], nwin = fnwin[j];
+        if (q0 < nwin) {
+          const uint64_t a = fa[j];
           const unsigned sh = (unsigned)(a & 15) * 2;
-          const uint32_t c0 = seq[wi], c1 = seq[wi + 1], c2 = seq[wi + 2];
+          const uint32_t c0 = fc[j][0], c1 = fc[j][1], c2 = fc[j][2];
           const uint64_t W = ((uint64_t)funnel_l(c0, c1, sh) << 32) | funnel_l(c1, c2, sh);
           const uint64_t R = rc64(W, 32);
           uint32_t h[kSkmNM];
@@ -159,9 +210,12 @@ __global__ __launch_bounds__(NT) void k_skm_make(const uint32_t *__restrict__ se
           uint32_t km = 0, sm = 0, hm = 0;
           if (hp) {  // (uniform) windows of one base: adjacent bases equal all along the window
             const uint64_t dx = W ^ (W << 2);  // base i differs from base i + 1: bits 63 - 2i, 62 - 2i
+            // (the bases kSkmC - 1 .. K1 - 1 lie in every window of the block: unless they are all equal, which is rare, no window is looked at)
+            if ((dx & ((~0ull >> (2 * (kSkmC - 1))) & (~0ull << (64 - 2 * (K1 - 1))))) == 0) {
 #pragma unroll
-            for (int w = 0; w < kSkmC; ++w)
-              if ((uint32_t)w < n_here && ((dx << (2 * w)) >> (64 - 2 * (K1 - 1))) == 0) hm |= 1u << w;
+              for (int w = 0; w < kSkmC; ++w)
+                if ((uint32_t)w < n_here && ((dx << (2 * w)) >> (64 - 2 * (K1 - 1))) == 0) hm |= 1u << w;
+            }
             if (hm && count_items) {
 #pragma unroll
               for (int w = 0; w < kSkmC; ++w)
@@ -172,7 +226,7 @@ __global__ __launch_bounds__(NT) void k_skm_make(const uint32_t *__restrict__ se
                     // count: the key is A...A (C...C); a window of T (G) is its reverse complement (strand 1: the bases either side swap and complement)
                     const bool strand = b >= 2;
                     const unsigned prev_raw = q0 + w == 0 ? kSentinel
-                                              : (w == 0 ? (unsigned)((seq[(a - 1) >> 4] >> (30 - 2 * (unsigned)((a - 1) & 15))) & 3u) : (unsigned)(W >> (64 - 2 * w)) & 3u);
+                                              : (w == 0 ? (unsigned)((fc[j][COUNT ? 3 : 0] >> (30 - 2 * (unsigned)((a - 1) & 15))) & 3u) : (unsigned)(W >> (64 - 2 * w)) & 3u);
                     const unsigned next_raw = q0 + w + 1 == nwin ? kSentinel : (unsigned)(W >> (62 - 2 * (w + K1))) & 3u;
                     const unsigned pv = strand ? comp_or_sentinel(next_raw) : prev_raw, nx = strand ? comp_or_sentinel(prev_raw) : next_raw;
                     atomicAdd(&hpl[cls][0], 1u);
@@ -194,7 +248,7 @@ __global__ __launch_bounds__(NT) void k_skm_make(const uint32_t *__restrict__ se
           smask[j] = sm;
           emask[j] = km & ((sm >> 1) | ~(km >> 1));  // window w ends a run: the next one starts one, or is not this pass's (bit 8 of km is clear)
           if constexpr (COUNT) {  // the window that starts one base earlier: the base in front of the block's first window, then 31 bases
-            const uint64_t pb = a > 0 ? (uint64_t)((seq[(a - 1) >> 4] >> (30 - 2 * (unsigned)((a - 1) & 15))) & 3u) : 0ull;
+            const uint64_t pb = a > 0 ? (uint64_t)((fc[j][COUNT ? 3 : 0] >> (30 - 2 * (unsigned)((a - 1) & 15))) & 3u) : 0ull;
             Wv[j] = (W >> 2) | (pb << 62);
             bflag[j] = (q0 == 0 ? 1u : 0u) | (q0 + n_here == nwin ? 2u : 0u) | (n_here << 2);
           } else {
@@ -1362,7 +1416,9 @@ bool s1_skm_front(mhx_ctx *c, uint32_t k, SkmFront *f, int pass, int n_passes, i
   unsigned long long *pre_hist = c->ws("sort_pre_hist", (size_t)kMaxFusedPasses * 256 * 8).as<unsigned long long>();
   constexpr int NT = 512, J = 2;
   const uint64_t cus = c->n_cus > 0 ? (uint64_t)c->n_cus : 256;
-  const unsigned grid = (unsigned)std::min<uint64_t>(div_ceil(n_blocks, (uint64_t)NT * J), cus * 8);
+  // (s1_skm_make_grid: fewer workgroups, each with several trips over the blocks — tests on libraries of a few trips in all)
+  const long long grid_knob = c->opt("s1_skm_make_grid", 0);
+  const unsigned grid = (unsigned)std::min<uint64_t>(div_ceil(n_blocks, (uint64_t)NT * J), grid_knob > 0 ? (uint64_t)grid_knob : cus * 8);
   const uint32_t n_bins = 1u << bin_bits;
   const uint32_t bin_lo = (uint32_t)((uint64_t)n_bins * pass / n_passes), bin_hi = (uint32_t)((uint64_t)n_bins * (pass + 1) / n_passes);
   // homopolymer windows are counted beside the records on one GPU (several GPUs: they stay in the records; a job with many gives the path up)

@@ -19,7 +19,8 @@ import oracle_binding as ob  # noqa: E402
 from megahit_amd import lib, synth  # noqa: E402
 
 RESET = dict(s1_skm=1, s1_stream_fill=7168, s1_stream_probes=1024, s1_skm_max_bin=65536, s1_skm_bin_bits=0, s1_skm_tags=0, s1_skm_cap_pct=36, s1_var_min_fill=50,
-             s1_skm_passes=0, s1_skm_deal=1, s1_skm_hp=1, count_skm=1, count_skm_group=2, s1_skm_split=1, s1_skm_split_stage=2560)
+             s1_skm_passes=0, s1_skm_deal=1, s1_skm_hp=1, count_skm=1, count_skm_group=2, s1_skm_split=1, s1_skm_split_stage=2560,
+             s1_skm_make_grid=0)
 
 
 def library(rng):
@@ -64,6 +65,8 @@ def knobs(rng):
         o["s1_skm_split"] = 0
     if rng.random() < 0.3:
         o["s1_skm_split_stage"] = int(rng.choice([0, 64, 700]))
+    if rng.random() < 0.4:  # (few workgroups: several trips each)
+        o["s1_skm_make_grid"] = int(rng.choice([1, 2, 5]))
     return o
 
 

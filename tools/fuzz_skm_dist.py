@@ -50,6 +50,8 @@ def main():
             opts["s1_skm_split"] = 0
         if rng.random() < 0.3:
             opts["s1_skm_split_stage"] = int(rng.choice([0, 64, 700]))
+        if rng.random() < 0.4:
+            opts["s1_skm_make_grid"] = int(rng.choice([1, 2, 5]))
 
         def load(r, e):
             pkg = ob.Package(shards[r], reverse=True)
