@@ -137,6 +137,18 @@ int mhx_set_option(mhx_ctx *, const char *name, long long value);
  *   s1_stream_wide (1)     0: stage 1 at k = 23..29 takes the segment group-by (k_s1_seg); 1: the bucket streaming with 64-bit table keys
  *   s2_agg_from_count (1)  0: stage 2 always makes its solid items per occurrence where stage 1 left no aggregated ones; 1: min count 1
  *                          (k <= 27) and min count >= 2 at k = 23..27 take them from a count of the (k+1)-mers (s2.hip s2_agg_from_count)
+ *   s2_dummy_list (1)      the '$' items of aggregated stage 2 (csrc/s2.hip k_s2d_emit): 1: the run ends of a workgroup's bitmap words are
+ *                          compacted into an LDS list and dealt one per lane, so that the gathers from the reads are in flight together;
+ *                          0: every thread walks the run ends of its own words one after the other (same items, other order);
+ *                          s2_dummy_list_cap (0 = the kernel's 4096): entries the list holds — a trip with more run ends is worked off in
+ *                          pieces of that many (tests)
+ *   s2_pre_hist (1)        1: the digit histograms of stage 2's sort are taken where its items are made — k_agg_compact at the end of stage 1,
+ *                          k_s2d_emit (needs s2_dummy_list) — and the sort reads no histogram of its own (no radix_hist_all_8B launch);
+ *                          0, or whenever the rows do not stand for exactly the items sorted: the sort takes them itself
+ *   s2_bound_from_s1 (1)   1: the room for the '$' items of stage 2 comes from a count that stage 1's pack kernel (k_pack_solid_inv*) took of
+ *                          the run ends in the words it wrote, valid while the bitmap is stage 1's own for this (k, m); 0, or a bitmap from
+ *                          elsewhere (mercy edges, mhx_set_is_solid, several GPUs): k_s2d_bound reads the bitmap and the host waits for it;
+ *                          2: both, and the call fails unless they agree (tests)
  *   sort_loaded_ut2 (0)    1: the 12-byte passes that load their records take units of two tiles (four workgroups per CU instead of three);
  *                          measured slower (profiles/r06_ab_loaded_ut2.jsonl): the passes are bound per scattered run, not by occupancy
  *   fetch_pinned (1)       0: mhx_fetch is one hipMemcpy into the caller's (pageable) memory; 1: results of >= 16 MB leave through two

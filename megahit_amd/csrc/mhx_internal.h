@@ -6,6 +6,7 @@
 #include <cstdio>
 #include <cstring>
 #include <functional>
+#include <deque>
 #include <map>
 #include <stdexcept>
 #include <string>
@@ -84,9 +85,20 @@ struct mhx_ctx {
   bool agg_valid = false;
   uint32_t agg_k = 0, agg_m = 0;
   uint64_t agg_n = 0;
+  // ws "s2_pre_hist" holds the digit histograms of stage 2's sort passes (s2_agg_sort_passes(agg_k), signature agg_hist_sig) over exactly
+  // the agg_n items, taken where stage 1 packed them; 0 passes: none.  Means something only while agg_valid; stage 2 adds its '$' items.
+  int agg_hist_passes = 0;
+  uint64_t agg_hist_sig = 0;
+  // item counts on their way to the device cursor (asynchronous copies from here: the handle outlives whatever call sent them, also one
+  // that ends in an exception); emptied when a stage 1 opens its outputs, behind a synchronisation
+  std::deque<uint64_t> agg_n_home;
   // the is_solid bitmap is exactly what stage 1 found for this (k, m) — no mercy edges added, not set by the caller: stage 2 may then take its
   // solid items from a count of the (k+1)-mers instead of from every occurrence (s2.hip s2_agg_from_count; 0: not so)
   uint32_t solid_plain_k = 0, solid_plain_m = 0;
+  // ... and s2_bound is what k_s2d_bound would count in that bitmap (two '$' items per run end), summed by the kernel that packed it:
+  // valid while solid_plain_k == s2_bound_k != 0
+  uint64_t s2_bound = 0;
+  uint32_t s2_bound_k = 0;
   uint64_t n_route = 0;      // multi-GPU: records in ws("route_records") (count events)
   uint32_t filter_kept = 0;           // lv1 buckets the filter keeps
   // stage 1: records per lv1 bucket the ranks of a multi-GPU run agreed on (comm.hip; 0: each call derives it from its own
@@ -173,6 +185,7 @@ struct SortPrep {
   // digit histograms of the sort's passes, taken by the extraction kernel (ws "sort_pre_hist"); hist_passes == 0: none
   int hist_passes = 0;
   uint64_t hist_sig = 0;  // passes_signature() of the plan they were taken for
+  const unsigned long long *hist = nullptr;  // where their rows lie when not in ws "sort_pre_hist" (device, [hist_passes][256])
   // first sort pass whose records are generated instead of loaded (sort_kernels.h OnesweepLaunch): the buffer holds NO items yet
   std::function<void(const OnesweepLaunch &)> gen;
   uint64_t gen_slots = 0;  // item slots it walks (> n when it drops the items of filtered-out lv1 buckets)
@@ -256,8 +269,10 @@ void s1_skm_bounds_of(mhx_ctx *c, const uint4 *recs, uint64_t n, uint32_t n_bins
 void s1_skm_groups_launch(mhx_ctx *c, bool agg, unsigned grid, const SkmFront &f, uint32_t k, uint32_t m, uint8_t *solid_bytes, unsigned long long *hist,
                           uint2 *agg_raw, uint32_t agg_cap, uint32_t *agg_counts, uint32_t *err, unsigned long long *marks_raw, uint32_t marks_cap,
                           uint32_t *marks_counts);
+struct DigitSpecs;
+// (agg_hist: the digit histograms of agg_specs that the items are added to, or nullptr)
 void s1_skm_hp_publish(mhx_ctx *c, const SkmFront &f, uint32_t k, uint32_t m, uint8_t *solid_bytes, unsigned long long *hist, uint2 *agg_items,
-                       uint64_t *agg_cursor, bool agg);
+                       uint64_t *agg_cursor, bool agg, const DigitSpecs *agg_specs = nullptr, unsigned long long *agg_hist = nullptr);
 // the owner's half on several GPUs (s1.hip): group-by over the received sources, marks as a list, aggregated items.  -> false: a region overflowed
 bool s1_skm_owner(mhx_ctx *c, uint32_t k, uint32_t m, const SkmFront &f, mhx_s1_result *out);
 
@@ -277,7 +292,9 @@ uint64_t s2_extract(mhx_ctx *c, uint32_t k, uint32_t m, bool filter_in_extract =
 int s2_process(mhx_ctx *c, uint32_t k, uint32_t *buf_a, uint32_t *buf_b, uint64_t n_items, mhx_sdbg_result *out);
 bool s2_use_aggregated(const mhx_ctx *c, uint32_t k, uint32_t m);
 uint64_t s2_agg_extract(mhx_ctx *c, uint32_t k);
-int s2_agg_process(mhx_ctx *c, uint32_t k, uint32_t *buf_a, uint32_t *buf_b, uint64_t n_items, mhx_sdbg_result *out);
+int s2_agg_process(mhx_ctx *c, uint32_t k, uint32_t *buf_a, uint32_t *buf_b, uint64_t n_items, mhx_sdbg_result *out, SortPrep *prep = nullptr);
+// the sort passes of aggregated stage-2 items: flag | W above the count_bits count bits, then the chars of the k-mer
+std::vector<SortPass> s2_agg_sort_passes(uint32_t k, int count_bits = 16);
 struct StageItems {
   uint64_t n;      // items in ws("items_a")
   int S;           // words per item

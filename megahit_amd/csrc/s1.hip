@@ -16,10 +16,16 @@
 
 namespace mhx {
 
-// regions of k_s1_seg -> one dense array: block (r, j) copies slice j of region r behind the items of the regions before it
+// regions of k_s1_seg -> one dense array: block (r, j) copies slice j of region r behind the items of the regions before it.
+// hist != nullptr (aggregated stage-2 items): the digit histograms of their sort's passes (specs) are taken on the way (sort_digits.h)
+template <bool HIST>
 __global__ __launch_bounds__(256) void k_agg_compact(const uint2 *__restrict__ raw, uint32_t cap, const uint32_t *__restrict__ counts,
-                                                    uint2 *__restrict__ dense, int from_back) {
+                                                    uint2 *__restrict__ dense, int from_back, DigitSpecs specs, unsigned long long *__restrict__ hist) {
   __shared__ uint64_t sm[256 / kWave + 1];
+  __shared__ uint32_t s_hist[HIST ? kItemHistRows : 1][256];  // (the plain copy — marks, events — reserves next to nothing)
+  if (HIST)
+    for (int i = threadIdx.x; i < kItemHistRows * 256; i += 256) (&s_hist[0][0])[i] = 0;  // (the scan below has barriers)
+  const ItemDigits digits(specs);
   const uint32_t r = blockIdx.x;
   uint64_t part = 0;
   for (uint32_t i = threadIdx.x; i < r; i += 256) part += counts[i];
@@ -27,7 +33,22 @@ __global__ __launch_bounds__(256) void k_agg_compact(const uint2 *__restrict__ r
   block_exclusive_sum<uint64_t, 256>(part, sm, &off);
   const uint32_t n = counts[r];
   const uint2 *src = raw + (size_t)r * cap;
-  for (uint32_t i = blockIdx.y * 256 + threadIdx.x; i < n; i += gridDim.y * 256) dense[off + i] = from_back ? src[cap - 1 - i] : src[i];
+  for (uint32_t i = blockIdx.y * 256 + threadIdx.x; i < n; i += gridDim.y * 256) {
+    const uint2 v = from_back ? src[cap - 1 - i] : src[i];
+    dense[off + i] = v;
+    if (HIST) item_hist_add(s_hist, digits, ((uint64_t)v.x << 32) | v.y);
+  }
+  if (HIST) {
+    __syncthreads();
+    item_hist_flush(s_hist, digits, hist);
+  }
+}
+
+static DigitSpecs no_digits() { return DigitSpecs{}; }
+static void agg_compact_launch(hipStream_t st, dim3 grid, const uint2 *raw, uint32_t cap, const uint32_t *counts, uint2 *dense, int from_back, const DigitSpecs &specs,
+                               unsigned long long *hist) {
+  if (hist) hipLaunchKernelGGL((k_agg_compact<true>), grid, dim3(256), 0, st, raw, cap, counts, dense, from_back, specs, hist);
+  else hipLaunchKernelGGL((k_agg_compact<false>), grid, dim3(256), 0, st, raw, cap, counts, dense, from_back, specs, hist);
 }
 
 // multi-GPU, sparse marks, classic path: positions of the set bytes of the (global) byte map, appended in any order
@@ -117,35 +138,63 @@ __global__ __launch_bounds__(256) void k_count_solid(const unsigned long long *_
 
 // mark_mode 1: bytes mark the NON-solid occurrences; a position is solid iff a (k+1)-mer starts there
 // (offset + k + 1 <= read length) and it is not marked.  One thread per 64 positions.
+// Both also add up what k_s2d_bound (s2.hip) would count in the words they write — two '$' items per end of a run of solid positions — into
+// n_solid[kCtrRunEnds], so that stage 2 need not read the bitmap for it: a word's neighbour bits come from the neighbouring lanes, at the
+// edges of a wavefront from one more byte of the map.
+__device__ __forceinline__ uint32_t run_end_items(unsigned long long v, unsigned long long prev63, unsigned long long next0) {
+  const unsigned long long l = v & ~((v << 1) | prev63), r = v & ~((v >> 1) | (next0 << 63));  // (s2d_run_ends)
+  return 2u * (uint32_t)(__builtin_popcountll(l) + __builtin_popcountll(r));
+}
 __global__ __launch_bounds__(256) void k_pack_solid_inv(const uint8_t *__restrict__ bytes, uint64_t n_bits, const uint64_t *__restrict__ start,
                                                         uint64_t n_seqs, uint32_t fixed_len, int k, unsigned long long *__restrict__ words,
                                                         uint64_t n_words, unsigned long long *__restrict__ n_solid) {
   __shared__ uint64_t sm[256 / kWave + 1];
-  uint64_t pop = 0;
-  for (uint64_t w = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; w < n_words; w += (uint64_t)gridDim.x * blockDim.x) {
-    unsigned long long v = 0;
-    const uint64_t p0 = w * 64;
-    uint64_t rid = p0 < n_bits ? seq_of_offset(start, n_seqs, fixed_len, p0) : 0;
-    uint64_t re = start[rid + 1];
-    const uint4 *pb = reinterpret_cast<const uint4 *>(bytes + p0);
-    for (int q = 0; q < 4; ++q) {
-      const uint4 x = pb[q];
-      const uint32_t xs[4] = {x.x, x.y, x.z, x.w};
-      for (int t = 0; t < 16; ++t) {
-        const uint64_t p = p0 + q * 16 + t;
-        if (p >= n_bits) break;
-        while (p >= re) re = start[++rid + 1];
-        const bool valid = p + (uint64_t)k + 1 <= re;  // a (k+1)-mer of this read starts at p
-        const bool marked = (xs[t >> 2] >> ((t & 3) * 8)) & 1u;
-        if (valid && !marked) v |= 1ull << (q * 16 + t);
+  uint64_t pop = 0, ends = 0;
+  const int lane = lane_id();
+  // solid bit of position p, which lies in read `rid` or — below its start — in the one before it
+  auto solid_at = [&](uint64_t p, uint64_t rid) -> unsigned long long {
+    if (p >= n_bits) return 0ull;
+    while (rid && p < start[rid]) --rid;
+    while (p >= start[rid + 1]) ++rid;
+    return p + (uint64_t)k + 1 <= start[rid + 1] && !(bytes[p] & 1u) ? 1ull : 0ull;
+  };
+  const uint64_t T = (uint64_t)gridDim.x * blockDim.x;
+  for (uint64_t w0 = (uint64_t)blockIdx.x * blockDim.x; w0 < n_words; w0 += T) {  // workgroup-uniform trip count (shuffles inside)
+    const uint64_t w = w0 + threadIdx.x;
+    unsigned long long v = 0, prev63 = 0, next0 = 0;
+    if (w < n_words) {
+      const uint64_t p0 = w * 64;
+      uint64_t rid = p0 < n_bits ? seq_of_offset(start, n_seqs, fixed_len, p0) : 0;
+      const uint64_t rid0 = rid;
+      uint64_t re = start[rid + 1];
+      const uint4 *pb = reinterpret_cast<const uint4 *>(bytes + p0);
+      for (int q = 0; q < 4; ++q) {
+        const uint4 x = pb[q];
+        const uint32_t xs[4] = {x.x, x.y, x.z, x.w};
+        for (int t = 0; t < 16; ++t) {
+          const uint64_t p = p0 + q * 16 + t;
+          if (p >= n_bits) break;
+          while (p >= re) re = start[++rid + 1];
+          const bool valid = p + (uint64_t)k + 1 <= re;  // a (k+1)-mer of this read starts at p
+          const bool marked = (xs[t >> 2] >> ((t & 3) * 8)) & 1u;
+          if (valid && !marked) v |= 1ull << (q * 16 + t);
+        }
       }
+      words[w] = v;
+      pop += (uint64_t)__builtin_popcountll(v);
+      if (lane == 0 && w) prev63 = solid_at(p0 - 1, rid0);
+      if (lane == kWave - 1 && w + 1 < n_words) next0 = solid_at(p0 + 64, rid);
     }
-    words[w] = v;
-    pop += (uint64_t)__builtin_popcountll(v);
+    const unsigned long long up = __shfl_up(v, 1, kWave), down = __shfl_down(v, 1, kWave);
+    if (lane > 0) prev63 = up >> 63;
+    if (lane < kWave - 1) next0 = down & 1ull;  // (a lane beyond the last word holds v = 0, as k_s2d_bound sees behind it)
+    ends += run_end_items(v, prev63, next0);
   }
-  uint64_t tot;
+  uint64_t tot, tot_e;
   block_exclusive_sum<uint64_t, 256>(pop, sm, &tot);
+  block_exclusive_sum<uint64_t, 256>(ends, sm, &tot_e);
   if (threadIdx.x == 0 && tot) atomicAdd(n_solid, (unsigned long long)tot);
+  if (threadIdx.x == 0 && tot_e) atomicAdd(n_solid + kCtrRunEnds, (unsigned long long)tot_e);
 }
 
 // The same for reads of one length L with L - k >= 16: the valid positions of 16 consecutive ones follow from the offset
@@ -158,7 +207,8 @@ __global__ __launch_bounds__(256) void k_pack_solid_inv_fixed(const uint8_t *__r
   const uint64_t T = (uint64_t)gridDim.x * blockDim.x, n_chunks = n_words * 4;
   const uint32_t step = (uint32_t)((T * 16) % L);  // the offset in the read advances by this much (mod L) per trip: one
   uint32_t off = (uint32_t)((((uint64_t)blockIdx.x * blockDim.x + threadIdx.x) * 16) % L);  // 64-bit remainder per thread, not per chunk
-  uint32_t pop = 0;
+  uint32_t pop = 0, ends = 0;
+  const int lane = lane_id();
   for (uint64_t g0 = (uint64_t)blockIdx.x * blockDim.x; g0 < n_chunks; g0 += T) {
     const uint64_t g = g0 + threadIdx.x, p0 = g * 16;
     uint32_t m16 = 0;
@@ -173,12 +223,25 @@ __global__ __launch_bounds__(256) void k_pack_solid_inv_fixed(const uint8_t *__r
     const unsigned long long v = join_4_lanes(m16);
     if ((threadIdx.x & 3) == 0 && g < n_chunks) words[g >> 2] = v;
     pop += (uint32_t)__builtin_popcount(m16);
+    // the run ends of the word on lane 4j: the bit before it is bit 15 of lane 4j - 1, the bit behind it bit 0 of lane 4j + 4
+    unsigned long long prev63 = (unsigned long long)(__shfl_up(m16, 1, kWave) >> 15) & 1ull, next0 = (unsigned long long)__shfl_down(m16, 4, kWave) & 1ull;
+    if (lane == 0) {  // ... of the wavefront before this one: position p0 - 1, at offset off - 1 of its read
+      const uint32_t o = off ? off - 1 : L - 1;
+      prev63 = g < n_chunks && p0 && p0 - 1 < n_bits && o + (uint32_t)k + 1 <= L && !(bytes[p0 - 1] & 1u) ? 1ull : 0ull;
+    }
+    if (lane == kWave - 4) {  // ... of the wavefront behind this one: position p0 + 64
+      const uint32_t o = (off + 64u) % L;
+      next0 = g < n_chunks && p0 + 64 < n_bits && o + (uint32_t)k + 1 <= L && !(bytes[p0 + 64] & 1u) ? 1ull : 0ull;
+    }
+    if ((lane & 3) == 0 && g < n_chunks) ends += run_end_items(v, prev63, next0);
     off += step;
     if (off >= L) off -= L;
   }
-  uint64_t tot;
+  uint64_t tot, tot_e;
   block_exclusive_sum<uint64_t, 256>((uint64_t)pop, sm, &tot);
+  block_exclusive_sum<uint64_t, 256>((uint64_t)ends, sm, &tot_e);
   if (threadIdx.x == 0 && tot) atomicAdd(n_solid, (unsigned long long)tot);
+  if (threadIdx.x == 0 && tot_e) atomicAdd(n_solid + kCtrRunEnds, (unsigned long long)tot_e);
 }
 
 // multi-GPU: the adopted slice holds the summed NON-solid marks of the local reads -> is_solid = valid & ~marked
@@ -440,6 +503,10 @@ struct S1Stage {
   uint2 *agg_items = nullptr;
   uint64_t *agg_cursor = nullptr;
   uint64_t agg_prev = 0, agg_bound = 0;
+  // digit histograms of stage 2's sort over the aggregated items, taken by the kernels that pack them (ws "s2_pre_hist"; nullptr: not taken)
+  unsigned long long *agg_hist = nullptr;
+  DigitSpecs agg_specs = no_digits();
+  uint64_t agg_hist_sig = 0;
   uint32_t seg_grid = 0, seg_cap = 0, seg_mcap = 0;
   uint32_t *seg_err = nullptr;
   int mark_mode = 0, mark_mode_used = 0;
@@ -519,11 +586,31 @@ struct S1Stage {
     const bool agg_continues = acc && c->agg_valid && c->agg_k == k && c->agg_m == m;
     c->agg_valid = false;
     agg_cursor = c->ws("s2_agg_cursor", 64).as<uint64_t>();
+    if (!c->agg_n_home.empty()) {  // (counts of an earlier stage: their copies have long run, but only a synchronisation says so)
+      MHX_HIP(hipStreamSynchronize(st));
+      c->agg_n_home.clear();
+    }
     agg_prev = agg_continues ? c->agg_n : 0;  // items of the earlier passes stay in front
     agg_bound = (n_items / m + 16) * 2;
+    // Stage 2 sorts exactly these items plus its '$' items when it takes them in place (s2.hip s2_agg_in_place): the kernels that pack
+    // them take the digit histograms of that sort.  A workspace of their own: the front of a later pass over a range of bins writes
+    // "sort_pre_hist" again.  Not when the items continue those of an earlier call (accumulate): the rows would be partial.
+    agg_hist = nullptr;
+    c->agg_hist_passes = 0;
+    if (agg && !global && !c->filter_on && !c->accumulate && agg_prev == 0 && c->opt("s2_pre_hist", 1) != 0) {
+      const std::vector<SortPass> ps = s2_agg_sort_passes(k);
+      if (!ps.empty() && ps.size() <= (size_t)kItemHistRows) {
+        agg_specs.n = (int)ps.size();
+        for (size_t p = 0; p < ps.size(); ++p) agg_specs.d[p] = spec_of_pass(ps[p], 2);
+        agg_hist_sig = passes_signature(ps);
+        agg_hist = c->ws("s2_pre_hist", (size_t)kItemHistRows * 256 * 8).as<unsigned long long>();
+        MHX_HIP(hipMemsetAsync(agg_hist, 0, (size_t)kItemHistRows * 256 * 8, st));
+      }
+    }
     seg_err = c->ws("s1_seg_err", 64).as<uint32_t>();
   }
   void agg_prepare_classic() {  // k_tile_groups appends to the dense array through a global cursor
+    agg_hist = nullptr;  // (... and takes no histograms)
     if (!agg) return;
     agg_items = grow_preserving(c, c->work["s2_agg_items"], (agg_prev + agg_bound) * 8, agg_prev * 8).as<uint2>();
     MHX_HIP(hipMemsetAsync(agg_cursor, 0, 24, st));
@@ -690,8 +777,8 @@ struct S1Stage {
       unsigned long long *dense = grow_preserving(c, c->work["s1_marks"], (marks_prev + seg_marks) * 8 + 64, marks_prev * 8).as<unsigned long long>();
       if (seg_marks)
         MHX_LAUNCH(c, "marks_compact", (double)seg_marks * 16,
-                   hipLaunchKernelGGL(k_agg_compact, dim3(seg_grid, 8), dim3(256), 0, st, reinterpret_cast<const uint2 *>(spare), seg_mcap,
-                                      c->work["s1_mark_counts"].as<uint32_t>(), reinterpret_cast<uint2 *>(dense + marks_prev), 0));
+                   agg_compact_launch(st, dim3(seg_grid, 8), reinterpret_cast<const uint2 *>(spare), seg_mcap,
+                                      c->work["s1_mark_counts"].as<uint32_t>(), reinterpret_cast<uint2 *>(dense + marks_prev), 0, no_digits(), nullptr));
       c->n_marks = marks_prev + seg_marks;
     }
     if (agg) {  // pack the workgroups' regions behind the items of the earlier passes
@@ -700,11 +787,10 @@ struct S1Stage {
       uint2 *dense = grow_preserving(c, c->work["s2_agg_items"], (agg_prev + total) * 8 + 64, agg_prev * 8).as<uint2>();
       if (total)
         MHX_LAUNCH(c, "agg_compact", (double)total * 16,
-                   hipLaunchKernelGGL(k_agg_compact, dim3(seg_grid, 8), dim3(256), 0, st, reinterpret_cast<const uint2 *>(spare), seg_cap,
-                                      c->work["s2_agg_counts"].as<uint32_t>(), dense + agg_prev, 1));
-      const uint64_t agg_n = agg_prev + total;
-      MHX_HIP(hipMemcpyAsync(agg_cursor, &agg_n, 8, hipMemcpyHostToDevice, st));
-      MHX_HIP(hipStreamSynchronize(st));  // agg_n is a stack variable
+                   agg_compact_launch(st, dim3(seg_grid, 8), reinterpret_cast<const uint2 *>(spare), seg_cap,
+                                      c->work["s2_agg_counts"].as<uint32_t>(), dense + agg_prev, 1, agg_specs, agg_hist));
+      c->agg_n_home.push_back(agg_prev + total);  // (a home that outlives this call: mhx_ctx)
+      MHX_HIP(hipMemcpyAsync(agg_cursor, &c->agg_n_home.back(), 8, hipMemcpyHostToDevice, st));
     }
     return 0;
   }
@@ -785,8 +871,8 @@ struct S1Stage {
       unsigned long long *dense = grow_preserving(c, c->work["s1_marks"], (marks_prev + seg_marks) * 8 + 64, marks_prev * 8).as<unsigned long long>();
       if (seg_marks)
         MHX_LAUNCH(c, "marks_compact", (double)seg_marks * 16,
-                   hipLaunchKernelGGL(k_agg_compact, dim3(seg_grid, 8), dim3(256), 0, st, reinterpret_cast<const uint2 *>(mraw), seg_mcap, mcounts,
-                                      reinterpret_cast<uint2 *>(dense + marks_prev), 0));
+                   agg_compact_launch(st, dim3(seg_grid, 8), reinterpret_cast<const uint2 *>(mraw), seg_mcap, mcounts,
+                                      reinterpret_cast<uint2 *>(dense + marks_prev), 0, no_digits(), nullptr));
       c->n_marks = marks_prev + seg_marks;
     }
     if (agg) {
@@ -797,11 +883,11 @@ struct S1Stage {
       uint2 *dense = grow_preserving(c, c->work["s2_agg_items"], std::max(agg_prev + total, expect) * 8 + 64, agg_prev * 8).as<uint2>();
       if (total)
         MHX_LAUNCH(c, "agg_compact", (double)total * 16,
-                   hipLaunchKernelGGL(k_agg_compact, dim3(seg_grid, 8), dim3(256), 0, st, reinterpret_cast<const uint2 *>(spare), seg_cap, counts, dense + agg_prev, 1));
-      const uint64_t agg_n = agg_prev + total;
-      MHX_HIP(hipMemcpyAsync(agg_cursor, &agg_n, 8, hipMemcpyHostToDevice, st));
-      MHX_HIP(hipStreamSynchronize(st));  // agg_n is a stack variable
-      agg_prev = agg_n;  // (the next pass over a range of bins appends)
+                   agg_compact_launch(st, dim3(seg_grid, 8), reinterpret_cast<const uint2 *>(spare), seg_cap, counts, dense + agg_prev, 1, agg_specs,
+                                      agg_hist));
+      c->agg_n_home.push_back(agg_prev + total);  // (a home that outlives this call: mhx_ctx)
+      MHX_HIP(hipMemcpyAsync(agg_cursor, &c->agg_n_home.back(), 8, hipMemcpyHostToDevice, st));
+      agg_prev = c->agg_n_home.back();  // (the next pass over a range of bins appends)
     }
     return true;
   }
@@ -810,7 +896,7 @@ struct S1Stage {
     if (!f.hp) return;
     uint2 *dense = nullptr;
     if (agg) dense = grow_preserving(c, c->work["s2_agg_items"], (agg_prev + 4) * 8 + 64, agg_prev * 8).as<uint2>();  // (room for two keys' items)
-    s1_skm_hp_publish(c, f, k, m, solid_bytes, hist, dense, agg_cursor, agg);
+    s1_skm_hp_publish(c, f, k, m, solid_bytes, hist, dense, agg_cursor, agg, &agg_specs, agg_hist);
   }
   void group_classic() {
     agg_prepare_classic();
@@ -826,6 +912,8 @@ struct S1Stage {
       c->agg_valid = true;
       c->agg_k = k;
       c->agg_m = m;
+      c->agg_hist_passes = agg_hist ? agg_specs.n : 0;
+      c->agg_hist_sig = agg_hist_sig;
     }
     if (sparse && classic_ran) {  // the classic kernel marked a byte map of the global read set: turn it into the list
       const uint64_t n_bytes = div_ceil(n_bits, 64) * 64;
@@ -845,7 +933,9 @@ struct S1Stage {
       MHX_LAUNCH(c, "count_solid", (double)n_words64 * 8,
                  hipLaunchKernelGGL(k_count_solid, dim3((unsigned)std::min<uint64_t>(div_ceil(n_words64, 256), 4096)), dim3(256), 0, st, is_solid, n_words64, ctr));
     c->global_marks_inverted = global && !mark_atomic;
-    if (n_words64 && !mark_atomic && mark_mode_used == 1 && !global) {
+    const bool bound_too = n_words64 && !mark_atomic && mark_mode_used == 1 && !global;  // (the kernels that also count stage 2's '$' items)
+    if (bound_too) {
+      MHX_HIP(hipMemsetAsync(ctr + kCtrRunEnds, 0, 8, st));
       if (s.fixed_len >= k + 16 && c->opt("s1_pack_fixed", 1))
         MHX_LAUNCH(c, "pack_solid", (double)n_words64 * 72,
                    hipLaunchKernelGGL(k_pack_solid_inv_fixed, dim3((unsigned)std::min<uint64_t>(div_ceil(n_words64 * 4, 256), 4096)), dim3(256), 0, st, solid_bytes, n_bits,
@@ -861,11 +951,13 @@ struct S1Stage {
                                     n_words64, ctr));
     uint64_t n_solid = 0, n_mercy = 0;
     {
-      unsigned long long h[2];
-      MHX_HIP(hipMemcpyAsync(h, ctr, 16, hipMemcpyDeviceToHost, st));
+      unsigned long long h[kCtrRunEnds + 1];
+      MHX_HIP(hipMemcpyAsync(h, ctr, sizeof h, hipMemcpyDeviceToHost, st));
       MHX_HIP(hipStreamSynchronize(st));
       n_solid = h[0];
       n_mercy = h[1];
+      c->s2_bound = h[kCtrRunEnds];
+      c->s2_bound_k = bound_too ? k : 0;
       if (want_mercy && (c->accumulate || c->filter_on)) {  // keep the candidates of every pass; publish their sorted union
         const uint64_t prev = acc ? c->mercy_acc_n : 0;
         DevBuf &ma = grow_preserving(c, c->work["mercy_acc"], (prev + n_mercy) * 8 + 8, prev * 8);
@@ -1184,8 +1276,8 @@ bool count_stream_groups(mhx_ctx *c, uint32_t k, uint32_t m, uint32_t *first_0_o
     unsigned long long *dense = c->ws("cs_events_dense", (o->n_events + n_look) * 8 + 64).as<unsigned long long>();
     if (o->n_events)
       MHX_LAUNCH(c, "events_compact", (double)o->n_events * 16,
-                 hipLaunchKernelGGL(k_agg_compact, dim3(grid, 8), dim3(256), 0, st, reinterpret_cast<const uint2 *>(a.marks_raw), ecap, ecounts,
-                                    reinterpret_cast<uint2 *>(dense), 0));
+                 agg_compact_launch(st, dim3(grid, 8), reinterpret_cast<const uint2 *>(a.marks_raw), ecap, ecounts,
+                                    reinterpret_cast<uint2 *>(dense), 0, no_digits(), nullptr));
     if (n_look) MHX_HIP(hipMemcpyAsync(dense + o->n_events, a.giant.ev, (size_t)n_look * 8, hipMemcpyDeviceToDevice, st));
     o->n_events += n_look;
     o->events = dense;

@@ -17,6 +17,8 @@
 
 namespace mhx {
 
+constexpr int kCtrRunEnds = 5;  // slot of ws "s1_counters" where the k_pack_solid_inv kernels leave stage 2's bound of '$' items (s1.hip)
+
 // COMPACT (no mercy requested): the aux part is one word, the absolute position of the (k-1)-mer; that is
 // all the group reduction needs to set is_solid, and it makes the record 12 instead of 16 bytes at k <= 29.
 // item of slot j (0 .. L-k+3) of the read at base offset st, length L (read_to_sdbg_s1.cpp:228-292, :344-363)

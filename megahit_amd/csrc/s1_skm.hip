@@ -392,7 +392,8 @@ __global__ __launch_bounds__(NT) void k_skm_make(const uint32_t *__restrict__ se
 // the one or two keys the homopolymer windows are (A...A with T...T, C...C with G...G): histogram, the mark of a key seen once, the
 // aggregated stage-2 items of a solid one, behind the items of the group-by — as the walk over the table does for every other key
 __global__ void k_skm_hp_publish(const unsigned long long *__restrict__ hp, int k, uint32_t m, uint8_t *__restrict__ solid_bytes,
-                                 unsigned long long *__restrict__ hist, uint2 *__restrict__ agg_items, uint64_t *__restrict__ agg_cursor, int agg) {
+                                 unsigned long long *__restrict__ hist, uint2 *__restrict__ agg_items, uint64_t *__restrict__ agg_cursor, int agg,
+                                 DigitSpecs agg_specs, unsigned long long *__restrict__ agg_hist) {
   if (threadIdx.x || blockIdx.x) return;
   for (int x = 0; x < 2; ++x) {
     const unsigned long long cnt = hp[x];
@@ -411,6 +412,10 @@ __global__ void k_skm_hp_publish(const unsigned long long *__restrict__ hp, int 
         const uint64_t v = xs[y];
         const uint64_t f = ((v << 2) & mask_k) | (1ull << 19) | ((v >> 62) << 16) | hb;
         agg_items[at++] = make_uint2((uint32_t)(f >> 32), (uint32_t)f);
+        if (agg_hist) {  // the digit histograms of stage 2's sort (k_agg_compact took those of the items before these)
+          const uint32_t w[2] = {(uint32_t)(f >> 32), (uint32_t)f};
+          for (int p = 0; p < agg_specs.n; ++p) atomicAdd(&agg_hist[p * 256 + words_digit2<2>(w, agg_specs.d[p])], 1ull);
+        }
       }
       *agg_cursor = at;
     }
@@ -1651,10 +1656,13 @@ void count_skm_hp_publish(mhx_ctx *c, const unsigned long long *hp, uint32_t k, 
 
 // the homopolymer keys counted by k_skm_make -> histogram, mark or aggregated items (after the last pass of the group-by)
 void s1_skm_hp_publish(mhx_ctx *c, const SkmFront &f, uint32_t k, uint32_t m, uint8_t *solid_bytes, unsigned long long *hist, uint2 *agg_items,
-                       uint64_t *agg_cursor, bool agg) {
+                       uint64_t *agg_cursor, bool agg, const DigitSpecs *agg_specs, unsigned long long *agg_hist) {
   if (!f.hp) return;
+  DigitSpecs specs;
+  specs.n = 0;
+  if (agg_specs && agg_hist) specs = *agg_specs;
   MHX_LAUNCH(c, "s1_skm_hp", 64.0, hipLaunchKernelGGL(k_skm_hp_publish, dim3(1), dim3(64), 0, c->stream, f.hp, (int)k, m, solid_bytes, hist, agg_items, agg_cursor,
-                                                       agg ? 1 : 0));
+                                                       agg ? 1 : 0, specs, agg_specs ? agg_hist : nullptr));
 }
 
 // several GPUs: where the bins start in an array of records ordered by bin (a source of the owner's group-by)

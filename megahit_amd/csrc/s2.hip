@@ -12,6 +12,7 @@
 //   bucket_stats            per-bucket starting offset / item / tip / large counts (sdbg_meta.h:22-34)
 #include "dev_prims.h"
 #include "mhx_internal.h"
+#include "sort_digits.h"
 #include "tile_groups.h"
 
 namespace mhx {
@@ -269,8 +270,143 @@ __global__ __launch_bounds__(256) void k_s2d_bound(const unsigned long long *__r
   if (threadIdx.x == 0 && tot) atomicAdd(total, (unsigned long long)tot);
 }
 constexpr int kS2dWords = 8;
-// emission in arbitrary order (the items are sorted next): per block one atomicAdd on the output cursor
+constexpr int kS2dList = 4096;                 // run ends the LDS list of a trip holds (16 KB; 2 540 per trip at bench.py's library)
+constexpr int kS2dGroup = 3;                   // rounds of 256 list entries whose gathers a lane has in flight together
+// Emission in arbitrary order (the items are sorted next).  Per trip of a workgroup (256 x kS2dWords bitmap words): phase 1 compacts the
+// run ends of the trip into an LDS list (bit position within the trip | left flag << 17 | right flag << 18), phase 2 deals the list to the
+// lanes 256 entries at a time, so that a lane has the gathers of kS2dGroup run ends in flight at once instead of one after the other: a
+// sweep that counts the items (the palindrome test, once), one scan over the lanes' counts and one atomicAdd on the output cursor per
+// list, then a sweep that gathers again (cache) and stores (a trip with more run ends than the list holds is worked off in list-sized pieces; list_cap shrinks it for the tests).
+// hist != nullptr: the digit histograms of the sort's passes (specs) are taken from the items in registers.  A list whose items would
+// end beyond items_cap (the bound they were given room for) raises *err instead of being written.
 __global__ __launch_bounds__(256) void k_s2d_emit(const uint32_t *__restrict__ seq, const uint64_t *__restrict__ start, uint64_t n_seqs,
+                                                  uint32_t fixed_len, int k, const unsigned long long *__restrict__ solid, uint64_t n_words,
+                                                  uint2 *__restrict__ items, unsigned long long *__restrict__ cursor, int fsh, int bsh, int csh,
+                                                  uint32_t list_cap, DigitSpecs specs, unsigned long long *__restrict__ hist,
+                                                  unsigned long long items_cap, uint32_t *__restrict__ err) {
+  // (fsh / bsh / csh: where the "full" flag, the W char and the count sit below the chars: 19 / 16 / 0 in the seq2sdbg layout of the
+  //  aggregated items of k <= 22, cb + 3 / cb / 0 with the cb = 60 - 2k count bits of k = 23..28)
+  __shared__ uint32_t s_list[kS2dList];
+  __shared__ uint32_t sm[256 / kWave + 1];
+  __shared__ unsigned long long s_base;
+  __shared__ uint32_t s_hist[kItemHistRows][256];
+  if (hist) {
+    for (int i = threadIdx.x; i < kItemHistRows * 256; i += 256) (&s_hist[0][0])[i] = 0;
+    __syncthreads();
+  }
+  const ItemDigits digits(specs);
+  const uint64_t mask_k = ~0ull << (64 - 2 * k), mask_k1 = ~0ull << (64 - 2 * (k - 1));
+  for (uint64_t blk = blockIdx.x; blk * (256ull * kS2dWords) < n_words; blk += gridDim.x) {
+    const uint64_t w_base = blk * (256ull * kS2dWords);
+    unsigned long long ls[kS2dWords], rs[kS2dWords];
+    uint32_t cnt = 0;
+#pragma unroll
+    for (int q = 0; q < kS2dWords; ++q) {
+      const uint64_t i = w_base + (uint64_t)q * 256 + threadIdx.x;
+      ls[q] = rs[q] = 0;
+      if (i < n_words) s2d_run_ends(solid, i, n_words, &ls[q], &rs[q]);
+      cnt += (uint32_t)__builtin_popcountll(ls[q] | rs[q]);
+    }
+    uint32_t tot;
+    const uint32_t first = block_exclusive_sum<uint32_t, 256>(cnt, sm, &tot);
+    for (uint32_t pb = 0; pb < tot; pb += list_cap) {
+      const uint32_t n = min(list_cap, tot - pb);
+      // phase 1: entries [pb, pb + n) of the trip into the list
+      if (first < pb + n && first + cnt > pb) {
+        uint32_t idx = first - pb;  // (wraps below pb: the test against n drops those)
+#pragma unroll
+        for (int q = 0; q < kS2dWords; ++q) {
+          const unsigned long long l = ls[q], r = rs[q];
+          const uint32_t at = (uint32_t)(q * 256 + threadIdx.x) * 64u;
+          for (unsigned long long cand = l | r; cand; cand &= cand - 1) {
+            const int b = __builtin_ctzll(cand);
+            if (idx < n) s_list[idx] = (at + (uint32_t)b) | ((uint32_t)((l >> b) & 1ull) << 17) | ((uint32_t)((r >> b) & 1ull) << 18);
+            ++idx;
+          }
+        }
+      }
+      __syncthreads();
+      // phase 2: one end per lane and round, kS2dGroup rounds' gathers in flight together.  First the item counts (the palindrome test's
+      // outcome goes into bit 19 of the lane's own entries), then, behind the scan, the items.
+      const uint64_t fo_base = w_base * 64;
+      uint32_t c = 0;
+      for (uint32_t j0 = 0; j0 * 256 < n; j0 += kS2dGroup) {
+        uint32_t ent[kS2dGroup];
+        uint64_t es[kS2dGroup];
+#pragma unroll
+        for (int g = 0; g < kS2dGroup; ++g) {
+          const uint32_t idx = (j0 + g) * 256 + threadIdx.x;
+          ent[g] = idx < n ? s_list[idx] : 0u;  // (no flags: no items; its gather reads the trip's first position)
+        }
+#pragma unroll
+        for (int g = 0; g < kS2dGroup; ++g) {
+          uint32_t w[2];
+          load_chars<2>(seq, fo_base + (ent[g] & 0x1FFFFu), k + 1, w);
+          es[g] = ((uint64_t)w[0] << 32) | w[1];
+        }
+#pragma unroll
+        for (int g = 0; g < kS2dGroup; ++g) {
+          const uint32_t ends = ((ent[g] >> 17) & 1u) + ((ent[g] >> 18) & 1u);
+          const bool pal = es[g] == rc64_s2(es[g], k + 1);  // (palindromes emit the forward item only)
+          c += ends * (pal ? 1u : 2u);
+          if (pal && ends) s_list[(j0 + g) * 256 + threadIdx.x] = ent[g] | (1u << 19);
+        }
+      }
+      uint32_t n_out;
+      const uint32_t excl = block_exclusive_sum<uint32_t, 256>(c, sm, &n_out);
+      if (threadIdx.x == 0) s_base = n_out ? atomicAdd(cursor, (unsigned long long)n_out) : 0ull;
+      __syncthreads();
+      uint2 *dst = items + s_base + excl;
+      const bool fits = s_base + n_out <= items_cap;  // (workgroup-uniform)
+      if (!fits && threadIdx.x == 0) atomicOr(err, 1u);
+      for (uint32_t j0 = 0; fits && j0 * 256 < n; j0 += kS2dGroup) {
+        uint32_t ent[kS2dGroup];
+        uint64_t es[kS2dGroup];
+#pragma unroll
+        for (int g = 0; g < kS2dGroup; ++g) {
+          const uint32_t idx = (j0 + g) * 256 + threadIdx.x;
+          ent[g] = idx < n ? s_list[idx] : 0u;
+        }
+#pragma unroll
+        for (int g = 0; g < kS2dGroup; ++g) {
+          uint32_t w[2];
+          load_chars<2>(seq, fo_base + (ent[g] & 0x1FFFFu), k + 1, w);
+          es[g] = ((uint64_t)w[0] << 32) | w[1];
+        }
+#pragma unroll
+        for (int g = 0; g < kS2dGroup; ++g) {
+          if (!(ent[g] & (3u << 17))) continue;
+          const uint64_t e = es[g], er = rc64_s2(e, k + 1);
+          const bool pal = (ent[g] >> 19) & 1u;
+          auto put = [&](uint64_t key, uint64_t full, uint64_t wc) {
+            const uint64_t v = key | (full << fsh) | (wc << bsh) | (1ull << csh);
+            *dst++ = make_uint2((uint32_t)(v >> 32), (uint32_t)v);
+            if (hist) item_hist_add(s_hist, digits, v);
+          };
+          if ((ent[g] >> 17) & 1u) {                                       // left-$ (read_to_sdbg_s2.cpp:387-396, :457-512)
+            put(e & mask_k, 1, kSentinel);                                 //   fwd: e[0..k-1], W = $
+            if (!pal) put((er << 4) & mask_k1, 0, (er >> 60) & 3u);        //   rc : e'[2..k],  W = e'[1]
+          }
+          if ((ent[g] >> 18) & 1u) {                                       // right-$ (:411-425)
+            put((e << 4) & mask_k1, 0, (e >> 60) & 3u);                    //   fwd: e[2..k],   W = e[1]
+            if (!pal) put(er & mask_k, 1, kSentinel);                      //   rc : e'[0..k-1], W = $
+          }
+        }
+      }
+      __syncthreads();  // (the next list is written behind the last read of this one)
+    }
+  }  // blk
+  if (hist) {
+    __syncthreads();
+    item_hist_flush(s_hist, digits, hist);
+  }
+  (void)start;
+  (void)n_seqs;
+  (void)fixed_len;
+}
+// The per-thread walk (s2_dummy_list = 0): a thread goes through the run ends of its own words one after the other, twice — chains of
+// dependent gathers.  Kept for the A/B against k_s2d_emit.
+__global__ __launch_bounds__(256) void k_s2d_emit_walk(const uint32_t *__restrict__ seq, const uint64_t *__restrict__ start, uint64_t n_seqs,
                                                   uint32_t fixed_len, int k, const unsigned long long *__restrict__ solid, uint64_t n_words,
                                                   uint2 *__restrict__ items, unsigned long long *__restrict__ cursor, int fsh = 19, int bsh = 16, int csh = 0) {
   // (fsh / bsh / csh: where the "full" flag, the W char and the count sit below the chars: 19 / 16 / 0 in the seq2sdbg layout of the
@@ -1303,41 +1439,80 @@ int s2_process(mhx_ctx *c, uint32_t k, uint32_t *buf_a, uint32_t *buf_b, uint64_
   return 0;
 }
 
+// Upper bound of the '$' items of the bitmap `solid` (exact unless palindromes occur).  from_s1: it is stage 1's own bitmap of (k, m), whose
+// pack kernel summed the same figure (mhx_ctx::s2_bound) — no kernel, no copy, no host round trip; else k_s2d_bound into cur[1].
+static uint64_t s2d_bound(mhx_ctx *c, uint32_t k, uint32_t m, const unsigned long long *solid, uint64_t n_words, unsigned long long *cur, bool from_s1) {
+  if (!n_words) return 0;
+  const long long mode = c->opt("s2_bound_from_s1", 1);  // (2: both, and they must agree — tests)
+  const bool cached = from_s1 && mode != 0 && c->solid_plain_k == k && c->solid_plain_m == m && c->s2_bound_k == k;
+  if (cached && mode != 2) return c->s2_bound;
+  hipStream_t st = c->stream;
+  uint64_t bound = 0;
+  MHX_LAUNCH(c, "s2_bound", (double)n_words * 8,
+             hipLaunchKernelGGL(k_s2d_bound, dim3((unsigned)std::min<uint64_t>(div_ceil(n_words, 256), 2048)), dim3(256), 0, st, solid, n_words, cur + 1));
+  MHX_HIP(hipMemcpyAsync(&bound, cur + 1, 8, hipMemcpyDeviceToHost, st));
+  MHX_HIP(hipStreamSynchronize(st));
+  if (cached && bound != c->s2_bound)
+    throw Error("read2sdbg_s2: stage 1 counted " + std::to_string(c->s2_bound) + " '$' items at the run ends of its bitmap, the bitmap holds " + std::to_string(bound));
+  return bound;
+}
+// The '$' items of the run ends of `solid` (n_words bitmap words), written to dst (room for the bound of k_s2d_bound); -> their number.
+// cur: the zeroed 64-byte cursor block (word 0: the cursor, word 4: the kernel's error flag).  hist: the digit histograms of `specs` are added up there (k_s2d_emit's list form only).
+static uint64_t s2d_emit_items(mhx_ctx *c, uint32_t k, const unsigned long long *solid, uint64_t n_words, uint64_t bound, uint2 *dst, unsigned long long *cur,
+                               int fsh = 19, int bsh = 16, int csh = 0, const DigitSpecs *specs = nullptr, unsigned long long *hist = nullptr) {
+  if (!bound) return 0;
+  SeqSet &s = c->seqs;
+  hipStream_t st = c->stream;
+  const uint64_t trips = div_ceil(n_words, 256 * kS2dWords);
+  dim3 grid((unsigned)std::min<uint64_t>(trips, 4096));
+  if (c->opt("s2_dummy_list", 1) != 0) {
+    // (every workgroup ends with up to 256 global atomics per histogram row: no more of them than the device holds at once, 5 per CU)
+    grid.x = (unsigned)std::min<uint64_t>(trips, (uint64_t)(c->n_cus > 0 ? c->n_cus : 256) * 5);
+    const long long cap = c->opt("s2_dummy_list_cap", 0);
+    const uint32_t list_cap = cap > 0 ? (uint32_t)std::min<long long>(cap, kS2dList) : (uint32_t)kS2dList;
+    const DigitSpecs none{};
+    if (!specs || specs->n > kItemHistRows) hist = nullptr;
+    MHX_LAUNCH(c, "s2_extract", (double)bound * 8 + (double)n_words * 8,
+               hipLaunchKernelGGL(k_s2d_emit, grid, dim3(256), 0, st, s.words.as<uint32_t>(), s.start.as<uint64_t>(), s.n_seqs, s.fixed_len, (int)k, solid, n_words, dst,
+                                  cur, fsh, bsh, csh, list_cap, hist ? *specs : none, hist, (unsigned long long)bound, reinterpret_cast<uint32_t *>(cur + 4)));
+  } else {
+    if (hist) throw Error("read2sdbg_s2: the per-thread walk takes no digit histograms");
+    MHX_LAUNCH(c, "s2_extract", (double)bound * 8 + (double)n_words * 8,
+               hipLaunchKernelGGL(k_s2d_emit_walk, grid, dim3(256), 0, st, s.words.as<uint32_t>(), s.start.as<uint64_t>(), s.n_seqs, s.fixed_len, (int)k, solid, n_words,
+                                  dst, cur, fsh, bsh, csh));
+  }
+  unsigned long long h_cur[5] = {0, 0, 0, 0, 0};
+  MHX_HIP(hipMemcpyAsync(h_cur, cur, sizeof h_cur, hipMemcpyDeviceToHost, st));
+  MHX_HIP(hipStreamSynchronize(st));
+  if ((h_cur[4] & 0xFFFFFFFFull) || h_cur[0] > bound) throw Error("read2sdbg_s2: more '$' items than their bound");
+  return h_cur[0];
+}
 // aggregated stage 2 (k <= 22): solid items from stage 1 + dummy items from the local reads -> ws "items_a"
 uint64_t s2_agg_extract(mhx_ctx *c, uint32_t k) {
   SeqSet &s = c->seqs;
   hipStream_t st = c->stream;
-  const uint64_t ns = s.n_seqs, n_agg = c->agg_n;
+  const uint64_t n_agg = c->agg_n;
   auto it = c->results.find(c->global_bases ? MHX_BUF_IS_SOLID_LOCAL : MHX_BUF_IS_SOLID);
   if (it == c->results.end() || it->second.used < div_ceil(s.n_bases, 64) * 8) throw Error("read2sdbg_s2: no is_solid bitmap");
   const unsigned long long *solid = it->second.as<unsigned long long>();
   const uint64_t n_words = div_ceil(s.n_bases, 64);
   unsigned long long *cur = c->ws("s2d_cursor", 64).as<unsigned long long>();
-  MHX_HIP(hipMemsetAsync(cur, 0, 16, st));
-  uint64_t bound = 0;
-  if (n_words) {
-    MHX_LAUNCH(c, "s2_bound", (double)n_words * 8,
-               hipLaunchKernelGGL(k_s2d_bound, dim3((unsigned)std::min<uint64_t>(div_ceil(n_words, 256), 2048)), dim3(256), 0, st, solid, n_words, cur + 1));
-    MHX_HIP(hipMemcpyAsync(&bound, cur + 1, 8, hipMemcpyDeviceToHost, st));
-    MHX_HIP(hipStreamSynchronize(st));
-  }
+  MHX_HIP(hipMemsetAsync(cur, 0, 64, st));
+  const uint64_t bound = s2d_bound(c, k, c->agg_m, solid, n_words, cur, !c->global_bases);
   uint32_t *buf_a = c->ws("items_a", (n_agg + bound) * 8 + 64).as<uint32_t>();
   if (n_agg) MHX_HIP(hipMemcpyAsync(buf_a, c->work["s2_agg_items"].p, n_agg * 8, hipMemcpyDeviceToDevice, st));
-  uint64_t n_dummy = 0;
-  if (bound) {
-    MHX_LAUNCH(c, "s2_extract", (double)bound * 8 + (double)n_words * 8,
-               hipLaunchKernelGGL(k_s2d_emit, dim3((unsigned)std::min<uint64_t>(div_ceil(n_words, 256 * kS2dWords), 4096)), dim3(256), 0, st, s.words.as<uint32_t>(),
-                                  s.start.as<uint64_t>(), ns, s.fixed_len, (int)k, solid, n_words, reinterpret_cast<uint2 *>(buf_a) + n_agg, cur));
-    MHX_HIP(hipMemcpyAsync(&n_dummy, cur, 8, hipMemcpyDeviceToHost, st));
-    MHX_HIP(hipStreamSynchronize(st));
-  }
+  const uint64_t n_dummy = s2d_emit_items(c, k, solid, n_words, bound, reinterpret_cast<uint2 *>(buf_a) + n_agg, cur);
   const uint64_t n_items = n_agg + n_dummy;
   return n_items;
 }
-// sort by k-mer chars, "full" flag and W (the count bits [0,16) ride along), then emit
-int s2_agg_process(mhx_ctx *c, uint32_t k, uint32_t *buf_a, uint32_t *buf_b, uint64_t n_items, mhx_sdbg_result *out) {
+std::vector<SortPass> s2_agg_sort_passes(uint32_t k, int count_bits) {
+  return make_passes_ranges(2, {{count_bits, count_bits + 4}, {64 - 2 * (int)k, 64}});
+}
+// sort by k-mer chars, "full" flag and W (the count bits [0,16) ride along), then emit.  prep: what the producers of exactly these items
+// left for the sort (their digit histograms)
+int s2_agg_process(mhx_ctx *c, uint32_t k, uint32_t *buf_a, uint32_t *buf_b, uint64_t n_items, mhx_sdbg_result *out, SortPrep *prep) {
   // (the whole-key order also orders equal keys by their count bits: the emission sums them, any order does)
-  uint32_t *sorted = sort_whole_key(c, buf_a, buf_b, n_items, 2, 2, make_passes_ranges(2, {{16, 20}, {64 - 2 * (int)k, 64}}));
+  uint32_t *sorted = sort_whole_key(c, buf_a, buf_b, n_items, 2, 2, s2_agg_sort_passes(k), prep);
   emit_sdbg(c, sorted, n_items, 2, 2, k, 2, out);
   return 0;
 }
@@ -1476,14 +1651,8 @@ static bool s2_agg_from_count(mhx_ctx *c, uint32_t k, uint32_t m, mhx_sdbg_resul
     solid = v;
   }
   unsigned long long *cur = c->ws("s2d_cursor", 64).as<unsigned long long>();
-  MHX_HIP(hipMemsetAsync(cur, 0, 32, st));
-  uint64_t bound = 0;
-  if (n_words) {
-    MHX_LAUNCH(c, "s2_bound", (double)n_words * 8,
-               hipLaunchKernelGGL(k_s2d_bound, dim3((unsigned)std::min<uint64_t>(div_ceil(n_words, 256), 2048)), dim3(256), 0, st, solid, n_words, cur + 1));
-    MHX_HIP(hipMemcpyAsync(&bound, cur + 1, 8, hipMemcpyDeviceToHost, st));
-    MHX_HIP(hipStreamSynchronize(st));
-  }
+  MHX_HIP(hipMemsetAsync(cur, 0, 64, st));
+  const uint64_t bound = s2d_bound(c, k, m, solid, n_words, cur, m > 1);
   // 3. items: per edge and strand ceil(multiplicity / cmax) of them, then the dummies.  (The edge regions live in the count's spare sort
   //    buffer "items_a" / "items_b": the items get buffers of their own.)
   const uint64_t items_cap = 2 * (n_edges + o.n_items / cmax + 1);
@@ -1498,18 +1667,11 @@ static bool s2_agg_from_count(mhx_ctx *c, uint32_t k, uint32_t m, mhx_sdbg_resul
   MHX_HIP(hipStreamSynchronize(st));
   if (h_cur[3] & 0xFFFFFFFFull) throw Error("read2sdbg_s2: more aggregated items than their bound");
   const uint64_t n_agg = h_cur[2];
-  uint64_t n_dummy = 0;
-  if (bound) {
-    MHX_LAUNCH(c, "s2_extract", (double)bound * 8 + (double)n_words * 8,
-               hipLaunchKernelGGL(k_s2d_emit, dim3((unsigned)std::min<uint64_t>(div_ceil(n_words, 256 * kS2dWords), 4096)), dim3(256), 0, st, s.words.as<uint32_t>(),
-                                  s.start.as<uint64_t>(), ns, s.fixed_len, (int)k, solid, n_words, reinterpret_cast<uint2 *>(buf_a) + n_agg, cur, fsh, bsh, csh));
-    MHX_HIP(hipMemcpyAsync(&n_dummy, cur, 8, hipMemcpyDeviceToHost, st));
-    MHX_HIP(hipStreamSynchronize(st));
-  }
+  const uint64_t n_dummy = s2d_emit_items(c, k, solid, n_words, bound, reinterpret_cast<uint2 *>(buf_a) + n_agg, cur, fsh, bsh, csh);
   const uint64_t n_items = n_agg + n_dummy;
   uint32_t *buf_b = c->ws("s2c_items_b", n_items * 8 + 64).as<uint32_t>();
   // 4. sort by chars, flag and W (the count bits ride along), emit
-  uint32_t *sorted = sort_whole_key(c, buf_a, buf_b, n_items, 2, 2, make_passes_ranges(2, {{cbits, cbits + 4}, {64 - 2 * (int)k, 64}}));
+  uint32_t *sorted = sort_whole_key(c, buf_a, buf_b, n_items, 2, 2, s2_agg_sort_passes(k, cbits));
   emit_sdbg(c, sorted, n_items, 2, 2, k, 2, out, cb);
   c->last_s1_plan = "stage 2 from a count of the (k+1)-mers: " + o.plan;
   return true;
@@ -1528,27 +1690,36 @@ static int s2_agg_in_place(mhx_ctx *c, uint32_t k, mhx_sdbg_result *out) {
   const unsigned long long *solid = it->second.as<unsigned long long>();
   const uint64_t n_words = div_ceil(s.n_bases, 64);
   unsigned long long *cur = c->ws("s2d_cursor", 64).as<unsigned long long>();
-  MHX_HIP(hipMemsetAsync(cur, 0, 16, st));
-  uint64_t bound = 0;
-  if (n_words) {
-    MHX_LAUNCH(c, "s2_bound", (double)n_words * 8,
-               hipLaunchKernelGGL(k_s2d_bound, dim3((unsigned)std::min<uint64_t>(div_ceil(n_words, 256), 2048)), dim3(256), 0, st, solid, n_words, cur + 1));
-    MHX_HIP(hipMemcpyAsync(&bound, cur + 1, 8, hipMemcpyDeviceToHost, st));
-    MHX_HIP(hipStreamSynchronize(st));
-  }
+  MHX_HIP(hipMemsetAsync(cur, 0, 64, st));
+  const uint64_t bound = s2d_bound(c, k, c->agg_m, solid, n_words, cur, true);
   uint32_t *buf_a = grow_preserving(c, c->work["s2_agg_items"], (n_agg + bound) * 8 + 64, n_agg * 8).as<uint32_t>();
-  uint64_t n_dummy = 0;
-  if (bound) {
-    MHX_LAUNCH(c, "s2_extract", (double)bound * 8 + (double)n_words * 8,
-               hipLaunchKernelGGL(k_s2d_emit, dim3((unsigned)std::min<uint64_t>(div_ceil(n_words, 256 * kS2dWords), 4096)), dim3(256), 0, st, s.words.as<uint32_t>(),
-                                  s.start.as<uint64_t>(), s.n_seqs, s.fixed_len, (int)k, solid, n_words, reinterpret_cast<uint2 *>(buf_a) + n_agg, cur));
-    MHX_HIP(hipMemcpyAsync(&n_dummy, cur, 8, hipMemcpyDeviceToHost, st));
-    MHX_HIP(hipStreamSynchronize(st));
+  // Stage 1 took the digit histograms of this sort over its n_agg items where it packed them (ws "s2_pre_hist", for exactly this k and
+  // this pass plan); k_s2d_emit adds those of the '$' items, and the sort reads no histogram of its own.  Anything that does not match:
+  // the sort takes them itself.
+  const std::vector<SortPass> passes = s2_agg_sort_passes(k);
+  DigitSpecs specs{};
+  unsigned long long *pre_hist = nullptr;
+  if (c->opt("s2_pre_hist", 1) != 0 && c->opt("s2_dummy_list", 1) != 0 && c->agg_hist_passes == (int)passes.size() && c->agg_hist_passes <= kItemHistRows &&
+      c->agg_hist_sig == passes_signature(passes) && c->work.count("s2_pre_hist")) {
+    pre_hist = c->work["s2_pre_hist"].as<unsigned long long>();
+    specs.n = (int)passes.size();
+    for (int p = 0; p < specs.n; ++p) specs.d[p] = spec_of_pass(passes[p], 2);
   }
+  // (from here on the items are being consumed, and the rows count '$' items too: a call that fails below leaves nothing that claims otherwise)
+  c->agg_valid = false;
+  c->agg_hist_passes = 0;
+  const uint64_t n_dummy = s2d_emit_items(c, k, solid, n_words, bound, reinterpret_cast<uint2 *>(buf_a) + n_agg, cur, 19, 16, 0, &specs, pre_hist);
   const uint64_t n_items = n_agg + n_dummy;
   uint32_t *buf_b = c->ws("items_b", n_items * 8 + 64).as<uint32_t>();
-  c->agg_valid = false;
-  return s2_agg_process(c, k, buf_a, buf_b, n_items, out);
+  SortPrep prep;
+  if (pre_hist) {
+    prep.buf = buf_a;
+    prep.n = n_items;
+    prep.hist_passes = specs.n;
+    prep.hist_sig = passes_signature(passes);
+    prep.hist = pre_hist;
+  }
+  return s2_agg_process(c, k, buf_a, buf_b, n_items, out, &prep);
 }
 
 int run_s2(mhx_ctx *c, uint32_t k, uint32_t m, mhx_sdbg_result *out) {

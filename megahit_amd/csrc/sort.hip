@@ -338,8 +338,8 @@ static uint32_t *radix_sort_onesweep(mhx_ctx *c, uint32_t *a, uint32_t *b, uint6
   if (gen && !pre) throw Error("radix sort: a generated first pass needs the digit histograms of the plan (pre-hist)");
   if (split && !pre) throw Error("radix sort: a split first pass needs the digit histograms of the plan (pre-hist)");
   if (pre)
-    MHX_HIP(hipMemcpyAsync(gh, static_cast<const unsigned long long *>(c->work["sort_pre_hist"].p) + (size_t)prep.hist_first * 256, (size_t)P * 256 * 8,
-                           hipMemcpyDeviceToDevice, st));
+    MHX_HIP(hipMemcpyAsync(gh, (prep.hist ? prep.hist : static_cast<const unsigned long long *>(c->work["sort_pre_hist"].p)) + (size_t)prep.hist_first * 256,
+                           (size_t)P * 256 * 8, hipMemcpyDeviceToDevice, st));
   for (int p0 = 0; p0 < P && !pre; p0 += kMaxFusedPasses) {  // one read of the input per 16 passes
     DigitSpecs specs;
     specs.n = std::min(kMaxFusedPasses, P - p0);
