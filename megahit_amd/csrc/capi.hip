@@ -138,7 +138,7 @@ void upload_sequences(mhx_ctx *c, const uint32_t *packed, uint64_t n_words, uint
                       const uint64_t *start_pos) {
   SeqSet &s = c->seqs;
   hipStream_t st = c->stream;
-  c->agg_valid = false; c->agg_hist_passes = 0; c->solid_plain_k = 0;
+  c->s1.drop();
   s.n_seqs = n_seqs;
   s.fixed_len = start_pos ? 0 : fixed_len;
   s.n_words = n_words;
@@ -204,7 +204,7 @@ void append_sequences(mhx_ctx *c, const uint32_t *packed, uint64_t n_words, uint
                       const uint16_t *mult) {
   SeqSet &s = c->seqs;
   hipStream_t st = c->stream;
-  c->agg_valid = false; c->agg_hist_passes = 0; c->solid_plain_k = 0;
+  c->s1.drop();
   if (n_new == 0) return;
   const uint64_t add_bases = start_pos ? start_pos[n_new] : n_new * (uint64_t)fixed_len;
   if (add_bases > n_words * 16) throw Error("append_sequences: start_pos/n_seqs exceed the packed buffer");
@@ -306,7 +306,7 @@ __global__ void k_unpack_edges(const uint32_t *__restrict__ raw, uint64_t n_edge
 void upload_edges(mhx_ctx *c, const uint32_t *raw, uint64_t n_edges, uint32_t k, uint32_t wpe) {
   hipStream_t st = c->stream;
   SeqSet &s = c->seqs;
-  c->agg_valid = false; c->agg_hist_passes = 0; c->solid_plain_k = 0;
+  c->s1.drop();
   const uint32_t len = k + 1;
   if (wpe != (len * 2 + 16 + 31) / 32) throw Error("load_edges: words_per_edge does not match k");
   uint32_t *d_raw = c->ws("edges_raw", (n_edges * wpe + 4) * 4).as<uint32_t>();
@@ -437,7 +437,7 @@ static bool upload_bin_records_fixed(mhx_ctx *c, const uint32_t *records, uint64
 }
 
 void upload_bin_records(mhx_ctx *c, const uint32_t *records, uint64_t n_words, uint64_t n_seqs, int reverse) {
-  c->agg_valid = false; c->agg_hist_passes = 0; c->solid_plain_k = 0;
+  c->s1.drop();
   if (upload_bin_records_fixed(c, records, n_words, n_seqs, reverse)) return;
   // lengths (host): an empty read becomes a 1-base 'A' (sequence_package.h:275-281)
   std::vector<uint64_t> rec_off(n_seqs + 1), start(n_seqs + 1);
@@ -558,7 +558,7 @@ int mhx_trim(mhx_ctx *c) {
     // (stage 1's aggregated stage-2 items are state that the next stage 2 reads, not scratch: they stay while they are valid; a bucket
     // filter's tables go, and the filter with them)
     for (auto it = c->work.begin(); it != c->work.end();) {
-      if (c->agg_valid && it->first == "s2_agg_items") {
+      if (c->s1.has_items() && it->first == "s2_agg_items") {
         ++it;
         continue;
       }
@@ -566,7 +566,7 @@ int mhx_trim(mhx_ctx *c) {
       it = c->work.erase(it);
     }
     c->filter_on = c->accumulate = false;
-    c->agg_hist_passes = 0;  // (their rows went with ws "s2_pre_hist": stage 2's sort takes its histograms itself)
+    c->s1.drop_hist();  // (their rows went with ws "s2_pre_hist": stage 2's sort takes its histograms itself)
     // the unitig graph's cleaning state (owner map, flags, the edge ranking the owner map comes from) lives in workspaces
     c->ut_ready = c->ut_owner = false;
     // the sorted-items view aliases a workspace
@@ -594,8 +594,7 @@ int mhx_reset(mhx_ctx *c) {
     c->n_parts = 1;
     c->part_begin.clear();
     c->pos_base = c->global_bases = 0;
-    c->agg_valid = false; c->agg_hist_passes = 0; c->solid_plain_k = 0;
-    c->agg_n = 0;
+    c->s1 = mhx::S1Handoff();  // (behind the synchronisation above: no count is on its way any more)
     c->n_route = 0;
     c->s1_density = 0;
     c->filter_kept = 0;
@@ -821,7 +820,7 @@ int mhx_set_is_solid(mhx_ctx *c, const uint64_t *bits, uint64_t n_words) {
   MHX_TRY({
     uint64_t need = mhx::div_ceil(c->seqs.n_bases, 64);
     if (n_words < need) throw mhx::Error("set_is_solid: bitmap too short");
-    c->agg_valid = false; c->agg_hist_passes = 0; c->solid_plain_k = 0;
+    c->s1.drop();
     mhx::DevBuf &b = c->result(MHX_BUF_IS_SOLID, (need + 1) * 8);
     b.used = need * 8;
     if (need) MHX_HIP(hipMemcpyAsync(b.p, bits, need * 8, hipMemcpyHostToDevice, c->stream));

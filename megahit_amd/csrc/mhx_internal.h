@@ -6,13 +6,13 @@
 #include <cstdio>
 #include <cstring>
 #include <functional>
-#include <deque>
 #include <map>
 #include <stdexcept>
 #include <string>
 #include <vector>
 
 #include "../../include/mhx.h"
+#include "s1_handoff.h"
 
 namespace mhx {
 
@@ -80,25 +80,7 @@ struct mhx_ctx {
   int my_part = 0, n_parts = 1;
   std::vector<uint32_t> part_begin;
   uint64_t pos_base = 0, global_bases = 0;
-  // stage-2 items aggregated by stage 1 (ws "s2_agg_items"): valid for one (k, m) until the reads or the
-  // is_solid bitmap change
-  bool agg_valid = false;
-  uint32_t agg_k = 0, agg_m = 0;
-  uint64_t agg_n = 0;
-  // ws "s2_pre_hist" holds the digit histograms of stage 2's sort passes (s2_agg_sort_passes(agg_k), signature agg_hist_sig) over exactly
-  // the agg_n items, taken where stage 1 packed them; 0 passes: none.  Means something only while agg_valid; stage 2 adds its '$' items.
-  int agg_hist_passes = 0;
-  uint64_t agg_hist_sig = 0;
-  // item counts on their way to the device cursor (asynchronous copies from here: the handle outlives whatever call sent them, also one
-  // that ends in an exception); emptied when a stage 1 opens its outputs, behind a synchronisation
-  std::deque<uint64_t> agg_n_home;
-  // the is_solid bitmap is exactly what stage 1 found for this (k, m) — no mercy edges added, not set by the caller: stage 2 may then take its
-  // solid items from a count of the (k+1)-mers instead of from every occurrence (s2.hip s2_agg_from_count; 0: not so)
-  uint32_t solid_plain_k = 0, solid_plain_m = 0;
-  // ... and s2_bound is what k_s2d_bound would count in that bitmap (two '$' items per run end), summed by the kernel that packed it:
-  // valid while solid_plain_k == s2_bound_k != 0
-  uint64_t s2_bound = 0;
-  uint32_t s2_bound_k = 0;
+  mhx::S1Handoff s1;  // what stage 1 left for stage 2: aggregated items, their histograms, its claim on the bitmap, the '$' items' bound (s1_handoff.h)
   uint64_t n_route = 0;      // multi-GPU: records in ws("route_records") (count events)
   uint32_t filter_kept = 0;           // lv1 buckets the filter keeps
   // stage 1: records per lv1 bucket the ranks of a multi-GPU run agreed on (comm.hip; 0: each call derives it from its own

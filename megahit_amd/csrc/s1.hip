@@ -506,7 +506,7 @@ struct S1Stage {
   // digit histograms of stage 2's sort over the aggregated items, taken by the kernels that pack them (ws "s2_pre_hist"; nullptr: not taken)
   unsigned long long *agg_hist = nullptr;
   DigitSpecs agg_specs = no_digits();
-  uint64_t agg_hist_sig = 0;
+  uint64_t agg_sig = 0;
   uint32_t seg_grid = 0, seg_cap = 0, seg_mcap = 0;
   uint32_t *seg_err = nullptr;
   int mark_mode = 0, mark_mode_used = 0;
@@ -583,26 +583,22 @@ struct S1Stage {
     // aggregated stage-2 items (k <= 22, m >= 2): at most 2 per solid run, a solid run has >= m records
     const bool agg_off = getenv("MHX_S2_PER_OCCURRENCE") != nullptr;  // (read per call: a resident server answers requests with different environments)
     agg = !agg_off && k <= 22 && m >= 2 && KWv == 2;
-    const bool agg_continues = acc && c->agg_valid && c->agg_k == k && c->agg_m == m;
-    c->agg_valid = false;
+    const S1Handoff::Opened opened = c->s1.open_items(k, m, acc);
     agg_cursor = c->ws("s2_agg_cursor", 64).as<uint64_t>();
-    if (!c->agg_n_home.empty()) {  // (counts of an earlier stage: their copies have long run, but only a synchronisation says so)
-      MHX_HIP(hipStreamSynchronize(st));
-      c->agg_n_home.clear();
-    }
-    agg_prev = agg_continues ? c->agg_n : 0;  // items of the earlier passes stay in front
+    // (counts of an earlier stage on their way to the device: their copies have long run, but only a synchronisation says so)
+    if (!opened.in_flight.empty()) MHX_HIP(hipStreamSynchronize(st));
+    agg_prev = opened.continues ? c->s1.agg_n : 0;  // items of the earlier passes stay in front
     agg_bound = (n_items / m + 16) * 2;
     // Stage 2 sorts exactly these items plus its '$' items when it takes them in place (s2.hip s2_agg_in_place): the kernels that pack
     // them take the digit histograms of that sort.  A workspace of their own: the front of a later pass over a range of bins writes
     // "sort_pre_hist" again.  Not when the items continue those of an earlier call (accumulate): the rows would be partial.
     agg_hist = nullptr;
-    c->agg_hist_passes = 0;
     if (agg && !global && !c->filter_on && !c->accumulate && agg_prev == 0 && c->opt("s2_pre_hist", 1) != 0) {
       const std::vector<SortPass> ps = s2_agg_sort_passes(k);
       if (!ps.empty() && ps.size() <= (size_t)kItemHistRows) {
         agg_specs.n = (int)ps.size();
         for (size_t p = 0; p < ps.size(); ++p) agg_specs.d[p] = spec_of_pass(ps[p], 2);
-        agg_hist_sig = passes_signature(ps);
+        agg_sig = passes_signature(ps);
         agg_hist = c->ws("s2_pre_hist", (size_t)kItemHistRows * 256 * 8).as<unsigned long long>();
         MHX_HIP(hipMemsetAsync(agg_hist, 0, (size_t)kItemHistRows * 256 * 8, st));
       }
@@ -781,18 +777,22 @@ struct S1Stage {
                                       c->work["s1_mark_counts"].as<uint32_t>(), reinterpret_cast<uint2 *>(dense + marks_prev), 0, no_digits(), nullptr));
       c->n_marks = marks_prev + seg_marks;
     }
-    if (agg) {  // pack the workgroups' regions behind the items of the earlier passes
-      uint64_t total = 0;
-      for (uint32_t v : h_counts) total += v;
-      uint2 *dense = grow_preserving(c, c->work["s2_agg_items"], (agg_prev + total) * 8 + 64, agg_prev * 8).as<uint2>();
-      if (total)
-        MHX_LAUNCH(c, "agg_compact", (double)total * 16,
-                   agg_compact_launch(st, dim3(seg_grid, 8), reinterpret_cast<const uint2 *>(spare), seg_cap,
-                                      c->work["s2_agg_counts"].as<uint32_t>(), dense + agg_prev, 1, agg_specs, agg_hist));
-      c->agg_n_home.push_back(agg_prev + total);  // (a home that outlives this call: mhx_ctx)
-      MHX_HIP(hipMemcpyAsync(agg_cursor, &c->agg_n_home.back(), 8, hipMemcpyHostToDevice, st));
-    }
+    // (agg_prev stays: a second run of the group-by, after a way back, packs behind the same earlier passes' items)
+    if (agg) pack_agg_regions(h_counts, c->work["s2_agg_counts"].as<uint32_t>(), 0);
     return 0;
+  }
+  // pack the workgroups' item regions (seg_grid regions of seg_cap slots in the spare sort buffer, `counts` on the device and here) behind
+  // the items of the earlier passes; the array is sized for max(what it holds now, expect) items.  -> the items it holds now
+  uint64_t pack_agg_regions(const std::vector<uint32_t> &h_counts, const uint32_t *counts, uint64_t expect) {
+    uint64_t total = 0;
+    for (uint32_t v : h_counts) total += v;
+    uint2 *dense = grow_preserving(c, c->work["s2_agg_items"], std::max(agg_prev + total, expect) * 8 + 64, agg_prev * 8).as<uint2>();
+    if (total)
+      MHX_LAUNCH(c, "agg_compact", (double)total * 16,
+                 agg_compact_launch(st, dim3(seg_grid, 8), reinterpret_cast<const uint2 *>(spare), seg_cap, counts, dense + agg_prev, 1, agg_specs, agg_hist));
+    const uint64_t *home = c->s1.count_home(agg_prev + total);  // (a home that outlives this call: the handle)
+    MHX_HIP(hipMemcpyAsync(agg_cursor, home, 8, hipMemcpyHostToDevice, st));
+    return *home;
   }
   // the sources of a pre-sorted stage become one unsorted array (a way back only)
   void gather_sources() {
@@ -876,18 +876,11 @@ struct S1Stage {
       c->n_marks = marks_prev + seg_marks;
     }
     if (agg) {
-      uint64_t total = 0;
-      for (uint32_t v : h_counts) total += v;
+      uint64_t now = agg_prev;
+      for (uint32_t v : h_counts) now += v;
       // (a pass of several: the array is sized for all of them after the first — the bins fill evenly — instead of growing pass by pass)
-      const uint64_t expect = !sparse && f.bin_hi > f.bin_lo ? (uint64_t)((double)(agg_prev + total) * (double)f.n_bins / (double)f.bin_hi * 1.05) : agg_prev + total;
-      uint2 *dense = grow_preserving(c, c->work["s2_agg_items"], std::max(agg_prev + total, expect) * 8 + 64, agg_prev * 8).as<uint2>();
-      if (total)
-        MHX_LAUNCH(c, "agg_compact", (double)total * 16,
-                   agg_compact_launch(st, dim3(seg_grid, 8), reinterpret_cast<const uint2 *>(spare), seg_cap, counts, dense + agg_prev, 1, agg_specs,
-                                      agg_hist));
-      c->agg_n_home.push_back(agg_prev + total);  // (a home that outlives this call: mhx_ctx)
-      MHX_HIP(hipMemcpyAsync(agg_cursor, &c->agg_n_home.back(), 8, hipMemcpyHostToDevice, st));
-      agg_prev = c->agg_n_home.back();  // (the next pass over a range of bins appends)
+      const uint64_t expect = !sparse && f.bin_hi > f.bin_lo ? (uint64_t)((double)now * (double)f.n_bins / (double)f.bin_hi * 1.05) : 0;
+      agg_prev = pack_agg_regions(h_counts, counts, expect);  // (the next pass over a range of bins appends)
     }
     return true;
   }
@@ -907,13 +900,9 @@ struct S1Stage {
 
   void publish(mhx_s1_result *out) {
     if (agg && (S == 3 || (S == 4 && !compact))) {  // also with zero local items: every rank takes the same stage-2 path
-      c->agg_n = 0;
-      MHX_HIP(hipMemcpyAsync(&c->agg_n, agg_cursor, 8, hipMemcpyDeviceToHost, st));
-      c->agg_valid = true;
-      c->agg_k = k;
-      c->agg_m = m;
-      c->agg_hist_passes = agg_hist ? agg_specs.n : 0;
-      c->agg_hist_sig = agg_hist_sig;
+      c->s1.agg_n = 0;
+      MHX_HIP(hipMemcpyAsync(&c->s1.agg_n, agg_cursor, 8, hipMemcpyDeviceToHost, st));
+      c->s1.publish_items(k, m, agg_hist ? agg_specs.n : 0, agg_sig);
     }
     if (sparse && classic_ran) {  // the classic kernel marked a byte map of the global read set: turn it into the list
       const uint64_t n_bytes = div_ceil(n_bits, 64) * 64;
@@ -949,15 +938,14 @@ struct S1Stage {
       MHX_LAUNCH(c, "pack_solid", (double)n_words64 * 72,
                  hipLaunchKernelGGL(k_pack_solid, dim3((unsigned)std::min<uint64_t>(div_ceil(n_words64 * 4, 256), 4096)), dim3(256), 0, st, solid_bytes, n_bits, is_solid,
                                     n_words64, ctr));
-    uint64_t n_solid = 0, n_mercy = 0;
+    uint64_t n_solid = 0, n_mercy = 0, run_ends = 0;
     {
       unsigned long long h[kCtrRunEnds + 1];
       MHX_HIP(hipMemcpyAsync(h, ctr, sizeof h, hipMemcpyDeviceToHost, st));
       MHX_HIP(hipStreamSynchronize(st));
       n_solid = h[0];
       n_mercy = h[1];
-      c->s2_bound = h[kCtrRunEnds];
-      c->s2_bound_k = bound_too ? k : 0;
+      run_ends = h[kCtrRunEnds];
       if (want_mercy && (c->accumulate || c->filter_on)) {  // keep the candidates of every pass; publish their sorted union
         const uint64_t prev = acc ? c->mercy_acc_n : 0;
         DevBuf &ma = grow_preserving(c, c->work["mercy_acc"], (prev + n_mercy) * 8 + 8, prev * 8);
@@ -977,8 +965,8 @@ struct S1Stage {
       c->result(MHX_BUF_MERCY_CAND, 8);
       c->results[MHX_BUF_MERCY_CAND].used = 0;
     }
-    c->solid_plain_k = global ? 0 : k;  // (the bitmap is stage 1's own for this (k, m) until mercy edges or the caller change it)
-    c->solid_plain_m = m;
+    c->s1.publish_bitmap(k, m, !global);  // (the bitmap is stage 1's own for this (k, m) until mercy edges or the caller change it)
+    if (bound_too) c->s1.publish_bound(k, run_ends);
     c->results[MHX_BUF_SORTED_ITEMS].release();
     c->results[MHX_BUF_SORTED_ITEMS].p = sorted;
     c->results[MHX_BUF_SORTED_ITEMS].cap = 0;

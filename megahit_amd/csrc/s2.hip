@@ -1439,31 +1439,50 @@ int s2_process(mhx_ctx *c, uint32_t k, uint32_t *buf_a, uint32_t *buf_b, uint64_
   return 0;
 }
 
-// Upper bound of the '$' items of the bitmap `solid` (exact unless palindromes occur).  from_s1: it is stage 1's own bitmap of (k, m), whose
-// pack kernel summed the same figure (mhx_ctx::s2_bound) — no kernel, no copy, no host round trip; else k_s2d_bound into cur[1].
-static uint64_t s2d_bound(mhx_ctx *c, uint32_t k, uint32_t m, const unsigned long long *solid, uint64_t n_words, unsigned long long *cur, bool from_s1) {
-  if (!n_words) return 0;
-  const long long mode = c->opt("s2_bound_from_s1", 1);  // (2: both, and they must agree — tests)
-  const bool cached = from_s1 && mode != 0 && c->solid_plain_k == k && c->solid_plain_m == m && c->s2_bound_k == k;
-  if (cached && mode != 2) return c->s2_bound;
+// The front of aggregated stage 2's '$' items, which come from the ends of the runs of solid positions in a bitmap: the bitmap, the zeroed
+// 64-byte cursor block (word 0: the cursor, word 1: k_s2d_bound's sum, word 4: the emitting kernel's error flag; words 2, 3 are the
+// caller's) and the upper bound of their number (exact unless palindromes occur).
+struct S2dFront {
+  const unsigned long long *solid;
+  uint64_t n_words;
+  unsigned long long *cur;
+  uint64_t bound;
+};
+// solid: the bitmap, nullptr: results[which].  from_s1: it may be stage 1's own bitmap of (k, m), whose pack kernel summed the bound
+// (S1Handoff::bound_for) — then no kernel, no copy, no host round trip; else k_s2d_bound into cur[1].
+static S2dFront s2d_open(mhx_ctx *c, uint32_t k, uint32_t m, const unsigned long long *solid, int which, bool from_s1) {
   hipStream_t st = c->stream;
-  uint64_t bound = 0;
-  MHX_LAUNCH(c, "s2_bound", (double)n_words * 8,
-             hipLaunchKernelGGL(k_s2d_bound, dim3((unsigned)std::min<uint64_t>(div_ceil(n_words, 256), 2048)), dim3(256), 0, st, solid, n_words, cur + 1));
-  MHX_HIP(hipMemcpyAsync(&bound, cur + 1, 8, hipMemcpyDeviceToHost, st));
+  S2dFront f{solid, div_ceil(c->seqs.n_bases, 64), nullptr, 0};
+  if (!f.solid) {
+    auto it = c->results.find(which);
+    if (it == c->results.end() || it->second.used < f.n_words * 8) throw Error("read2sdbg_s2: no is_solid bitmap");
+    f.solid = it->second.as<unsigned long long>();
+  }
+  f.cur = c->ws("s2d_cursor", 64).as<unsigned long long>();
+  MHX_HIP(hipMemsetAsync(f.cur, 0, 64, st));
+  if (!f.n_words) return f;
+  const long long mode = c->opt("s2_bound_from_s1", 1);  // (2: both, and they must agree — tests)
+  uint64_t s1_bound = 0;
+  const bool cached = from_s1 && mode != 0 && c->s1.bound_for(k, m, &s1_bound);
+  f.bound = s1_bound;
+  if (cached && mode != 2) return f;
+  MHX_LAUNCH(c, "s2_bound", (double)f.n_words * 8,
+             hipLaunchKernelGGL(k_s2d_bound, dim3((unsigned)std::min<uint64_t>(div_ceil(f.n_words, 256), 2048)), dim3(256), 0, st, f.solid, f.n_words, f.cur + 1));
+  MHX_HIP(hipMemcpyAsync(&f.bound, f.cur + 1, 8, hipMemcpyDeviceToHost, st));
   MHX_HIP(hipStreamSynchronize(st));
-  if (cached && bound != c->s2_bound)
-    throw Error("read2sdbg_s2: stage 1 counted " + std::to_string(c->s2_bound) + " '$' items at the run ends of its bitmap, the bitmap holds " + std::to_string(bound));
-  return bound;
+  if (cached && f.bound != s1_bound)
+    throw Error("read2sdbg_s2: stage 1 counted " + std::to_string(s1_bound) + " '$' items at the run ends of its bitmap, the bitmap holds " + std::to_string(f.bound));
+  return f;
 }
-// The '$' items of the run ends of `solid` (n_words bitmap words), written to dst (room for the bound of k_s2d_bound); -> their number.
-// cur: the zeroed 64-byte cursor block (word 0: the cursor, word 4: the kernel's error flag).  hist: the digit histograms of `specs` are added up there (k_s2d_emit's list form only).
-static uint64_t s2d_emit_items(mhx_ctx *c, uint32_t k, const unsigned long long *solid, uint64_t n_words, uint64_t bound, uint2 *dst, unsigned long long *cur,
-                               int fsh = 19, int bsh = 16, int csh = 0, const DigitSpecs *specs = nullptr, unsigned long long *hist = nullptr) {
-  if (!bound) return 0;
+// The '$' items of the front, written behind the n_agg items of `items` (room for n_agg + f.bound); -> their number.
+// hist: the digit histograms of `specs` are added up there (k_s2d_emit's list form only).
+static uint64_t s2d_emit_items(mhx_ctx *c, uint32_t k, const S2dFront &f, uint32_t *items, uint64_t n_agg, int fsh = 19, int bsh = 16, int csh = 0,
+                               const DigitSpecs *specs = nullptr, unsigned long long *hist = nullptr) {
+  if (!f.bound) return 0;
+  uint2 *dst = reinterpret_cast<uint2 *>(items) + n_agg;
   SeqSet &s = c->seqs;
   hipStream_t st = c->stream;
-  const uint64_t trips = div_ceil(n_words, 256 * kS2dWords);
+  const uint64_t trips = div_ceil(f.n_words, 256 * kS2dWords);
   dim3 grid((unsigned)std::min<uint64_t>(trips, 4096));
   if (c->opt("s2_dummy_list", 1) != 0) {
     // (every workgroup ends with up to 256 global atomics per histogram row: no more of them than the device holds at once, 5 per CU)
@@ -1472,38 +1491,28 @@ static uint64_t s2d_emit_items(mhx_ctx *c, uint32_t k, const unsigned long long 
     const uint32_t list_cap = cap > 0 ? (uint32_t)std::min<long long>(cap, kS2dList) : (uint32_t)kS2dList;
     const DigitSpecs none{};
     if (!specs || specs->n > kItemHistRows) hist = nullptr;
-    MHX_LAUNCH(c, "s2_extract", (double)bound * 8 + (double)n_words * 8,
-               hipLaunchKernelGGL(k_s2d_emit, grid, dim3(256), 0, st, s.words.as<uint32_t>(), s.start.as<uint64_t>(), s.n_seqs, s.fixed_len, (int)k, solid, n_words, dst,
-                                  cur, fsh, bsh, csh, list_cap, hist ? *specs : none, hist, (unsigned long long)bound, reinterpret_cast<uint32_t *>(cur + 4)));
+    MHX_LAUNCH(c, "s2_extract", (double)f.bound * 8 + (double)f.n_words * 8,
+               hipLaunchKernelGGL(k_s2d_emit, grid, dim3(256), 0, st, s.words.as<uint32_t>(), s.start.as<uint64_t>(), s.n_seqs, s.fixed_len, (int)k, f.solid, f.n_words, dst,
+                                  f.cur, fsh, bsh, csh, list_cap, hist ? *specs : none, hist, (unsigned long long)f.bound, reinterpret_cast<uint32_t *>(f.cur + 4)));
   } else {
     if (hist) throw Error("read2sdbg_s2: the per-thread walk takes no digit histograms");
-    MHX_LAUNCH(c, "s2_extract", (double)bound * 8 + (double)n_words * 8,
-               hipLaunchKernelGGL(k_s2d_emit_walk, grid, dim3(256), 0, st, s.words.as<uint32_t>(), s.start.as<uint64_t>(), s.n_seqs, s.fixed_len, (int)k, solid, n_words,
-                                  dst, cur, fsh, bsh, csh));
+    MHX_LAUNCH(c, "s2_extract", (double)f.bound * 8 + (double)f.n_words * 8,
+               hipLaunchKernelGGL(k_s2d_emit_walk, grid, dim3(256), 0, st, s.words.as<uint32_t>(), s.start.as<uint64_t>(), s.n_seqs, s.fixed_len, (int)k, f.solid, f.n_words,
+                                  dst, f.cur, fsh, bsh, csh));
   }
   unsigned long long h_cur[5] = {0, 0, 0, 0, 0};
-  MHX_HIP(hipMemcpyAsync(h_cur, cur, sizeof h_cur, hipMemcpyDeviceToHost, st));
+  MHX_HIP(hipMemcpyAsync(h_cur, f.cur, sizeof h_cur, hipMemcpyDeviceToHost, st));
   MHX_HIP(hipStreamSynchronize(st));
-  if ((h_cur[4] & 0xFFFFFFFFull) || h_cur[0] > bound) throw Error("read2sdbg_s2: more '$' items than their bound");
+  if ((h_cur[4] & 0xFFFFFFFFull) || h_cur[0] > f.bound) throw Error("read2sdbg_s2: more '$' items than their bound");
   return h_cur[0];
 }
 // aggregated stage 2 (k <= 22): solid items from stage 1 + dummy items from the local reads -> ws "items_a"
 uint64_t s2_agg_extract(mhx_ctx *c, uint32_t k) {
-  SeqSet &s = c->seqs;
-  hipStream_t st = c->stream;
-  const uint64_t n_agg = c->agg_n;
-  auto it = c->results.find(c->global_bases ? MHX_BUF_IS_SOLID_LOCAL : MHX_BUF_IS_SOLID);
-  if (it == c->results.end() || it->second.used < div_ceil(s.n_bases, 64) * 8) throw Error("read2sdbg_s2: no is_solid bitmap");
-  const unsigned long long *solid = it->second.as<unsigned long long>();
-  const uint64_t n_words = div_ceil(s.n_bases, 64);
-  unsigned long long *cur = c->ws("s2d_cursor", 64).as<unsigned long long>();
-  MHX_HIP(hipMemsetAsync(cur, 0, 64, st));
-  const uint64_t bound = s2d_bound(c, k, c->agg_m, solid, n_words, cur, !c->global_bases);
-  uint32_t *buf_a = c->ws("items_a", (n_agg + bound) * 8 + 64).as<uint32_t>();
-  if (n_agg) MHX_HIP(hipMemcpyAsync(buf_a, c->work["s2_agg_items"].p, n_agg * 8, hipMemcpyDeviceToDevice, st));
-  const uint64_t n_dummy = s2d_emit_items(c, k, solid, n_words, bound, reinterpret_cast<uint2 *>(buf_a) + n_agg, cur);
-  const uint64_t n_items = n_agg + n_dummy;
-  return n_items;
+  const uint64_t n_agg = c->s1.agg_n;
+  const S2dFront f = s2d_open(c, k, c->s1.items_m(), nullptr, c->global_bases ? MHX_BUF_IS_SOLID_LOCAL : MHX_BUF_IS_SOLID, !c->global_bases);
+  uint32_t *buf_a = c->ws("items_a", (n_agg + f.bound) * 8 + 64).as<uint32_t>();
+  if (n_agg) MHX_HIP(hipMemcpyAsync(buf_a, c->work["s2_agg_items"].p, n_agg * 8, hipMemcpyDeviceToDevice, c->stream));
+  return n_agg + s2d_emit_items(c, k, f, buf_a, n_agg);
 }
 std::vector<SortPass> s2_agg_sort_passes(uint32_t k, int count_bits) {
   return make_passes_ranges(2, {{count_bits, count_bits + 4}, {64 - 2 * (int)k, 64}});
@@ -1591,7 +1600,7 @@ __global__ __launch_bounds__(256) void k_valid_starts(unsigned long long *__rest
 bool s2_agg_from_count_applies(const mhx_ctx *c, uint32_t k, uint32_t m) {
   if (!c->opt("s2_agg_from_count", 1) || c->filter_on || c->accumulate || c->n_parts > 1 || c->global_bases) return false;
   if (m < 1 || k < 10 || k > 27) return false;
-  if (m > 1 && (k <= 22 || c->solid_plain_k != k || c->solid_plain_m != m)) return false;  // (k <= 22: stage 1 made the aggregated items itself)
+  if (m > 1 && (k <= 22 || !c->s1.bitmap_is_s1s(k, m))) return false;  // (k <= 22: stage 1 made the aggregated items itself)
   return count_stream_applies(c, k, m, true);
 }
 // -> false: the count gave up (nothing published: the per-occurrence path runs)
@@ -1637,26 +1646,20 @@ static bool s2_agg_from_count(mhx_ctx *c, uint32_t k, uint32_t m, mhx_sdbg_resul
   uint64_t n_edges = 0;
   for (uint32_t v : h_counts) n_edges += v;
   // 2. the bitmap the '$' items come from: stage 1's (min count > 1) or every (k+1)-mer start (min count 1)
-  const uint64_t n_words = div_ceil(s.n_bases, 64);
-  const unsigned long long *solid = nullptr;
-  if (m > 1) {
-    auto it = c->results.find(MHX_BUF_IS_SOLID);
-    if (it == c->results.end() || it->second.used < n_words * 8) throw Error("read2sdbg_s2: no is_solid bitmap");
-    solid = it->second.as<unsigned long long>();
-  } else {
-    unsigned long long *v = c->ws("s2c_valid", (n_words + 1) * 8).as<unsigned long long>();
+  unsigned long long *valid = nullptr;
+  if (m == 1) {
+    const uint64_t n_words = div_ceil(s.n_bases, 64);
+    valid = c->ws("s2c_valid", (n_words + 1) * 8).as<unsigned long long>();
     if (n_words)
       MHX_LAUNCH(c, "s2_valid_starts", (double)n_words * 8,
-                 hipLaunchKernelGGL(k_valid_starts, dim3((unsigned)div_ceil(n_words, 256)), dim3(256), 0, st, v, n_words, s.start.as<uint64_t>(), ns, s.fixed_len, (int)k));
-    solid = v;
+                 hipLaunchKernelGGL(k_valid_starts, dim3((unsigned)div_ceil(n_words, 256)), dim3(256), 0, st, valid, n_words, s.start.as<uint64_t>(), ns, s.fixed_len, (int)k));
   }
-  unsigned long long *cur = c->ws("s2d_cursor", 64).as<unsigned long long>();
-  MHX_HIP(hipMemsetAsync(cur, 0, 64, st));
-  const uint64_t bound = s2d_bound(c, k, m, solid, n_words, cur, m > 1);
+  const S2dFront f = s2d_open(c, k, m, valid, MHX_BUF_IS_SOLID, m > 1);
+  unsigned long long *cur = f.cur;
   // 3. items: per edge and strand ceil(multiplicity / cmax) of them, then the dummies.  (The edge regions live in the count's spare sort
   //    buffer "items_a" / "items_b": the items get buffers of their own.)
   const uint64_t items_cap = 2 * (n_edges + o.n_items / cmax + 1);
-  uint32_t *buf_a = c->ws("s2c_items_a", (items_cap + bound) * 8 + 64).as<uint32_t>();
+  uint32_t *buf_a = c->ws("s2c_items_a", (items_cap + f.bound) * 8 + 64).as<uint32_t>();
   uint32_t *err = reinterpret_cast<uint32_t *>(cur + 3);
   if (n_edges)
     MHX_LAUNCH(c, "s2_edges_to_items", (double)n_edges * 16,
@@ -1667,8 +1670,7 @@ static bool s2_agg_from_count(mhx_ctx *c, uint32_t k, uint32_t m, mhx_sdbg_resul
   MHX_HIP(hipStreamSynchronize(st));
   if (h_cur[3] & 0xFFFFFFFFull) throw Error("read2sdbg_s2: more aggregated items than their bound");
   const uint64_t n_agg = h_cur[2];
-  const uint64_t n_dummy = s2d_emit_items(c, k, solid, n_words, bound, reinterpret_cast<uint2 *>(buf_a) + n_agg, cur, fsh, bsh, csh);
-  const uint64_t n_items = n_agg + n_dummy;
+  const uint64_t n_items = n_agg + s2d_emit_items(c, k, f, buf_a, n_agg, fsh, bsh, csh);
   uint32_t *buf_b = c->ws("s2c_items_b", n_items * 8 + 64).as<uint32_t>();
   // 4. sort by chars, flag and W (the count bits ride along), emit
   uint32_t *sorted = sort_whole_key(c, buf_a, buf_b, n_items, 2, 2, s2_agg_sort_passes(k, cbits));
@@ -1676,40 +1678,30 @@ static bool s2_agg_from_count(mhx_ctx *c, uint32_t k, uint32_t m, mhx_sdbg_resul
   c->last_s1_plan = "stage 2 from a count of the (k+1)-mers: " + o.plan;
   return true;
 }
-bool s2_use_aggregated(const mhx_ctx *c, uint32_t k, uint32_t m) { return c->agg_valid && c->agg_k == k && c->agg_m == m && m > 1; }
+bool s2_use_aggregated(const mhx_ctx *c, uint32_t k, uint32_t m) { return m > 1 && c->s1.items_for(k, m); }
 
 // Single GPU, everything resident: the aggregated items are sorted where stage 1 left them (ws "s2_agg_items", the dummies
 // appended behind them) instead of being copied into "items_a" first — 0.94 GB read + written per step at 10 M reads.  The
 // sort consumes them: a second stage 2 without a new stage 1 takes the per-occurrence path (same records).
 static int s2_agg_in_place(mhx_ctx *c, uint32_t k, mhx_sdbg_result *out) {
-  SeqSet &s = c->seqs;
-  hipStream_t st = c->stream;
-  const uint64_t n_agg = c->agg_n;
-  auto it = c->results.find(MHX_BUF_IS_SOLID);
-  if (it == c->results.end() || it->second.used < div_ceil(s.n_bases, 64) * 8) throw Error("read2sdbg_s2: no is_solid bitmap");
-  const unsigned long long *solid = it->second.as<unsigned long long>();
-  const uint64_t n_words = div_ceil(s.n_bases, 64);
-  unsigned long long *cur = c->ws("s2d_cursor", 64).as<unsigned long long>();
-  MHX_HIP(hipMemsetAsync(cur, 0, 64, st));
-  const uint64_t bound = s2d_bound(c, k, c->agg_m, solid, n_words, cur, true);
-  uint32_t *buf_a = grow_preserving(c, c->work["s2_agg_items"], (n_agg + bound) * 8 + 64, n_agg * 8).as<uint32_t>();
+  const uint64_t n_agg = c->s1.agg_n;
+  const S2dFront f = s2d_open(c, k, c->s1.items_m(), nullptr, MHX_BUF_IS_SOLID, true);
+  uint32_t *buf_a = grow_preserving(c, c->work["s2_agg_items"], (n_agg + f.bound) * 8 + 64, n_agg * 8).as<uint32_t>();
   // Stage 1 took the digit histograms of this sort over its n_agg items where it packed them (ws "s2_pre_hist", for exactly this k and
   // this pass plan); k_s2d_emit adds those of the '$' items, and the sort reads no histogram of its own.  Anything that does not match:
   // the sort takes them itself.
   const std::vector<SortPass> passes = s2_agg_sort_passes(k);
   DigitSpecs specs{};
   unsigned long long *pre_hist = nullptr;
-  if (c->opt("s2_pre_hist", 1) != 0 && c->opt("s2_dummy_list", 1) != 0 && c->agg_hist_passes == (int)passes.size() && c->agg_hist_passes <= kItemHistRows &&
-      c->agg_hist_sig == passes_signature(passes) && c->work.count("s2_pre_hist")) {
+  if (c->opt("s2_pre_hist", 1) != 0 && c->opt("s2_dummy_list", 1) != 0 && (int)passes.size() <= kItemHistRows &&
+      c->s1.hist_for((int)passes.size(), passes_signature(passes)) && c->work.count("s2_pre_hist")) {
     pre_hist = c->work["s2_pre_hist"].as<unsigned long long>();
     specs.n = (int)passes.size();
     for (int p = 0; p < specs.n; ++p) specs.d[p] = spec_of_pass(passes[p], 2);
   }
   // (from here on the items are being consumed, and the rows count '$' items too: a call that fails below leaves nothing that claims otherwise)
-  c->agg_valid = false;
-  c->agg_hist_passes = 0;
-  const uint64_t n_dummy = s2d_emit_items(c, k, solid, n_words, bound, reinterpret_cast<uint2 *>(buf_a) + n_agg, cur, 19, 16, 0, &specs, pre_hist);
-  const uint64_t n_items = n_agg + n_dummy;
+  c->s1.consume_items();
+  const uint64_t n_items = n_agg + s2d_emit_items(c, k, f, buf_a, n_agg, 19, 16, 0, &specs, pre_hist);
   uint32_t *buf_b = c->ws("items_b", n_items * 8 + 64).as<uint32_t>();
   SortPrep prep;
   if (pre_hist) {

@@ -5,7 +5,7 @@ made — k_agg_compact at the end of stage 1, k_s2d_emit, k_skm_hp_publish — s
 for the '$' items comes from a count that stage 1's pack kernel took of the run ends in the bitmap words it wrote (s2_bound_from_s1).
 Every case against the oracle's SdBG: libraries with fewer bitmap words than a workgroup takes, a run end in most words, runs of one and
 two positions, runs that touch word and trip boundaries, palindromic ends, every knob setting, other k, the item layouts of
-s2_agg_from_count, passes over ranges of bins, the prefix plan, two ranks; which kernels ran; and no state left from an earlier call."""
+s2_agg_from_count, passes over ranges of bins, the prefix plan, two ranks; which kernels ran, also behind mhx_trim; and no state left from an earlier call."""
 import numpy as np
 import pytest
 
@@ -80,9 +80,9 @@ def wanted(kind, k, m):
     return _oracle[(kind, k, m)]
 
 
-def both_stages(engine, kind, k, m, opts, stage2_twice=False, reload=True):
+def both_stages(engine, kind, k, m, opts, stage2_twice=False, reload=True, trim=False):
     """stage 1 and stage 2 under opts; -> (the kernels of stage 2, stage 1's plan).  reload=False: on the library the engine holds
-    (loading clears what an earlier stage 1 left in the handle)"""
+    (loading clears what an earlier stage 1 left in the handle).  trim: the workspaces are released between the stages"""
     pkg, want1, want2 = wanted(kind, k, m)
     if reload:
         load(engine, pkg)
@@ -95,6 +95,8 @@ def both_stages(engine, kind, k, m, opts, stage2_twice=False, reload=True):
             solid = engine.fetch(lib.BUF_IS_SOLID, np.uint64)
             assert np.array_equal(solid, want1["is_solid"][: solid.size])
         plan = engine.last_s1_plan()
+        if trim:
+            engine.trim()
         engine.profile(True)
         engine.profile_reset()
         r2 = engine.read2sdbg_s2(k, m)
@@ -184,6 +186,26 @@ def test_items_appended_pass_by_pass(engine, opts):
 def test_stage_2_twice_after_one_stage_1(engine):
     both_stages(engine, "pe100", 21, 2, dict(SKM), stage2_twice=True)
     both_stages(engine, "short30", 21, 2, dict(PREFIX), stage2_twice=True)
+
+
+# stage 2's launches behind a trim, as the commit before the hand-off record (csrc/s1_handoff.h) made them.  tiny60: 24 random reads share
+# no (k+1)-mer — no solid position, no item, nothing to emit or sort; and the prefix plan marks the SOLID occurrences of a job this small
+# (no sample of the polarity under 2^16 items), so its pack kernel counts no run ends and k_s2d_bound runs
+NOTHING = {"s2_extract": 0, "s2_bound": 0, "radix_hist_all_8B": 0, "radix_scatter_8B": 0}
+TRIMMED = {("tiny60", "skm"): NOTHING, ("tiny60", "prefix"): dict(NOTHING, s2_bound=1),
+           ("pe100", "skm"): {"s2_extract": 1, "s2_bound": 0, "radix_hist_all_8B": 1, "radix_scatter_8B": 6},
+           ("pe100", "prefix"): {"s2_extract": 1, "s2_bound": 0, "radix_hist_all_8B": 1, "radix_scatter_8B": 6}}
+
+
+@pytest.mark.parametrize("plan", ["skm", "prefix"])
+@pytest.mark.parametrize("kind", ["tiny60", "pe100"])
+def test_workspaces_trimmed_between_the_stages(engine, kind, plan):
+    """mhx_trim between stage 1 and stage 2: the aggregated items stay, the rows of their histograms go with ws "s2_pre_hist" (the sort
+    takes its histograms itself), the bound of the '$' items lives in the handle and the bitmap is a result (no k_s2d_bound)"""
+    stats, _ = both_stages(engine, kind, 21, 2, dict(SKM if plan == "skm" else PREFIX), trim=True)
+    got = {n: launches(stats, n) for n in NOTHING}
+    print(kind, plan, got)
+    assert got == TRIMMED[kind, plan], (got, sorted(stats))
 
 
 @pytest.mark.parametrize("bound", [1, 2], ids=["bound from stage 1", "bound cross-checked"])
