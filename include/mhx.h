@@ -473,7 +473,8 @@ int mhx_sdbg_load_bytes(mhx_ctx *, const uint8_t *bytes, uint64_t n_bytes, const
  * character mapping (sequence_package.h:78-83).  text2 != NULL: a paired library, records interleaved r1, r2, r1, ...
  * (paired_fastx_reader.cpp:7-43).  Replaces SequenceLibCollection::Build's parse + pack (sequence_lib.cpp:8-91).
  * out->status 1 = the text is not plain FASTA / four-line FASTQ (carriage returns, multi-line FASTQ, junk before the
- * first header, mates of different counts): nothing was produced, run a sequential kseq-compatible parser instead. ---- */
+ * first header, a FASTA text that ends in a '>' alone on its line, mates of different counts): nothing was produced, run a
+ * sequential kseq-compatible parser instead. ---- */
 typedef struct {
   uint64_t n_reads, n_bases, n_words; /* n_bases counts an all-N / empty read as 1 (it is stored as one 'A') */
   uint32_t max_len;

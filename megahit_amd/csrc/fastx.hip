@@ -11,7 +11,10 @@
 // packed 2 bits per base, MSB first, behind the length word (:224-240).  Paired files are parsed separately and their
 // records interleaved (paired_fastx_reader.cpp:7-43).
 // Anything else (carriage returns, '+'/'@'-led lines inside FASTA, FASTQ that is not four lines per record, junk before
-// the first header) is reported back as status 1: the caller then runs its sequential kseq-compatible parser.
+// the first header, a FASTA text whose last byte is a '>' that begins a line) is reported back as status 1: the caller then
+// runs its sequential kseq-compatible parser.  The last of these because kseq returns no record for a header char with
+// nothing at all behind it (">a\nACGT\n>" holds one record, ">" none, ">a\nACGT\n>\n" two); as a line it would count as
+// a header here.
 #include "dev_prims.h"
 #include "mhx_internal.h"
 
@@ -179,6 +182,10 @@ static ParsedFastx parse_one(mhx_ctx *c, const char *h_text, uint64_t n, const s
     return p;
   }
   const bool fastq = h_text[0] == '@';
+  if (!fastq && h_text[n - 1] == '>' && (n == 1 || h_text[n - 2] == '\n')) {  // kseq: end of file, no record (see the top)
+    p.status = 1;
+    return p;
+  }
   char *t = W("text", n + 64).as<char>();
   upload_pinned(c, t, h_text, n);
   const uint64_t n_chunks = div_ceil(n, (uint64_t)kTextChunk);

@@ -177,10 +177,16 @@ void TextFile::close() {
   owned.shrink_to_fit();
 }
 
-void parse_fastx_sequential(const char *t, size_t n, const std::function<void(const char *, size_t)> &on_seq) {
-  size_t i = 0;
-  int last_char = 0;
-  std::string seq, line;
+bool FastxSequentialReader::next(std::string *seq) {
+  const char *t = t_;
+  const size_t n = n_;
+  size_t &i = i_;
+  seq->clear();
+  if (at_end_) return false;
+  auto end = [&] {  // nothing more will come, however often the caller asks
+    at_end_ = true;
+    return false;
+  };
   // one line starting at i (without its '\n'); advances i past the newline
   auto take_line = [&](std::string *dst, bool append) {
     size_t e = i;
@@ -190,51 +196,61 @@ void parse_fastx_sequential(const char *t, size_t n, const std::function<void(co
     i = e < n ? e + 1 : n;
     if (dst->size() > 1 && dst->back() == '\r') dst->pop_back();  // ks_getuntil2: on the accumulated string
   };
-  for (;;) {
-    if (last_char == 0) {  // jump to the next header char, anywhere
-      while (i < n && t[i] != '>' && t[i] != '@') ++i;
-      if (i >= n) return;
-      last_char = t[i++];
-    }
-    if (i >= n) return;  // a header char at the very end: ks_getuntil finds nothing -> EOF
-    // name = up to the first whitespace, then the rest of the header line is the comment
-    {
-      size_t e = i;
-      while (e < n && !isspace((unsigned char)t[e])) ++e;
-      const bool at_newline = e < n && t[e] == '\n';
-      i = e < n ? e + 1 : n;
-      if (!at_newline && e < n) take_line(&line, false);
-    }
-    seq.clear();
-    int c = -1;
-    while (i < n) {
-      c = (unsigned char)t[i++];
-      if (c == '>' || c == '+' || c == '@') break;
-      if (c == '\n') {
-        c = -1;
-        continue;
-      }
-      seq.push_back((char)c);
-      take_line(&seq, true);
+  if (last_char_ == 0) {  // jump to the next header char, anywhere
+    while (i < n && t[i] != '>' && t[i] != '@') ++i;
+    if (i >= n) return end();
+    last_char_ = t[i++];
+  }
+  if (i >= n) return end();  // a header char at the very end: ks_getuntil finds nothing -> EOF
+  // name = up to the first whitespace, then the rest of the header line is the comment
+  {
+    size_t e = i;
+    while (e < n && !isspace((unsigned char)t[e])) ++e;
+    const bool at_newline = e < n && t[e] == '\n';
+    i = e < n ? e + 1 : n;
+    if (!at_newline && e < n) take_line(&line_, false);
+  }
+  int c = -1;
+  while (i < n) {
+    c = (unsigned char)t[i++];
+    if (c == '>' || c == '+' || c == '@') break;
+    if (c == '\n') {
       c = -1;
-    }
-    if (c == '>' || c == '@') last_char = c;
-    else last_char = 0;
-    if (c != '+') {  // FASTA record (or the last record of the stream)
-      on_seq(seq.data(), seq.size());
-      if (c == -1) return;  // end of text
       continue;
     }
-    // FASTQ: skip the rest of the '+' line, then read quality lines until they cover the sequence
-    while (i < n && t[i] != '\n') ++i;
-    if (i >= n) return;  // no quality string: error -> the reader stops
-    ++i;
-    std::string qual;
-    do take_line(&qual, true);  // (kseq reads at least one quality line, even for an empty sequence)
-    while (qual.size() < seq.size() && i < n);
-    last_char = 0;
-    if (qual.size() != seq.size()) return;  // malformed: the reader stops here
-    on_seq(seq.data(), seq.size());
+    seq->push_back((char)c);
+    take_line(seq, true);
+    c = -1;
+  }
+  if (c == '>' || c == '@') last_char_ = c;
+  else last_char_ = 0;
+  if (c != '+') {  // FASTA record (or the last record of the stream)
+    if (c == -1) at_end_ = true;
+    return true;
+  }
+  // FASTQ: skip the rest of the '+' line, then read quality lines until they cover the sequence
+  while (i < n && t[i] != '\n') ++i;
+  if (i >= n) return end();  // no quality string: kseq's error at the end of the stream
+  ++i;
+  qual_.clear();
+  do take_line(&qual_, true);  // (kseq reads at least one quality line, even for an empty sequence)
+  while (qual_.size() < seq->size() && i < n);
+  last_char_ = 0;
+  return qual_.size() == seq->size();  // malformed: kseq_read returns -2 and the next call looks for a header from here
+}
+
+void parse_fastx_sequential(const char *t, size_t n, const std::function<void(const char *, size_t)> &on_seq, const char *t2, size_t n2) {
+  FastxSequentialReader a(t, n), b(t2, t2 ? n2 : 0);
+  std::string sa, sb;
+  for (;;) {  // one batch of the reference's build per round
+    size_t got = 0;
+    for (;; ++got) {
+      const bool ok_a = a.next(&sa), ok_b = t2 ? b.next(&sb) : true;  // the reference reads both mates before it looks
+      if (!ok_a || !ok_b) break;
+      on_seq(sa.data(), sa.size());
+      if (t2) on_seq(sb.data(), sb.size());
+    }
+    if (!got) return;
   }
 }
 

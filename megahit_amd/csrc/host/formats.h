@@ -65,10 +65,29 @@ struct TextFile {
   void close();
 };
 TextFile open_text_file(const std::string &path);
-// Sequential FASTA/FASTQ parser with kseq's semantics (kseq.h:193-247): multi-line records, junk before the first header,
-// '\r' stripped at line ends as ks_getuntil2 does, the stream ends at the first malformed FASTQ record.  calls
-// on_seq(ptr, len) per record.  The fallback of `buildlib` for texts the GPU parser declines.
-void parse_fastx_sequential(const char *text, size_t n, const std::function<void(const char *, size_t)> &on_seq);
+// Sequential FASTA/FASTQ reader with kseq's semantics (kseq.h:193-247): multi-line records, junk before the first header,
+// '\r' stripped at line ends as ks_getuntil2 does.  next() -> false at the end of the text and at a malformed FASTQ record;
+// after a malformed record a further next() reads on from where that one stopped, as a further kseq_read does.
+class FastxSequentialReader {
+ public:
+  FastxSequentialReader(const char *text, size_t n) : t_(text), n_(n) {}
+  bool next(std::string *seq);
+
+ private:
+  const char *t_;
+  size_t n_, i_ = 0;
+  int last_char_ = 0;
+  bool at_end_ = false;
+  std::string line_, qual_;
+};
+// The fallback of `buildlib` for texts the GPU parser declines: on_seq(ptr, len) per record of the library, the records of
+// text2 (if any) alternating with those of text.  The reference builds a library batch by batch (sequence_lib.cpp:49-61 over
+// AsyncSequenceReader): a batch ends where a reader returns nothing, the next one reads on, and the first empty batch ends
+// the library.  So a malformed record is skipped unless it comes first or directly after another one, and of two mate
+// files the longer one's surplus is dropped (paired_fastx_reader.cpp:7-43).  The reference's other batch limits (2^22
+// records, 2^28 bases) change the outcome only for a malformed record right at such a limit; they are not reproduced.
+void parse_fastx_sequential(const char *text, size_t n, const std::function<void(const char *, size_t)> &on_seq,
+                            const char *text2 = nullptr, size_t n2 = 0);
 // TrimN + character map + 2-bit packing of one sequence, appended as a .bin record (fastx_reader.cpp:56-71,
 // sequence_package.h:78-83,224-240,262-267); returns the stored length
 uint32_t append_bin_record(std::vector<uint32_t> *out, const char *s, size_t len);

@@ -1182,17 +1182,8 @@ int main_buildlib(int argc, char **argv) {
         ++total_reads;
         max_len = std::max(max_len, L);
       };
-      if (ty == "pe") {  // alternate the two files, stop when either ends (paired_fastx_reader.cpp:7-43)
-        std::vector<std::string> a, b;
-        mhxio::parse_fastx_sequential(t1.data, t1.size, [&](const char *s, size_t len) { a.emplace_back(s, len); });
-        mhxio::parse_fastx_sequential(t2.data, t2.size, [&](const char *s, size_t len) { b.emplace_back(s, len); });
-        for (size_t i = 0; i < std::min(a.size(), b.size()); ++i) {
-          add(a[i].data(), a[i].size());
-          add(b[i].data(), b[i].size());
-        }
-      } else {
-        mhxio::parse_fastx_sequential(t1.data, t1.size, add);
-      }
+      if (ty == "pe") mhxio::parse_fastx_sequential(t1.data, t1.size, add, t2.data ? t2.data : "", t2.size);
+      else mhxio::parse_fastx_sequential(t1.data, t1.size, add);
       if (!rec.empty() && fwrite(rec.data(), 4, rec.size(), bin) != rec.size()) fatal("write error on %s.bin", out.c_str());
     }
     t1.close();

@@ -59,4 +59,22 @@ def make_cases(d, seed=1):
     cases["fastq_truncated_quality"] = ("bad\nse %s\n" % w("bad.fq", fq_bad), True)
     p2s = w("pe_2_short.fa", "".join(">p%d/2\n%s\n" % (i, s) for i, s in enumerate(m2[:250])))
     cases["pe_unequal"] = ("pe lib\npe %s %s\n" % (p1, p2s), True)
+    # line, word and block edges (appended last: the draws above stay what they were)
+    cases["fasta_bare_header_at_eof"] = ("bare\nse %s\n" % w("bare.fa", ">a\nACGT\n>b\nTTGCA\n>"), True)  # kseq: no record for the last '>'
+    cases["fasta_header_last_no_newline"] = ("hdr last\nse %s\n" % w("hdr_last.fa", ">a\nACGT\n>b"), False)
+    cases["fasta_trailing_blank_lines"] = ("blank\nse %s\n" % w("blank.fa", ">a\nACGT\n\n>b\nTT\nG\n\n\n"), False)
+    cases["fastq_quality_led_by_at_plus_gt"] = ("qual\nse %s\n" % w("qual.fq", "@a\nACGT\n+\n@III\n@b\nTTGCA\n+b\n+IIII\n@c\nGGC\n+\n>II\n@d\nA\n+\n@\n"), False)
+    edge = [rand_seq(rng, L) for L in (1, 15, 16, 17, 31, 32, 33, 63, 64, 65, 127, 128, 129, 255, 256, 257)]
+    for L in (1, 16, 17, 33):
+        s = rand_seq(rng, L)
+        edge += [s[:i] + "N" + s[i + 1:] for i in (0, 15, 16, L - 1) if i < L] + ["N" * L, "n" * L]
+    edge += ["NANNN", "NNACGTNNACGT", rand_seq(rng, 16) + "N" + rand_seq(rng, 5), "N" + rand_seq(rng, 32) + "n" + rand_seq(rng, 40)]
+    cases["fasta_edge_lengths"] = ("edges\nse %s\n" % w("edge.fa", "".join(">e%d\n%s\n" % (i, s) for i, s in enumerate(edge))), False)
+    big = [rand_seq(rng, int(rng.choice([1, 15, 16, 17, 33, 64, 65, 100, 129, 257])), p_n=0.02 if i % 5 == 0 else 0.0) for i in range(1500)]
+    fa_big = "".join(">b%d\n%s\n" % (i, wrap(s, 60) if i % 2 else s) for i, s in enumerate(big))
+    assert len(fa_big) > 65536 + 4096  # more than one block of the newline kernels
+    cases["fasta_multi_block"] = ("blocks\nse %s\n" % w("blocks.fa", fa_big), False)
+    # the reference reads on behind a malformed record (its next batch starts there): the records after it are in the library
+    fq_mid = "@a\nACGT\n+\nIIII\n@broken\nACGTACGT\n+\nIIII\n@lost\nACGT\n+\nIIII\n@kept\nTTGCA\n+\nIIIII\n"
+    cases["fastq_malformed_record_in_the_middle"] = ("mid\nse %s\n" % w("mid.fq", fq_mid), True)
     return cases
