@@ -176,6 +176,13 @@ int mhx_set_option(mhx_ctx *, const char *name, long long value);
  *                          count_skm_group (2): chunks of 64 windows per round of compare-and-swaps (4 spills registers: measured slower)
  *   dist_skm (1)           several GPUs: 0: stage 1 never exchanges super-k-mer records by bin (comm.hip dist_s1_skm; the pre-sorted exchange
  *                          of 12-byte records runs); 1: where every rank serves the shape (as s1_skm, at most 8 ranks, no memory plan)
+ *   count_skm_dist (0)     several GPUs, opt-in: 1: `count` exchanges super-k-mer records by bin too (comm.hip dist_count_skm; needs count_skm,
+ *                          s1_skm and dist_skm non-zero): 19 <= k <= 21, min count <= 2, at most 8 ranks, one pass (no memory plan); the bin
+ *                          owners group the windows (k_count_skm<.., EVENTS>), solid edges cross to the owners of their lv1 buckets (8 bytes
+ *                          each), homopolymer tallies are summed over the ranks; the ranks take it and give it up together, and the pre-sorted
+ *                          exchange then runs.  Set it to the same value on every rank.  0: the pre-sorted exchange, as before.
+ *                          count_skm_ev_cap (0 = sized by the driver): events a workgroup's region holds at a bin owner (tests: 1 forces
+ *                          the overflow and the give-up)
  * The CLI's memory plan (host/mhx_core.cpp plan_ranges): MHX_PLAN_BY_TIME=0 plans by space only; MHX_ALLOC_S_PER_GB=<seconds> sets the
  * hipMalloc rate the time plan assumes (tests).
  * (mhx_tuning.conf of this tree: s1_gen_blocked = 1.) */

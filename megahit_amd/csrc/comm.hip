@@ -390,21 +390,49 @@ static bool dist_s1_presorted(mhx_ctx *c, mhx_comm *cm, uint32_t k, uint32_t m, 
 // whole job), on taking this form at all (any rank may veto: shape, a memory plan, more than kSkmSrcMax ranks) and on giving it up (a
 // record array or an output region that overflowed, a bin of low-complexity reads): -> false, nothing of the pass published, the
 // pre-sorted exchange of the prefix plan runs.
-static bool dist_s1_skm(mhx_ctx *c, mhx_comm *cm, uint32_t k, uint32_t m, mhx_s1_result *r1, std::string *why) {
-  const int n = cm->n, rank = cm->rank;
+// The two halves stage 1 and `count` share.  skm_agree: one all-reduce — any rank that cannot vetoes, the largest shard sizes the bins
+// (-> the bin bits, 0: the form is not taken).  skm_exchange: this rank's records made and ordered by bin, each owner's slice sent as it is,
+// the sources of this owner's group-by in *o (its own slice where it lies, the others in ws "items_recv"); one all-reduce on giving up, which
+// for `count` also adds up the ranks' homopolymer tallies (hp_sum: 32 values, s1_skm.hip k_skm_make).  A rank of `count` without a window makes
+// no records and still owns its bins.
+static int skm_agree(mhx_ctx *c, mhx_comm *cm, uint32_t k, bool applies) {
   const SeqSet &sq = c->seqs;
   const uint64_t n_win_local = sq.n_bases > sq.n_seqs * (uint64_t)k ? sq.n_bases - sq.n_seqs * (uint64_t)k : 0;
-  std::vector<uint64_t> v{s1_skm_dist_applies(c, k, m) ? 0ull : 1ull, n_win_local};
-  cm->all_reduce(v, true);  // any rank that cannot vetoes; the largest shard sizes the bins
+  std::vector<uint64_t> v{applies ? 0ull : 1ull, n_win_local};
+  cm->all_reduce(v, true);
   const long long knob = c->opt("s1_skm", 1);
-  if (v[0] || (knob < 2 && v[1] * (uint64_t)n < (uint64_t)c->opt("s1_skm_min_windows", 1 << 22))) return false;
+  if (v[0] || (knob < 2 && v[1] * (uint64_t)cm->n < (uint64_t)c->opt("s1_skm_min_windows", 1 << 22))) return 0;
   int bin_bits = 16;
-  while (bin_bits < 20 && (double)v[1] * (double)n * 0.29 / (double)(1ull << bin_bits) > 8192.0) ++bin_bits;
+  while (bin_bits < 20 && (double)v[1] * (double)cm->n * 0.29 / (double)(1ull << bin_bits) > 8192.0) ++bin_bits;
   if (const long long fb = c->opt("s1_skm_bin_bits", 0)) bin_bits = (int)std::min<long long>(20, std::max<long long>(8, fb));
+  return bin_bits;
+}
+static bool skm_exchange(mhx_ctx *c, mhx_comm *cm, uint32_t k, int bin_bits, bool for_count, SkmFront *o, std::vector<uint64_t> *hp_sum, std::string *why) {
+  const int n = cm->n, rank = cm->rank;
+  const SeqSet &sq = c->seqs;
   hipStream_t st = c->stream;
   SkmFront f{};
-  std::vector<uint64_t> fail{s1_skm_front(c, k, &f, 0, 1, bin_bits) ? 0ull : 1ull};
-  cm->all_reduce(fail, true);
+  bool made = true;
+  if (sq.n_seqs && sq.max_len >= k + 1) {
+    made = s1_skm_front(c, k, &f, 0, 1, bin_bits, for_count);
+  } else {  // (count only: stage 1 leaves the form when a rank has no window)
+    f.n_src = 1;
+    f.n_bins = 1u << bin_bits;
+    f.bin_bits = bin_bits;
+    f.bin_hi = f.n_bins;
+    f.src[0] = c->ws("items_a", 64).as<uint4>();
+    uint64_t *zero = c->ws("s1_bucket_bounds", ((size_t)f.n_bins + 1) * 8 + 64).as<uint64_t>();
+    MHX_HIP(hipMemsetAsync(zero, 0, ((size_t)f.n_bins + 1) * 8, st));
+    f.src_bounds[0] = zero;
+  }
+  std::vector<uint64_t> fail(hp_sum ? 33 : 1, 0);
+  fail[0] = made ? 0ull : 1ull;
+  if (hp_sum && made && f.hp) {
+    MHX_HIP(hipMemcpyAsync(&fail[1], f.hp + 8, 32 * 8, hipMemcpyDeviceToHost, st));
+    MHX_HIP(hipStreamSynchronize(st));
+  }
+  cm->all_reduce(fail, false);  // (a sum: the ranks that gave up, the tallies of all)
+  if (hp_sum) hp_sum->assign(fail.begin() + 1, fail.end());
   if (fail[0]) {
     *why = f.n_records ? "a rank's bin of low-complexity reads" : "a rank's record array overflowed";
     return false;
@@ -426,8 +454,8 @@ static bool dist_s1_skm(mhx_ctx *c, mhx_comm *cm, uint32_t k, uint32_t m, mhx_s1
   uint4 *recv = c->ws("items_recv", n_recv * 16 + 64).as<uint4>();
   cm->all_to_all_v(f.src[0], counts, recv, rc, 16, true);
   // the sources of this owner's group-by: its own slice where it lies, the others in the receive buffer; where the bins start in each
-  SkmFront o = f;
-  o.n_src = n;
+  *o = f;
+  o->n_src = n;
   uint64_t *sb = c->ws("skm_src_bounds", (size_t)n * ((size_t)n_bins + 1) * 8 + 64).as<uint64_t>();
   uint64_t at = 0;
   for (int p = 0; p < n; ++p) {
@@ -437,13 +465,21 @@ static bool dist_s1_skm(mhx_ctx *c, mhx_comm *cm, uint32_t k, uint32_t m, mhx_s1
       ptr = recv + at;
       at += rc[p];
     }
-    o.src[p] = ptr;
-    o.src_bounds[p] = sb + (size_t)p * ((size_t)n_bins + 1);
+    o->src[p] = ptr;
+    o->src_bounds[p] = sb + (size_t)p * ((size_t)n_bins + 1);
     s1_skm_bounds_of(c, ptr, rc[p], n_bins, sb + (size_t)p * ((size_t)n_bins + 1));
   }
-  o.bin_lo = (uint32_t)cut[rank];
-  o.bin_hi = (uint32_t)cut[rank + 1];
-  o.n_records = total;
+  o->bin_lo = (uint32_t)cut[rank];
+  o->bin_hi = (uint32_t)cut[rank + 1];
+  o->n_records = total;
+  return true;
+}
+
+static bool dist_s1_skm(mhx_ctx *c, mhx_comm *cm, uint32_t k, uint32_t m, mhx_s1_result *r1, std::string *why) {
+  const int bin_bits = skm_agree(c, cm, k, s1_skm_dist_applies(c, k, m));
+  if (!bin_bits) return false;
+  SkmFront o{};
+  if (!skm_exchange(c, cm, k, bin_bits, false, &o, nullptr, why)) return false;
   mhx_s1_result rp{};
   std::vector<uint64_t> fail2{s1_skm_owner(c, k, m, o, &rp) ? 0ull : 1ull};
   cm->all_reduce(fail2, true);
@@ -452,6 +488,54 @@ static bool dist_s1_skm(mhx_ctx *c, mhx_comm *cm, uint32_t k, uint32_t m, mhx_s1
     return false;
   }
   *r1 = rp;
+  return true;
+}
+
+// `count` on the same records (opt-in: count_skm_dist; k 19..21, min count <= 2, at most kSkmSrcMax ranks, one pass): the records of
+// k_skm_make<.., COUNT> cross by bin — 16 bytes per ~3.5 windows where the pre-sorted exchange below moves 12 per window — and the owner of a
+// bin groups its windows (k_count_skm<.., EVENTS>).  What a bin owner finds belongs elsewhere: a solid edge to the owner of its lv1 bucket (a
+// second, small exchange of 8 bytes per edge: rank p ends up with the ordered edges of part_begin[p] .. part_begin[p + 1] as on every other
+// route), the events of a flagged key's windows to the ranks that hold the reads (stashed here, routed by the caller).  Homopolymer windows
+// never enter a record: the ranks add their tallies up and rank 0 publishes the one or two keys; a solid one without an in- or out-edge in
+// the sum makes all ranks give up, as one GPU does.  -> false: not taken, or given up together (*why) — the pre-sorted exchange runs and
+// starts every result array afresh.
+static bool dist_count_skm(mhx_ctx *c, mhx_comm *cm, uint32_t k, uint32_t m, mhx_count_result *out, std::string *why) {
+  const int n = cm->n, rank = cm->rank;
+  const int bin_bits = skm_agree(c, cm, k, count_skm_dist_applies(c, k, m));
+  if (!bin_bits) return false;
+  SkmFront o{};
+  std::vector<uint64_t> hp;
+  if (!skm_exchange(c, cm, k, bin_bits, true, &o, &hp, why)) return false;
+  bool hp_any = false;
+  for (int x = 0; x < 2; ++x) {  // (what k_count_hp_publish decides, known to every rank)
+    const uint64_t *t = &hp[(size_t)x * 16];
+    hp_any = hp_any || t[0] != 0;
+    if (!t[0] || t[0] < m) continue;
+    bool has_in = false, has_out = false;
+    for (int b = 0; b < 4; ++b) {
+      has_in = has_in || t[1 + b] >= m;
+      has_out = has_out || t[5 + b] >= m;
+    }
+    if (!has_in || !has_out) {
+      *why = "a solid homopolymer key without an in- or out-edge";
+      return false;
+    }
+  }
+  CountStreamOut so;
+  std::vector<uint64_t> fail{count_skm_dist_open(c, k, m, o, &so) ? 0ull : 1ull};
+  cm->all_reduce(fail, true);
+  if (fail[0]) {
+    *why = "an owner's edge or event region overflowed";
+    return false;
+  }
+  std::vector<uint64_t> counts(n, 0), rc;
+  const uint32_t *send = count_skm_dist_edges(c, k, m, &so, rank == 0 && hp_any ? reinterpret_cast<const unsigned long long *>(hp.data()) : nullptr, counts.data());
+  cm->all_to_all_counts(counts, rc);
+  uint64_t n_recv = 0;
+  for (int p = 0; p < n; ++p) n_recv += rc[p];
+  void *recv = c->ws("items_recv", n_recv * 8 + 64).p;
+  cm->all_to_all_v(send, counts, recv, rc, 8);
+  count_skm_dist_close(c, k, m, o, so, n_recv, o.n_items, out);
   return true;
 }
 
@@ -915,10 +999,14 @@ int mhx_dist_count(mhx_ctx *c, mhx_comm *cm, uint32_t k, uint32_t min_count, mhx
     for (int pass = 0; pass < dp.n; ++pass) {
       mhx::set_pass(c, dp, pass, true);
       mhx_count_result rp{};
-      if (!mhx::dist_count_presorted(c, cm, k, min_count, &rp)) {  // the classic exchange: 16-byte items, owner multisplit, tile path at the owner
+      bool done = false;
+      std::string skm_why;
+      if (dp.n == 1 && c->opt("count_skm_dist", 0)) done = mhx::dist_count_skm(c, cm, k, min_count, &rp, &skm_why);  // super-k-mer records, exchanged by bin (opt-in)
+      if (!done && !mhx::dist_count_presorted(c, cm, k, min_count, &rp)) {  // the classic exchange: 16-byte items, owner multisplit, tile path at the owner
         const uint64_t n = mhx::exchange_stage(c, cm, MHX_STAGE_COUNT, k, min_count);
         MHX_CK(mhx_dist_process_count(c, k, min_count, n, &rp));
       }
+      if (!skm_why.empty()) c->last_s1_plan += " [super-k-mer records given up: " + skm_why + "]";
       mhx::route(c, cm, MHX_ROUTE_COUNT_EVENTS);
       if (dp.n > 1) {  // the solid edges and their per-bucket numbers of every pass, kept on the device (a bucket belongs to one pass)
         mhx::DevBuf &src = c->results[MHX_BUF_EDGES];

@@ -957,6 +957,20 @@ void count_apply_events(mhx_ctx *c, const unsigned long long *ev, uint64_t n) {
   MHX_HIP(hipStreamSynchronize(st));
 }
 
+// the tail of the streaming forms: n_edges packed 8-byte solid edges in `ea` (uint64 each, the low word first in memory; swapped: (hi, lo) word
+// pairs already) -> ordered by the (k+1)-mer in `edges`, and the edges per lv1 bucket
+static void count_edges_tail(mhx_ctx *c, uint32_t *ea, uint32_t *eb, uint64_t n_edges, int key_bits, uint32_t *edges, unsigned long long *bcount, bool swapped) {
+  hipStream_t st = c->stream;
+  if (!n_edges) return;
+  // uint64 (lo word first in memory) -> (hi, lo) word pairs = the edge's word order; sort by the (k+1)-mer bits
+  if (!swapped) hipLaunchKernelGGL(k_swap_pairs, dim3((unsigned)div_ceil(n_edges, 256)), dim3(256), 0, st, ea, n_edges);
+  uint32_t *es = sort_whole_key(c, ea, eb, n_edges, 2, 2, make_passes(2, 64 - key_bits, 64));  // distinct keys: the count bits never decide
+  MHX_HIP(hipMemcpyAsync(edges, es, n_edges * 8, hipMemcpyDeviceToDevice, st));
+  MHX_LAUNCH(c, "edge_buckets", (double)n_edges * 8,
+             hipLaunchKernelGGL(k_edge_buckets, dim3((unsigned)div_ceil(n_edges, 256)), dim3(256), 0, st, edges, n_edges, bcount, 2));
+  MHX_HIP(hipGetLastError());
+}
+
 // count on the design of stage 1 (round 5; s1.hip: the first sort pass makes 12-byte records, two prefix passes, LDS group-by per
 // bucket with the has_in / has_out evidence in the table, first_0_out / last_0_in from a second look at the few buckets that
 // hold a solid key without an in- or out-edge).  -> false: that form gave up; nothing is published, the caller runs the
@@ -1086,13 +1100,7 @@ static bool count_run_stream(mhx_ctx *c, uint32_t k, uint32_t m, mhx_count_resul
       MHX_LAUNCH(c, "edges_compact", (double)n_edges * 16,
                  hipLaunchKernelGGL(k_edges_compact, dim3(o.grid, 4), dim3(256), 0, st, reinterpret_cast<const unsigned long long *>(o.spare), o.cap, o.counts,
                                     reinterpret_cast<unsigned long long *>(ea)));
-    // uint64 (lo word first in memory) -> (hi, lo) word pairs = the edge's word order; sort by the (k+1)-mer bits
-    hipLaunchKernelGGL(k_swap_pairs, dim3((unsigned)div_ceil(n_edges, 256)), dim3(256), 0, st, ea, n_edges);
-    uint32_t *es = sort_whole_key(c, ea, eb, n_edges, 2, 2, make_passes(2, 64 - key_bits, 64));  // distinct keys: the count bits never decide
-    MHX_HIP(hipMemcpyAsync(edges, es, n_edges * 8, hipMemcpyDeviceToDevice, st));
-    MHX_LAUNCH(c, "edge_buckets", (double)n_edges * 8,
-               hipLaunchKernelGGL(k_edge_buckets, dim3((unsigned)div_ceil(n_edges, 256)), dim3(256), 0, st, edges, n_edges, bcount, 2));
-    MHX_HIP(hipGetLastError());
+    count_edges_tail(c, ea, eb, n_edges, key_bits, edges, bcount, false);
   }
   if (pre) {  // several GPUs: the events -> sorted by position in ws("route_records"); first / last are finished by mhx_dist_apply_routed
     int hi_bit = 2;
@@ -1130,6 +1138,91 @@ int count_process_presorted(mhx_ctx *c, uint32_t k, uint32_t m, const S1Sources 
     return 0;
   }
   return -1;
+}
+
+// ---- several GPUs, super-k-mer records exchanged by minimizer bin (comm.hip dist_count_skm): the owner's half in three steps, between which
+// the ranks agree on going on and exchange the solid edges ----
+// the rank's result arrays as count_run_stream(pre) starts from, then the group-by over the bins this rank owns
+bool count_skm_dist_open(mhx_ctx *c, uint32_t k, uint32_t m, const SkmFront &f, CountStreamOut *o) {
+  hipStream_t st = c->stream;
+  const uint64_t ns = c->seqs.n_seqs;
+  uint32_t *first = c->result(MHX_BUF_FIRST_0_OUT, (ns ? ns : 1) * 4).as<uint32_t>();
+  c->result(MHX_BUF_LAST_0_IN, (ns ? ns : 1) * 4);
+  uint32_t *last = c->ws("last_p1", (ns ? ns : 1) * 4).as<uint32_t>();
+  c->results[MHX_BUF_FIRST_0_OUT].used = ns * 4;
+  c->results[MHX_BUF_LAST_0_IN].used = ns * 4;
+  unsigned long long *hist = c->result(MHX_BUF_MUL_HIST, (MHX_MAX_MUL + 1) * 8).as<unsigned long long>();
+  unsigned long long *bcount = c->result(MHX_BUF_BUCKET_COUNT, MHX_NUM_BUCKETS * 8).as<unsigned long long>();
+  MHX_HIP(hipMemsetAsync(first, 0xFF, (ns ? ns : 1) * 4, st));
+  MHX_HIP(hipMemsetAsync(last, 0x00, (ns ? ns : 1) * 4, st));
+  MHX_HIP(hipMemsetAsync(hist, 0, (MHX_MAX_MUL + 1) * 8, st));
+  MHX_HIP(hipMemsetAsync(bcount, 0, MHX_NUM_BUCKETS * 8, st));
+  return count_skm_owner(c, k, m, f, hist, o);
+}
+// the owner's solid edges packed, the homopolymer keys behind them on the one rank that publishes them (hp_sum: 32 tallies, the ranks' summed),
+// all split by the owner of the edge's lv1 bucket: -> (hi, lo) word pairs, owners ascending, counts[p] for owner p
+const uint32_t *count_skm_dist_edges(mhx_ctx *c, uint32_t k, uint32_t m, CountStreamOut *o, const unsigned long long *hp_sum, uint64_t *counts) {
+  hipStream_t st = c->stream;
+  if (c->work.find("owner_lut") == c->work.end()) throw Error("count: call mhx_set_partition first");
+  std::vector<uint32_t> hc(o->grid);
+  MHX_HIP(hipMemcpyAsync(hc.data(), o->counts, (size_t)o->grid * 4, hipMemcpyDeviceToHost, st));
+  MHX_HIP(hipStreamSynchronize(st));
+  uint64_t tot = 0;
+  for (uint32_t v : hc) tot += v;
+  unsigned long long *dense = c->ws("cs_edges_a", (tot + 3) * 8).as<unsigned long long>();
+  if (tot)
+    MHX_LAUNCH(c, "edges_compact", (double)tot * 16,
+               hipLaunchKernelGGL(k_edges_compact, dim3(o->grid, 4), dim3(256), 0, st, reinterpret_cast<const unsigned long long *>(o->spare), o->cap, o->counts, dense));
+  if (hp_sum) {
+    unsigned long long *hp = c->ws("skm_hp", 512).as<unsigned long long>();
+    MHX_HIP(hipMemcpyAsync(hp + 8, hp_sum, 32 * 8, hipMemcpyHostToDevice, st));
+    uint64_t ne = 0, nk = 0;
+    bool flagged = false;
+    count_skm_hp_publish(c, hp, k, m, c->results[MHX_BUF_MUL_HIST].as<unsigned long long>(), dense + tot, &ne, &nk, &flagged);
+    tot += ne;
+    o->n_distinct += nk;
+  }
+  uint32_t *send = c->ws("cs_edges_b", (tot + 1) * 8).as<uint32_t>();
+  if (tot) hipLaunchKernelGGL(k_swap_pairs, dim3((unsigned)div_ceil(tot, 256)), dim3(256), 0, st, reinterpret_cast<uint32_t *>(dense), tot);
+  partition_by_owner(c, reinterpret_cast<const uint32_t *>(dense), send, tot, 2, c->work["owner_lut"].as<uint8_t>(), c->n_parts, counts);
+  return send;
+}
+// the n_recv edges of this rank's lv1 buckets (ws "items_recv") -> ordered and published; the events -> ws "route_records" for the read owners
+void count_skm_dist_close(mhx_ctx *c, uint32_t k, uint32_t m, const SkmFront &f, const CountStreamOut &o, uint64_t n_recv, uint64_t n_items, mhx_count_result *out) {
+  hipStream_t st = c->stream;
+  const int key_bits = (int)(k + 1) * 2;
+  uint32_t *ea = c->ws("items_recv", n_recv * 8 + 64).as<uint32_t>();
+  uint32_t *eb = c->ws("cs_edges_a", (n_recv + 1) * 8).as<uint32_t>();
+  uint32_t *edges = c->result(MHX_BUF_EDGES, (n_recv ? n_recv : 1) * 8).as<uint32_t>();
+  c->results[MHX_BUF_EDGES].used = n_recv * 8;
+  count_edges_tail(c, ea, eb, n_recv, key_bits, edges, c->results[MHX_BUF_BUCKET_COUNT].as<unsigned long long>(), true);
+  unsigned long long *dense = c->ws("cs_events_dense", o.n_events * 8 + 64).as<unsigned long long>();
+  if (o.n_events)
+    MHX_LAUNCH(c, "events_compact", (double)o.n_events * 16,
+               hipLaunchKernelGGL(k_edges_compact, dim3(o.grid, 4), dim3(256), 0, st, o.events, o.ev_cap, o.ev_counts, dense));
+  int hi_bit = 2;
+  while (hi_bit < 64 && ((c->global_bases << 1) >> hi_bit)) ++hi_bit;
+  stash_route_records(c, dense, o.n_events, hi_bit);
+  mhx::DevBuf &si = c->results[MHX_BUF_SORTED_ITEMS];
+  si.release();
+  c->sorted_item_words = 3;
+  si.p = nullptr;
+  si.cap = 0;
+  si.used = 0;
+  c->count_acc_k = k;
+  c->count_acc_m = m;
+  char txt[320];
+  snprintf(txt, sizeof txt, "count: super-k-mers m%u, 2^%d bins (%llu records at this owner, bins %u..%u; %llu events) [exchanged by bin]", k + 1 - 9, f.bin_bits,
+           (unsigned long long)f.n_records, f.bin_lo, f.bin_hi, (unsigned long long)o.n_events);
+  c->last_s1_plan = txt;
+  MHX_HIP(hipStreamSynchronize(st));
+  if (out) {
+    out->n_items = n_items;
+    out->n_distinct = o.n_distinct;
+    out->n_edges = n_recv;
+    out->words_per_edge = 2;
+    out->item_words = 3;
+  }
 }
 
 int run_count(mhx_ctx *c, uint32_t k, uint32_t m, mhx_count_result *out) {

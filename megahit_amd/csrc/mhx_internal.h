@@ -241,7 +241,7 @@ struct SkmFront {
   uint32_t n_bins, max_bin;
   uint32_t bin_lo, bin_hi;  // the bins of this pass / of this owner
   int bin_bits;
-  unsigned long long *hp;   // one GPU: the homopolymer windows counted beside the records ([0..1] counts, [2..3] a position each), else nullptr
+  unsigned long long *hp;   // the homopolymer windows counted beside the records (stage 1, one GPU: [0..1] counts, [2..3] a position each; count: [8..]), else nullptr
 };
 bool s1_skm_applies(const mhx_ctx *c, uint32_t k, uint32_t m, int want_mercy);
 bool s1_skm_dist_applies(const mhx_ctx *c, uint32_t k, uint32_t m);
@@ -338,6 +338,9 @@ struct CountStreamOut {
   std::string plan;
   unsigned long long *events;  // several GPUs: position << 1 | kind, for the ranks that hold the reads (count.hip k_apply_count_events)
   uint64_t n_events;
+  // count_skm_owner: `events` are still per-workgroup regions of ev_cap entries, ev_counts[workgroup] of them filled
+  uint32_t ev_cap = 0;
+  uint32_t *ev_counts = nullptr;
   // count on super-k-mer records: what a pass made (the caller sums the passes for the plan line)
   const unsigned long long *skm_hp = nullptr;  // the homopolymer windows k_skm_make counted beside the records (nullptr: none)
   uint64_t skm_records = 0, skm_windows = 0;
@@ -352,6 +355,16 @@ bool count_skm_groups(mhx_ctx *c, uint32_t k, uint32_t m, uint32_t *first_0_out,
                       int pass, int n_passes);
 void count_skm_hp_publish(mhx_ctx *c, const unsigned long long *hp, uint32_t k, uint32_t m, unsigned long long *hist, unsigned long long *edges_at,
                           uint64_t *n_edges, uint64_t *n_keys, bool *flagged);
+// ... on several GPUs, records exchanged by bin (comm.hip dist_count_skm; opt-in: count_skm_dist).  count_skm_owner (s1_skm.hip): the group-by over
+// the sources the ranks sent for this rank's bins, edges and events to per-workgroup regions.  count.hip: count_skm_dist_open readies the rank's
+// result arrays and runs it (-> false: a region overflowed), count_skm_dist_edges packs the solid edges (hp_sum: this rank publishes the homopolymer
+// keys of the tallies summed over the ranks) and splits them by the owner of their lv1 bucket (-> the send buffer, counts per owner),
+// count_skm_dist_close orders the n_recv edges received in ws "items_recv", publishes them and stashes the events for their route
+bool count_skm_dist_applies(const mhx_ctx *c, uint32_t k, uint32_t m);
+bool count_skm_owner(mhx_ctx *c, uint32_t k, uint32_t m, const SkmFront &f, unsigned long long *hist, CountStreamOut *o);
+bool count_skm_dist_open(mhx_ctx *c, uint32_t k, uint32_t m, const SkmFront &f, CountStreamOut *o);
+const uint32_t *count_skm_dist_edges(mhx_ctx *c, uint32_t k, uint32_t m, CountStreamOut *o, const unsigned long long *hp_sum, uint64_t *counts);
+void count_skm_dist_close(mhx_ctx *c, uint32_t k, uint32_t m, const SkmFront &f, const CountStreamOut &o, uint64_t n_recv, uint64_t n_items, mhx_count_result *out);
 bool count_presort_applies(const mhx_ctx *c, uint32_t k, uint32_t m);
 uint32_t *count_presort(mhx_ctx *c, uint32_t k, uint64_t *n_items, uint32_t **other, int *pbits);
 int count_process_presorted(mhx_ctx *c, uint32_t k, uint32_t m, const S1Sources &src, mhx_count_result *out);  // count.hip; -1: gave up

@@ -22,6 +22,7 @@
 //                 non-solid occurrences (:464, inverted: a key of count 1 < m has one record, whose position sits next to the key) and the
 //                 aggregated stage-2 items; several sources per bin (several GPUs: one per sending rank) and the marks as a list there
 //   k_count_skm   the same for `count`: in / out characters in the slot, packed edges out, the windows of flagged keys in a second expansion
+//                 (EVENTS, several GPUs: those windows leave as a list of events for the ranks that hold the reads)
 // 6.0 GB of records at 10 M reads instead of 16: the sort and the read of the group-by move 2.7 x fewer bytes.
 // Shapes: no mercy, no lv1 bucket filter (the path cuts large jobs into passes over ranges of its OWN bins), reads of one length or of
 // several, min count <= 2, 19 <= k <= 22 (count: 21), positions below 2^36; everything else — and any input with a bin that outgrows what
@@ -990,9 +991,14 @@ struct CountSkmArgs {
   uint64_t c_n_seqs;
   uint32_t c_fixed_len;
   uint32_t *first_0_out, *last_0_in_p1;
+  // EVENTS (several GPUs: the reads live on other ranks): per-workgroup regions of events, position << 1 | (1: first_0_out, 0: last_0_in) —
+  // what k_s1_stream<COUNT> writes and k_apply_count_events reads; ev_counts[workgroup] is the region's cursor (zero at launch)
+  unsigned long long *ev_raw;
+  uint32_t ev_cap;
+  uint32_t *ev_counts;
 };
 
-template <bool TAGS, int G>
+template <bool TAGS, int G, bool EVENTS = false>
 __global__ __launch_bounds__(kSkmThreads) void k_count_skm(SkmSrcs srcs, CountSkmArgs a, uint32_t *__restrict__ ticket) {
   constexpr int NT = kSkmThreads, NSLOT = 1 << kSkmLogSlots, W = NSLOT / NT;
   constexpr unsigned long long kEmpty = ~0ull;  // never a key: the bits below the (k+1)-mer are zero
@@ -1299,7 +1305,26 @@ __global__ __launch_bounds__(kSkmThreads) void k_count_skm(SkmSrcs srcs, CountSk
                   while (keys[h] != w.key) h = (h + 1) & (NSLOT - 1);
                   f = chw[h] >> 30;
                 }
-                if (f) {
+                if constexpr (EVENTS) {
+                  // the same as events for the ranks that hold the reads: one reservation per wavefront in this workgroup's region
+                  const uint32_t ne = (f & 1u) + (f >> 1);
+                  const uint32_t incl = wave_inclusive_sum(ne);
+                  const uint32_t tot = __shfl(incl, kWave - 1, kWave);
+                  if (tot) {  // (uniform)
+                    uint32_t ebase = 0;
+                    if (lane == 0) ebase = atomicAdd(&a.ev_counts[blockIdx.x], tot);
+                    ebase = __shfl(ebase, 0, kWave);
+                    if (ebase + tot > a.ev_cap || ebase + tot < ebase) {
+                      if (lane == 0) atomicOr(a.err, 2u);
+                    } else {
+                      const unsigned long long abs = ((unsigned long long)w.tag << 32) | w.pos;
+                      unsigned long long *const ev = a.ev_raw + (size_t)blockIdx.x * a.ev_cap;
+                      uint32_t at = ebase + incl - ne;
+                      if (f & 1u) ev[at++] = (abs << 1) | (w.fwd ? 0ull : 1ull);
+                      if (f & 2u) ev[at] = (abs << 1) | (w.fwd ? 1ull : 0ull);
+                    }
+                  }
+                } else if (f) {
                   // no in-edge (f & 1): strand 0 -> last_0_in = max(off), strand 1 -> first_0_out = min(off + 1); no out-edge (f & 2): the roles swap
                   const uint64_t abs = ((uint64_t)w.tag << 32) | w.pos;
                   const uint64_t rid = seq_of_offset(a.c_start, a.c_n_seqs, a.c_fixed_len, abs);
@@ -1426,9 +1451,10 @@ bool s1_skm_front(mhx_ctx *c, uint32_t k, SkmFront *f, int pass, int n_passes, i
   const unsigned grid = (unsigned)std::min<uint64_t>(div_ceil(n_blocks, (uint64_t)NT * J), grid_knob > 0 ? (uint64_t)grid_knob : cus * 8);
   const uint32_t n_bins = 1u << bin_bits;
   const uint32_t bin_lo = (uint32_t)((uint64_t)n_bins * pass / n_passes), bin_hi = (uint32_t)((uint64_t)n_bins * (pass + 1) / n_passes);
-  // homopolymer windows are counted beside the records on one GPU (several GPUs: they stay in the records; a job with many gives the path up)
+  // homopolymer windows are counted beside the records on one GPU (several GPUs, stage 1: they stay in the records; a job with many gives the
+  // path up.  count's tallies carry no position: on several GPUs the ranks add theirs up, comm.hip dist_count_skm)
   unsigned long long *hp = nullptr;
-  if (!c->global_bases && c->opt("s1_skm_hp", 1)) hp = c->ws("skm_hp", 512).as<unsigned long long>();  // [0..3] stage 1: windows per class, a position each; [8 + 16 class + ..] count: windows, bases in front, bases behind
+  if ((!c->global_bases || for_count) && c->opt("s1_skm_hp", 1)) hp = c->ws("skm_hp", 512).as<unsigned long long>();  // [0..3] stage 1: windows per class, a position each; [8 + 16 class + ..] count: windows, bases in front, bases behind
   unsigned long long hp_init[48] = {0};
   hp_init[2] = hp_init[3] = ~0ull;
   unsigned long long h[4] = {0, 0, 0, 0};
@@ -1582,60 +1608,146 @@ bool count_skm_applies(const mhx_ctx *c, uint32_t k, uint32_t m) {
   const uint64_t n_win = s.n_bases > s.n_seqs * (uint64_t)k ? s.n_bases - s.n_seqs * (uint64_t)k : 0;
   return knob >= 2 || c->opt("s1_skm", 1) >= 2 || n_win >= (uint64_t)c->opt("s1_skm_min_windows", 1 << 22);
 }
-// -> false: gave up (record array, a bin of low-complexity reads, an edge region): the caller's arrays may hold partial results of this attempt
-// (pass of n_passes: a job whose record arrays would take more than s1_skm_pass_gb runs in passes over ranges of bins, as stage 1 does; the
-//  caller packs every pass's edge regions behind the earlier passes' edges and orders them once at the end)
-bool count_skm_groups(mhx_ctx *c, uint32_t k, uint32_t m, uint32_t *first_0_out, uint32_t *last_0_in_p1, unsigned long long *hist, CountStreamOut *o, bool *touched,
-                      int pass, int n_passes) {
+// the group-by's launch over the sources of `f`, edges to `grid` regions of `region` entries in `edges_raw`.  ev_raw: the EVENTS form — the
+// windows of flagged keys leave as events in regions of ev_cap entries (several GPUs) instead of moving first_0_out / last_0_in here.
+// -> the kernel's error bits (0: done), the distinct keys in *n_distinct
+static uint32_t count_skm_launch(mhx_ctx *c, uint32_t k, uint32_t m, const SkmFront &f, unsigned grid, unsigned long long *edges_raw, uint32_t region, uint32_t *counts,
+                                 uint32_t *first_0_out, uint32_t *last_0_in_p1, unsigned long long *hist, unsigned long long *ev_raw, uint32_t ev_cap,
+                                 uint32_t *ev_counts, uint64_t *n_distinct) {
   SeqSet &s = c->seqs;
   hipStream_t st = c->stream;
-  SkmFront f{};
-  if (!s1_skm_front(c, k, &f, pass, n_passes, 0, true)) return false;
-  const uint64_t cus = c->n_cus > 0 ? (uint64_t)c->n_cus : 256;
-  const unsigned grid = (unsigned)std::min<uint64_t>(cus, std::max<uint64_t>(1, div_ceil((uint64_t)(f.bin_hi - f.bin_lo), (uint64_t)kSkmBatch)));
-  const uint32_t region = (uint32_t)std::min<uint64_t>(f.spare_bytes / 8 / grid, 0xFFFFFFF0u);
-  uint32_t *counts = c->ws("cs_edge_counts", (size_t)grid * 4).as<uint32_t>();
   unsigned long long *ctr = c->ws("s1_counters", 64).as<unsigned long long>();
   uint32_t *seg_err = c->ws("s1_seg_err", 64).as<uint32_t>();
   uint32_t *ticket = c->ws("s1_stream_ticket", 64).as<uint32_t>();
   MHX_HIP(hipMemsetAsync(ctr, 0, 64, st));
   MHX_HIP(hipMemsetAsync(seg_err, 0, 4, st));
   MHX_HIP(hipMemsetAsync(ticket, 0, 4, st));
+  if (ev_raw) MHX_HIP(hipMemsetAsync(ev_counts, 0, (size_t)grid * 4, st));
   const uint32_t nslot = 1u << kSkmLogSlots;
-  CountSkmArgs a{(int)k, m, hist, ctr, reinterpret_cast<unsigned long long *>(f.spare), region, counts, seg_err,
+  CountSkmArgs a{(int)k, m, hist, ctr, edges_raw, region, counts, seg_err,
                  (uint32_t)std::min<long long>(std::max<long long>(c->opt("s1_stream_fill", nslot * 7 / 8), 1), nslot), (int)std::min<long long>(c->opt("s1_stream_probes", 1024), 1024),
-                 f.bin_lo, f.bin_hi, s.start.as<uint64_t>(), s.n_seqs, s.fixed_len, first_0_out, last_0_in_p1};
+                 f.bin_lo, f.bin_hi, s.start.as<uint64_t>(), s.n_seqs, s.fixed_len, first_0_out, last_0_in_p1, ev_raw, ev_cap, ev_counts};
   SkmSrcs srcs{};
-  srcs.n = 1;
-  srcs.ptr[0] = f.src[0];
-  srcs.bounds[0] = f.src_bounds[0];
-  const bool tags = (s.n_bases >> 32) != 0 || c->opt("s1_skm_tags", 0) != 0;
-  *touched = true;
+  srcs.n = f.n_src;
+  for (int q = 0; q < f.n_src; ++q) {
+    srcs.ptr[q] = f.src[q];
+    srcs.bounds[q] = f.src_bounds[q];
+  }
+  const uint64_t n_bits = c->global_bases ? c->global_bases : s.n_bases;
+  const bool tags = (n_bits >> 32) != 0 || c->opt("s1_skm_tags", 0) != 0;
   const bool g2 = c->opt("count_skm_group", 2) == 2;  // (four chunks per round of compare-and-swaps spill registers here: measured 13.6 against 13.1 ms)
+#define MHX_CSKM(EV)                                                                                                                     \
+  do {                                                                                                                                   \
+    if (tags && g2) hipLaunchKernelGGL((k_count_skm<true, 2, EV>), dim3(grid), dim3(kSkmThreads), 0, st, srcs, a, ticket);                \
+    else if (tags) hipLaunchKernelGGL((k_count_skm<true, 4, EV>), dim3(grid), dim3(kSkmThreads), 0, st, srcs, a, ticket);                 \
+    else if (g2) hipLaunchKernelGGL((k_count_skm<false, 2, EV>), dim3(grid), dim3(kSkmThreads), 0, st, srcs, a, ticket);                  \
+    else hipLaunchKernelGGL((k_count_skm<false, 4, EV>), dim3(grid), dim3(kSkmThreads), 0, st, srcs, a, ticket);                          \
+  } while (0)
   MHX_LAUNCH(c, "count_skm_groups", (double)f.n_records * 16, {
-    if (tags && g2) hipLaunchKernelGGL((k_count_skm<true, 2>), dim3(grid), dim3(kSkmThreads), 0, st, srcs, a, ticket);
-    else if (tags) hipLaunchKernelGGL((k_count_skm<true, 4>), dim3(grid), dim3(kSkmThreads), 0, st, srcs, a, ticket);
-    else if (g2) hipLaunchKernelGGL((k_count_skm<false, 2>), dim3(grid), dim3(kSkmThreads), 0, st, srcs, a, ticket);
-    else hipLaunchKernelGGL((k_count_skm<false, 4>), dim3(grid), dim3(kSkmThreads), 0, st, srcs, a, ticket);
+    if (ev_raw) MHX_CSKM(true);
+    else MHX_CSKM(false);
   });
+#undef MHX_CSKM
   uint32_t e = 0;
   unsigned long long h_ctr[8] = {0};
   MHX_HIP(hipMemcpyAsync(&e, seg_err, 4, hipMemcpyDeviceToHost, st));
   MHX_HIP(hipMemcpyAsync(h_ctr, ctr, 64, hipMemcpyDeviceToHost, st));
   MHX_HIP(hipStreamSynchronize(st));
-  if (e) return false;
+  *n_distinct = h_ctr[4];
+  return e;
+}
+
+// -> false: gave up (record array, a bin of low-complexity reads, an edge region): the caller's arrays may hold partial results of this attempt
+// (pass of n_passes: a job whose record arrays would take more than s1_skm_pass_gb runs in passes over ranges of bins, as stage 1 does; the
+//  caller packs every pass's edge regions behind the earlier passes' edges and orders them once at the end)
+bool count_skm_groups(mhx_ctx *c, uint32_t k, uint32_t m, uint32_t *first_0_out, uint32_t *last_0_in_p1, unsigned long long *hist, CountStreamOut *o, bool *touched,
+                      int pass, int n_passes) {
+  SkmFront f{};
+  if (!s1_skm_front(c, k, &f, pass, n_passes, 0, true)) return false;
+  const uint64_t cus = c->n_cus > 0 ? (uint64_t)c->n_cus : 256;
+  const unsigned grid = (unsigned)std::min<uint64_t>(cus, std::max<uint64_t>(1, div_ceil((uint64_t)(f.bin_hi - f.bin_lo), (uint64_t)kSkmBatch)));
+  const uint32_t region = (uint32_t)std::min<uint64_t>(f.spare_bytes / 8 / grid, 0xFFFFFFF0u);
+  uint32_t *counts = c->ws("cs_edge_counts", (size_t)grid * 4).as<uint32_t>();
+  *touched = true;
+  uint64_t n_distinct = 0;
+  if (count_skm_launch(c, k, m, f, grid, reinterpret_cast<unsigned long long *>(f.spare), region, counts, first_0_out, last_0_in_p1, hist, nullptr, 0, nullptr, &n_distinct))
+    return false;
   o->grid = grid;
   o->cap = region;
   o->counts = counts;
   o->spare = f.spare;
   o->sorted = nullptr;
   if (pass == 0) o->n_items = f.n_items;
-  o->n_distinct = h_ctr[4];
+  o->n_distinct = n_distinct;
   o->events = nullptr;
   o->n_events = 0;
   o->skm_hp = f.hp;
   o->skm_records = f.n_records;
   o->skm_windows = f.n_windows;
+  o->skm_max_bin = f.max_bin;
+  o->skm_bin_bits = f.bin_bits;
+  return true;
+}
+
+// several GPUs (comm.hip dist_count_skm): this rank's say.  The shape of count_skm_applies under a global layout, at most kSkmSrcMax ranks (one
+// source per sender), no memory plan; a rank without a window (no reads, or none of k + 1 bases) takes part: it sends nothing and owns its bins
+bool count_skm_dist_applies(const mhx_ctx *c, uint32_t k, uint32_t m) {
+  const SeqSet &s = c->seqs;
+  if (!c->opt("count_skm", 1) || !c->opt("s1_skm", 1) || !c->opt("dist_skm", 1) || !c->opt("count_skm_dist", 0)) return false;
+  if (!c->global_bases || c->n_parts > kSkmSrcMax || c->filter_on || c->accumulate || (c->global_bases >> 36)) return false;
+  if (k < 19 || k > 21 || m < 1 || m > 2) return false;
+  if (s.n_seqs && s.max_len >= k + 1 && !s.fixed_len &&
+      (double)s.n_bases * 100.0 < (double)c->opt("s1_var_min_fill", 50) * (double)s.n_seqs * s.max_len)
+    return false;
+  return s1_skm_passes(c, k) == 1;
+}
+
+// the owner's half: the group-by over the sources the ranks sent for this rank's bins (f: n_src, src, src_bounds, bin_lo / bin_hi, n_records).  The
+// solid edges of the bins leave in `grid` regions (o->spare, o->cap, o->counts) and the events of the flagged keys' windows as one dense list
+// (o->events); `hist` takes the histogram of this owner's keys.  -> false: an edge or event region overflowed
+bool count_skm_owner(mhx_ctx *c, uint32_t k, uint32_t m, const SkmFront &f, unsigned long long *hist, CountStreamOut *o) {
+  hipStream_t st = c->stream;
+  const uint64_t cus = c->n_cus > 0 ? (uint64_t)c->n_cus : 256;
+  const unsigned grid = (unsigned)std::min<uint64_t>(cus, std::max<uint64_t>(1, div_ceil((uint64_t)(f.bin_hi - f.bin_lo), (uint64_t)kSkmBatch)));
+  // edge regions: two entries per record this owner holds, as on one GPU (there: the spare sort buffer), and at least 4096 a workgroup — the
+  // owner's records may be many more than the rank made; they go to a buffer of their own when the spare one is smaller
+  const uint64_t want = std::max<uint64_t>(f.n_records * 2, (uint64_t)grid * 4096);
+  unsigned long long *edges_raw = reinterpret_cast<unsigned long long *>(f.spare);
+  uint64_t have = f.spare ? f.spare_bytes / 8 : 0;
+  if (have < want) {
+    edges_raw = c->ws("cs_skm_owner_edges", want * 8 + 64).as<unsigned long long>();
+    have = want;
+  }
+  const uint32_t region = (uint32_t)std::min<uint64_t>(have / grid, 0xFFFFFFF0u);
+  // event regions: at most two per window of a solid key without an in- or out-edge (read ends, tips: a few per thousand windows);
+  // count_skm_ev_cap sets the entries of a region (tests)
+  const long long ev_knob = c->opt("count_skm_ev_cap", 0);
+  const uint64_t ev_total = std::max<uint64_t>(f.n_records / (uint64_t)std::max<long long>(c->opt("count_event_share", 4), 1) * 4, (uint64_t)grid * 4096);
+  const uint32_t ev_cap = ev_knob > 0 ? (uint32_t)std::min<long long>(ev_knob, 0xFFFFFFF0ll) : (uint32_t)std::min<uint64_t>(ev_total / grid, 0xFFFFFFF0u);
+  unsigned long long *ev_raw = c->ws("cs_events", (size_t)grid * ev_cap * 8 + 64).as<unsigned long long>();
+  uint32_t *counts = c->ws("cs_edge_counts", (size_t)grid * 4).as<uint32_t>();
+  uint32_t *ev_counts = c->ws("cs_event_counts", (size_t)grid * 4).as<uint32_t>();
+  uint64_t n_distinct = 0;
+  if (count_skm_launch(c, k, m, f, grid, edges_raw, region, counts, nullptr, nullptr, hist, ev_raw, ev_cap, ev_counts, &n_distinct)) return false;
+  std::vector<uint32_t> h_ec(grid);
+  MHX_HIP(hipMemcpyAsync(h_ec.data(), ev_counts, (size_t)grid * 4, hipMemcpyDeviceToHost, st));
+  MHX_HIP(hipStreamSynchronize(st));
+  uint64_t n_events = 0;
+  for (uint32_t v : h_ec) n_events += v;  // (no region overflowed: every cursor is within ev_cap)
+  o->grid = grid;
+  o->cap = region;
+  o->counts = counts;
+  o->spare = reinterpret_cast<uint32_t *>(edges_raw);
+  o->sorted = nullptr;
+  o->n_items = 0;
+  o->n_distinct = n_distinct;
+  o->events = ev_raw;  // (regions still: count.hip packs them)
+  o->n_events = n_events;
+  o->ev_cap = ev_cap;
+  o->ev_counts = ev_counts;
+  o->skm_hp = nullptr;
+  o->skm_records = f.n_records;
+  o->skm_windows = 0;
   o->skm_max_bin = f.max_bin;
   o->skm_bin_bits = f.bin_bits;
   return true;

@@ -1,9 +1,11 @@
 """Randomised libraries on 2-9 thread ranks through mhx_dist_read2sdbg with the super-k-mer exchange, against the oracle on the union (GPU).
+Every third job or so is a `count` instead (mhx_dist_count with count_skm_dist = 1: worlds 2-8, k 19-21, min count 1-2, the same knobs).
 
     python tools/fuzz_skm_dist.py [seconds] [seed]
 
 Sometimes one rank's shard is empty or degenerate (reads shorter than k + 1, a single homopolymer read): such a rank vetoes the
-super-k-mer exchange for every rank, as do nine ranks (more senders than k_s1_skm takes); the job then runs on the pre-sorted exchange."""
+super-k-mer exchange of read2sdbg for every rank, as do nine ranks (more senders than k_s1_skm takes); the job then runs on the pre-sorted
+exchange.  `count` keeps the route with ranks that hold no window; a lone homopolymer read makes its ranks give up together."""
 import os
 import sys
 import time
@@ -18,6 +20,7 @@ import oracle_binding as ob  # noqa: E402
 from megahit_amd import lib  # noqa: E402
 from fuzz_skm import library  # noqa: E402
 from test_gpu_comm import run_ranks, sdbg_of, check_sdbg  # noqa: E402
+from test_gpu_wide_worlds import check_count, count_job, shard_loader  # noqa: E402
 
 
 def main():
@@ -29,6 +32,10 @@ def main():
         rng = np.random.default_rng(seed)
         world = int(rng.integers(2, 10))
         k = int(rng.integers(19, 23))
+        crng = np.random.default_rng([seed, 7])  # (a stream of its own: a seed's read2sdbg job is what it was before `count` jobs were drawn)
+        counting = crng.random() < 0.35
+        if counting:
+            world, k = int(crng.integers(2, 9)), int(crng.integers(19, 22))
         shards = [library(np.random.default_rng(seed * 10 + r)) for r in range(world)]
         odd = ""
         if rng.random() < 0.25:  # one empty or degenerate shard
@@ -52,6 +59,24 @@ def main():
             opts["s1_skm_split_stage"] = int(rng.choice([0, 64, 700]))
         if rng.random() < 0.4:
             opts["s1_skm_make_grid"] = int(rng.choice([1, 2, 5]))
+
+        if counting:
+            m = int(crng.integers(1, 3))
+            opts["count_skm_dist"] = 1
+            if crng.random() < 0.3:
+                opts["count_skm_group"] = 4
+            outs = count_job(world, k, m, 3 * int(seed % 2), opts, shard_loader(shards))
+            try:
+                check_count(outs, ob.Package(sum(shards, []), reverse=True), k, m)
+            except AssertionError as ex:
+                print("seed %d: count, world %d k %d m %d %s *** %s | %s" % (seed, world, k, m, opts, ex, outs[0]["plan"]), flush=True)
+                sys.exit(1)
+            on_path += outs[0]["plan"].startswith("count: super-k-mers")
+            print("seed %d: count, world %d%s, %d reads, k %d, m %d, %s | %s" % (seed, world, " (%s shard)" % odd if odd else "", sum(len(s) for s in shards), k, m,
+                                                                                 " ".join("%s=%d" % kv for kv in sorted(opts.items()) if kv[0] not in ("s1_skm", "s1_var_min_fill", "s1_skm_cap_pct")),
+                                                                                 outs[0]["plan"][:47]), flush=True)
+            rounds += 1
+            continue
 
         def load(r, e):
             pkg = ob.Package(shards[r], reverse=True)
