@@ -164,6 +164,12 @@ int mhx_set_option(mhx_ctx *, const char *name, long long value);
  *                          kernel of read sets beyond 2^32 bases on any read set (tests); s1_skm_deal (1) 0: every lane expands its own
  *                          record instead of the wavefront's windows being dealt to the lanes (measured 7 % slower); s1_skm_hp (1) 0: the
  *                          windows of one base (poly-A, poly-G) stay in the records instead of being counted beside them (one GPU);
+ *                          s1_skm_rep (0) 1: the windows of period 2, 3 and 4 — (AC)n, (AAG)n, (AGAT)n microsatellites — are counted
+ *                          beside the records too, per entry of a table of 320 (the first four or three bases name the window), and
+ *                          published as keys behind the group-by: reads of such repeats no longer fill one bin and cost the path
+ *                          (stage 1 and count; looked at only where s1_skm_hp is on, on one GPU; the plan line says how many windows);
+ *                          s1_skm_rep_slots (64 = all): slots of the LDS hash in which a workgroup of the make kernel tallies those
+ *                          windows (48 in stage 1, 16 in count) — tests: few or 0, and the tallies go to the global table directly;
  *                          s1_skm_split (1): the make kernel puts every record into the range of its bin's low digit (256 ranges of the
  *                          array), so the sort starts at the second digit: one 16-byte pass fewer (bins of two digits or more; a range
  *                          that overflows — skewed bins — makes the records again, unsplit); 0: one cursor and all passes;

@@ -1047,6 +1047,16 @@ static bool count_run_stream(mhx_ctx *c, uint32_t k, uint32_t m, mhx_count_resul
       n_dist += nk;
       if (flagged) skm_done = false;  // (a solid homopolymer key without an in- or out-edge: its windows would move first_0_out / last_0_in)
     }
+    uint64_t n_rep = 0;
+    if (skm_done && o.skm_hp && o.skm_rep) {  // s1_skm_rep: the keys of the windows of period <= 4, the same way
+      unsigned long long *dense = grow_preserving(c, c->work["cs_edges_a"], (skm_edges + 320 + 1) * 8, skm_edges * 8).as<unsigned long long>();
+      uint64_t ne = 0, nk = 0;
+      bool flagged = false;
+      count_skm_rep_publish(c, o.skm_hp, k, m, hist, dense + skm_edges, &ne, &nk, &flagged, &n_rep);
+      skm_edges += ne;
+      n_dist += nk;
+      if (flagged) skm_done = false;
+    }
     o.n_distinct = n_dist;
     if (skm_done) {
       char txt[320];
@@ -1055,6 +1065,7 @@ static bool count_run_stream(mhx_ctx *c, uint32_t k, uint32_t m, mhx_count_resul
                s.fixed_len ? "" : " [reads of several lengths]");
       o.plan = txt;
       if (n_passes > 1) o.plan += " [" + std::to_string(n_passes) + " passes over ranges of bins]";
+      if (o.skm_rep) o.plan += " [" + std::to_string(n_rep) + " windows of period <= 4 beside the records]";
     }
     if (!skm_done) {
       // count_skm = 3: a caller that left the memory plan to this path (mhx_count_self_planned) hears that it did not serve

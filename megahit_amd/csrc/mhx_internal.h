@@ -242,6 +242,7 @@ struct SkmFront {
   uint32_t bin_lo, bin_hi;  // the bins of this pass / of this owner
   int bin_bits;
   unsigned long long *hp;   // the homopolymer windows counted beside the records (stage 1, one GPU: [0..1] counts, [2..3] a position each; count: [8..]), else nullptr
+  bool rep;                 // s1_skm_rep: the windows of period <= 4 were counted beside the records too, in the table behind hp (s1_skm.hip kSkmRepAt)
 };
 bool s1_skm_applies(const mhx_ctx *c, uint32_t k, uint32_t m, int want_mercy);
 bool s1_skm_dist_applies(const mhx_ctx *c, uint32_t k, uint32_t m);
@@ -255,6 +256,9 @@ struct DigitSpecs;
 // (agg_hist: the digit histograms of agg_specs that the items are added to, or nullptr)
 void s1_skm_hp_publish(mhx_ctx *c, const SkmFront &f, uint32_t k, uint32_t m, uint8_t *solid_bytes, unsigned long long *hist, uint2 *agg_items,
                        uint64_t *agg_cursor, bool agg, const DigitSpecs *agg_specs = nullptr, unsigned long long *agg_hist = nullptr);
+// (s1_skm_rep: the keys of the windows of period <= 4; -> how many windows were counted beside the records)
+uint64_t s1_skm_rep_publish(mhx_ctx *c, const SkmFront &f, uint32_t k, uint32_t m, uint8_t *solid_bytes, unsigned long long *hist, uint2 *agg_items,
+                            uint64_t *agg_cursor, bool agg, const DigitSpecs *agg_specs = nullptr, unsigned long long *agg_hist = nullptr);
 // the owner's half on several GPUs (s1.hip): group-by over the received sources, marks as a list, aggregated items.  -> false: a region overflowed
 bool s1_skm_owner(mhx_ctx *c, uint32_t k, uint32_t m, const SkmFront &f, mhx_s1_result *out);
 
@@ -343,6 +347,7 @@ struct CountStreamOut {
   uint32_t *ev_counts = nullptr;
   // count on super-k-mer records: what a pass made (the caller sums the passes for the plan line)
   const unsigned long long *skm_hp = nullptr;  // the homopolymer windows k_skm_make counted beside the records (nullptr: none)
+  bool skm_rep = false;                        // ... and the windows of period <= 4 in the table behind them (s1_skm_rep)
   uint64_t skm_records = 0, skm_windows = 0;
   uint32_t skm_max_bin = 0;
   int skm_bin_bits = 0;
@@ -355,6 +360,8 @@ bool count_skm_groups(mhx_ctx *c, uint32_t k, uint32_t m, uint32_t *first_0_out,
                       int pass, int n_passes);
 void count_skm_hp_publish(mhx_ctx *c, const unsigned long long *hp, uint32_t k, uint32_t m, unsigned long long *hist, unsigned long long *edges_at,
                           uint64_t *n_edges, uint64_t *n_keys, bool *flagged);
+void count_skm_rep_publish(mhx_ctx *c, const unsigned long long *hp, uint32_t k, uint32_t m, unsigned long long *hist, unsigned long long *edges_at,
+                           uint64_t *n_edges, uint64_t *n_keys, bool *flagged, uint64_t *n_windows);
 // ... on several GPUs, records exchanged by bin (comm.hip dist_count_skm; opt-in: count_skm_dist).  count_skm_owner (s1_skm.hip): the group-by over
 // the sources the ranks sent for this rank's bins, edges and events to per-workgroup regions.  count.hip: count_skm_dist_open readies the rank's
 // result arrays and runs it (-> false: a region overflowed), count_skm_dist_edges packs the solid edges (hp_sum: this rank publishes the homopolymer

@@ -891,6 +891,13 @@ struct S1Stage {
     if (agg) dense = grow_preserving(c, c->work["s2_agg_items"], (agg_prev + 4) * 8 + 64, agg_prev * 8).as<uint2>();  // (room for two keys' items)
     s1_skm_hp_publish(c, f, k, m, solid_bytes, hist, dense, agg_cursor, agg, &agg_specs, agg_hist);
   }
+  // ... and of the windows of period <= 4 (s1_skm_rep).  -> how many windows those were
+  uint64_t publish_skm_rep(const SkmFront &f) {
+    if (!f.hp || !f.rep) return 0;
+    uint2 *dense = nullptr;
+    if (agg) dense = grow_preserving(c, c->work["s2_agg_items"], (agg_prev + 4 + 2 * 320) * 8 + 64, (agg_prev + 4) * 8).as<uint2>();  // (two items per entry at most, behind publish_skm_hp's)
+    return s1_skm_rep_publish(c, f, k, m, solid_bytes, hist, dense, agg_cursor, agg, &agg_specs, agg_hist);
+  }
   void group_classic() {
     agg_prepare_classic();
     ensure_byte_map();
@@ -1299,6 +1306,7 @@ static bool s1_skm_try(mhx_ctx *c, uint32_t k, uint32_t m, mhx_s1_result *out, s
     max_bin = std::max(max_bin, f.max_bin);
   }
   stage.publish_skm_hp(f);
+  const uint64_t n_rep = stage.publish_skm_rep(f);
   stage.n_items = f.n_items;  // what the reference sorts (read_to_sdbg_s1.cpp:344-363)
   stage.mark_mode_used = 1;
   char txt[320];
@@ -1307,6 +1315,7 @@ static bool s1_skm_try(mhx_ctx *c, uint32_t k, uint32_t m, mhx_s1_result *out, s
            c->seqs.fixed_len ? "" : " [reads of several lengths]");
   c->last_s1_plan = txt;
   if (n_passes > 1) c->last_s1_plan += " [" + std::to_string(n_passes) + " passes over ranges of bins]";
+  if (f.rep) c->last_s1_plan += " [" + std::to_string(n_rep) + " windows of period <= 4 beside the records]";
   stage.publish(out);
   return true;
 }

@@ -11,7 +11,8 @@
 //                 digit (per workgroup and trip one reservation per digit, the records ordered by digit in an LDS stage before they
 //                 leave) — the group-by needs the records grouped by bin, in no order inside a bin, so the first sort pass need not be a
 //                 pass over an array this kernel has just written; the digit histograms of the sort passes on the way; windows of ONE
-//                 base (poly-A, poly-G) counted beside the records; COUNT: a base more either side.  (s1_skm_split = 0, a bin of one
+//                 base (poly-A, poly-G) counted beside the records — REP (s1_skm_rep): all windows of period <= 4, per entry of a table
+//                 of 320, made into keys by k_skm_rep_publish / k_count_rep_publish; COUNT: a base more either side.  (s1_skm_split = 0, a bin of one
 //                 digit, or a range that overflowed — skewed bins: the record array through one cursor, one atomic per workgroup and trip)
 //   radix_sort    ONE pass over the high digit of the 16-bit bin, reading the ranges in order (sort_kernels.h SrcSplit; stable, so its
 //                 output is ordered by the whole bin); a second beyond 2^16 bins; all digits when the records were not split
@@ -26,7 +27,8 @@
 // 6.0 GB of records at 10 M reads instead of 16: the sort and the read of the group-by move 2.7 x fewer bytes.
 // Shapes: no mercy, no lv1 bucket filter (the path cuts large jobs into passes over ranges of its OWN bins), reads of one length or of
 // several, min count <= 2, 19 <= k <= 22 (count: 21), positions below 2^36; everything else — and any input with a bin that outgrows what
-// one workgroup should stream (repeats other than homopolymers) — takes the prefix plan (s1_stream.hip).  DESIGN.md 4o.
+// one workgroup should stream (repeats other than homopolymers; with s1_skm_rep: other than reads of period <= 4 throughout) — takes the
+// prefix plan (s1_stream.hip).  DESIGN.md 4o.
 #include <cstring>
 
 #include "s1_shared.h"
@@ -68,7 +70,20 @@ __device__ __forceinline__ uint32_t skm_bin_of(uint32_t minh) {  // (the minimum
 // digit leave as one run.  A trip with more records than the stage holds (stage_n; uniform) writes them from the registers to the places
 // reserved.  A reservation beyond its range writes nothing and raises bit 1 of *err: the host makes the records again without the split.
 constexpr int kSkmStage = 2560;  // records the stage holds: a trip of 512 x 2 blocks makes 2330 of random sequence (0.284 per window)
-template <int NT, int J, bool VAR, bool COUNT = false, bool SPLIT = false>
+// REP (s1_skm_rep): windows of PERIOD <= 4 — (AC)n, (AAG)n, (AGAT)n microsatellites, and the homopolymers with them — never enter a record.
+// A (k+1)-mer of period p is its first p bases repeated; one of 20 bases and more with periods 3 and 4 has period 1 (Fine and Wilf).  So a
+// window whose period divides 4 is named by its first FOUR bases (entries 0..255) and one of period 3 that is no homopolymer by its first
+// THREE (entries 256..319): kSkmRepN direct-indexed entries behind hp[] — stage 1: [e] windows, [kSkmRepN + e] the smallest position of one;
+// count: [9 e] windows, [9 e + 1 + x] base x in front, [9 e + 5 + x] base x behind, in the READ's orientation ('$' untallied) — which
+// k_skm_rep_publish / k_count_rep_publish turn into keys.  A workgroup tallies the entries it meets in a small LDS hash (a library's
+// repeat-throughout reads fall into a handful: (AC)n reads into ACAC and CACA, their other strand into GTGT and TGTG) and adds it to the
+// global table ONCE, at its end.  The hash has what LDS is left beside the 81 032 bytes of the SPLIT form while two workgroups share a CU's
+// 160 KB: 48 slots of 16 bytes in stage 1, 16 slots of 40 bytes in the count form; an entry's slot is one of the kSkmRepProbes behind its
+// hash value.  An entry that finds none goes to the global table from the registers: the lanes of a wavefront that hold the same entry
+// (count: and the same bases either side) send ONE add between them — neighbouring lanes hold neighbouring blocks of the same reads.
+constexpr int kSkmRepN = 320, kSkmRepAt = 64;  // (the table starts kSkmRepAt values behind hp)
+constexpr int kSkmRepSlotsS1 = 48, kSkmRepSlotsCount = 16, kSkmRepProbes = 8;
+template <int NT, int J, bool VAR, bool COUNT = false, bool SPLIT = false, bool REP = false>
 __global__ __launch_bounds__(NT) void k_skm_make(const uint32_t *__restrict__ seq, const uint64_t *__restrict__ start, uint32_t L, uint32_t bpr, uint64_t n_blocks,
                                                  int k, int bin_bits, uint32_t bin_lo, uint32_t bin_hi, int count_items, uint64_t pos_base,
                                                  unsigned long long *__restrict__ hp, uint4 *__restrict__ out, unsigned long long cap,
@@ -83,7 +98,18 @@ __global__ __launch_bounds__(NT) void k_skm_make(const uint32_t *__restrict__ se
   __shared__ uint32_t dh[3][256];  // the digit histograms of the sort passes, taken while the records are made
   __shared__ uint32_t lbin[J * kSkmC][NT];  // a thread's bins, read back by window number when its records leave (no register array indexed by a variable)
   __shared__ uint32_t hpl[2][12];  // COUNT: the homopolymer windows of this workgroup per class: [0] windows, [1 + x] base x in front, [5 + x] base x behind
+  constexpr int kSkmRepSlots = COUNT ? kSkmRepSlotsCount : kSkmRepSlotsS1;
+  __shared__ uint32_t rid[REP ? kSkmRepSlots : 1];                    // REP: the entry a slot holds (kSkmRepN: none yet)
+  __shared__ uint32_t rtl[REP ? kSkmRepSlots : 1][COUNT ? 9 : 1];     // ... its windows (count: and the bases in front and behind)
+  __shared__ unsigned long long rps[REP && !COUNT ? kSkmRepSlots : 1];  // ... the smallest position of one (stage 1)
   const int tid = threadIdx.x;
+  if constexpr (REP) {
+    if (tid < kSkmRepSlots) {
+      rid[tid] = (uint32_t)kSkmRepN;
+      if constexpr (!COUNT) rps[tid] = ~0ull;
+    }
+    if (tid < kSkmRepSlots * (COUNT ? 9 : 1)) rtl[tid / (COUNT ? 9 : 1)][tid % (COUNT ? 9 : 1)] = 0;
+  }
   if (tid < 24) hpl[tid / 12][tid % 12] = 0;
   for (int i = tid; i < 768; i += NT) dh[i >> 8][i & 255] = 0;
   if (SPLIT && tid < 256) dcnt[tid] = 0;
@@ -113,6 +139,58 @@ __global__ __launch_bounds__(NT) void k_skm_make(const uint32_t *__restrict__ se
   // last window: fq0 = fnwin = 0)
   uint64_t fa[J];
   uint32_t fq0[J], fnwin[J], fc[J][COUNT ? 4 : 3];
+  // REP: one window of entry e (count: bases pv in front, nx behind, 4 = none; stage 1: at position p) -> its slot of the LDS hash, claimed
+  // with a compare-and-swap on the first meeting; none among its kSkmRepProbes places: the global table
+  [[maybe_unused]] auto rep_tally = [&](uint32_t e, unsigned pv, unsigned nx, uint64_t p) {
+    if constexpr (REP) {
+      unsigned long long *const tab = hp + kSkmRepAt;
+      // (hp[kSkmRepAt - 1]: the slots in use — all of them; s1_skm_rep_slots, tests: fewer, or none)
+      const uint32_t n_slots = min((uint32_t)hp[kSkmRepAt - 1], (uint32_t)kSkmRepSlots);
+      uint32_t h = n_slots ? (e ^ (e >> 4) ^ (e >> 6)) % n_slots : 0u;
+      int slot = -1;
+      for (int n = 0; n < kSkmRepProbes && n_slots; ++n) {
+        const uint32_t old = atomicCAS(&rid[h], (uint32_t)kSkmRepN, e);
+        if (old == (uint32_t)kSkmRepN || old == e) {
+          slot = (int)h;
+          break;
+        }
+        h = h + 1 == n_slots ? 0u : h + 1;
+      }
+      if (slot >= 0) {
+        atomicAdd(&rtl[slot][0], 1u);
+        if constexpr (COUNT) {
+          if (pv < 4) atomicAdd(&rtl[slot][1 + pv], 1u);
+          if (nx < 4) atomicAdd(&rtl[slot][5 + nx], 1u);
+        } else {
+          atomicMin(&rps[slot], (unsigned long long)p);
+        }
+      } else {
+        // the lanes that are here with one entry (count: and the same bases either side) take turns, entry by entry; the first of them adds for all
+        const uint32_t sig = COUNT ? e | ((uint32_t)pv << 9) | ((uint32_t)nx << 12) : e;
+        for (;;) {
+          const uint32_t s0 = (uint32_t)__builtin_amdgcn_readfirstlane((int)sig);
+          const unsigned long long together = __ballot(sig == s0);  // (asked by every lane still in the loop: the vote names exactly the lanes of this turn)
+          if (sig == s0) {
+            if ((tid & (kWave - 1)) == __builtin_ctzll(together)) {
+              const unsigned long long n = (unsigned long long)__builtin_popcountll(together);
+              if constexpr (COUNT) {
+                atomicAdd(tab + 9 * e, n);
+                if (pv < 4) atomicAdd(tab + 9 * e + 1 + pv, n);
+                if (nx < 4) atomicAdd(tab + 9 * e + 5 + nx, n);
+              } else {
+                atomicAdd(tab + e, n);
+              }
+            }
+            break;
+          }
+        }
+        if constexpr (!COUNT) {  // (the smallest position settles early — positions grow with the trips — and is then only read)
+          unsigned long long *const at = tab + kSkmRepN + e;
+          if ((unsigned long long)p < __hip_atomic_load(at, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMin(at, (unsigned long long)p);
+        }
+      }
+    }
+  };
   auto fetch = [&](uint64_t it2) {  // (called once per trip, in the order of the trips)
     uint64_t r = blk_r;
     uint32_t q = blk_q;
@@ -209,7 +287,39 @@ __global__ __launch_bounds__(NT) void k_skm_make(const uint32_t *__restrict__ se
           // a pass of the memory plan keeps the bins [bin_lo, bin_hi): the windows of a run share their bin, so runs stay whole
           const uint32_t n_here = min((uint32_t)kSkmC, nwin - q0);
           uint32_t km = 0, sm = 0, hm = 0;
-          if (hp) {  // (uniform) windows of one base: adjacent bases equal all along the window
+          if constexpr (REP) {
+            // window w has period p when base i equals base i + p for i = w .. w + K1 - p - 1.  Periods 1 and 2 imply 4: only 4 and 3 are
+            // looked for, each behind the test on the pairs that lie in EVERY window of the block (i = kSkmC - 1 .. K1 - 1 - p): a block of
+            // random sequence looks at no window
+            const uint64_t d4 = W ^ (W << 8), d3 = W ^ (W << 6);
+            uint32_t m4 = 0, m3 = 0;
+            if ((d4 & ((~0ull >> (2 * (kSkmC - 1))) & (~0ull << (64 - 2 * (K1 - 4))))) == 0) {
+#pragma unroll
+              for (int w = 0; w < kSkmC; ++w)
+                if ((uint32_t)w < n_here && ((d4 << (2 * w)) >> (64 - 2 * (K1 - 4))) == 0) m4 |= 1u << w;
+            }
+            if ((d3 & ((~0ull >> (2 * (kSkmC - 1))) & (~0ull << (64 - 2 * (K1 - 3))))) == 0) {
+#pragma unroll
+              for (int w = 0; w < kSkmC; ++w)
+                if ((uint32_t)w < n_here && ((d3 << (2 * w)) >> (64 - 2 * (K1 - 3))) == 0) m3 |= 1u << w;
+            }
+            hm = m4 | m3;
+            if (hm && count_items) {
+#pragma unroll
+              for (int w = 0; w < kSkmC; ++w)
+                if ((hm >> w) & 1u) {
+                  // (periods 3 and 4 together: a homopolymer, named by its four bases)
+                  const uint32_t e = (m4 >> w) & 1u ? (uint32_t)(W >> (56 - 2 * w)) & 255u : 256u + ((uint32_t)(W >> (58 - 2 * w)) & 63u);
+                  unsigned prev_raw = 4, next_raw = 4;
+                  if constexpr (COUNT) {
+                    prev_raw = q0 + w == 0 ? kSentinel
+                                           : (w == 0 ? (unsigned)((fc[j][COUNT ? 3 : 0] >> (30 - 2 * (unsigned)((a - 1) & 15))) & 3u) : (unsigned)(W >> (64 - 2 * w)) & 3u);
+                    next_raw = q0 + w + 1 == nwin ? kSentinel : (unsigned)(W >> (62 - 2 * (w + K1))) & 3u;
+                  }
+                  rep_tally(e, prev_raw, next_raw, pos_base + a + (uint64_t)w);
+                }
+            }
+          } else if (hp) {  // (uniform) windows of one base: adjacent bases equal all along the window
             const uint64_t dx = W ^ (W << 2);  // base i differs from base i + 1: bits 63 - 2i, 62 - 2i
             // (the bases kSkmC - 1 .. K1 - 1 lie in every window of the block: unless they are all equal, which is rare, no window is looked at)
             if ((dx & ((~0ull >> (2 * (kSkmC - 1))) & (~0ull << (64 - 2 * (K1 - 1))))) == 0) {
@@ -366,11 +476,21 @@ __global__ __launch_bounds__(NT) void k_skm_make(const uint32_t *__restrict__ se
     items = wave_sum(items);
     if ((tid & (kWave - 1)) == 0 && items) atomicAdd(cursor + 3, items);
   }
+  if constexpr (REP) {  // the workgroup's entries -> the global table, once
+    __syncthreads();
+    constexpr int NV = COUNT ? 9 : 1;
+    if (count_items && tid < kSkmRepSlots * NV) {
+      const uint32_t e = rid[tid / NV], v = rtl[tid / NV][tid % NV];
+      if (e < (uint32_t)kSkmRepN && v) atomicAdd(hp + kSkmRepAt + (COUNT ? 9 * e + (uint32_t)(tid % NV) : e), (unsigned long long)v);
+      if constexpr (!COUNT)
+        if (e < (uint32_t)kSkmRepN && v) atomicMin(hp + kSkmRepAt + kSkmRepN + e, rps[tid]);
+    }
+  }
   if constexpr (COUNT) {
     __syncthreads();
     if (hp && count_items && tid < 24 && hpl[tid / 12][tid % 12]) atomicAdd(hp + 8 + (tid / 12) * 16 + (tid % 12), (unsigned long long)hpl[tid / 12][tid % 12]);
   }
-  if (!COUNT && hp && count_items) {
+  if (!COUNT && !REP && hp && count_items) {
 #pragma unroll
     for (int x = 0; x < 2; ++x) {
       const uint32_t n_w = wave_sum(hp_n[x]);
@@ -388,6 +508,136 @@ __global__ __launch_bounds__(NT) void k_skm_make(const uint32_t *__restrict__ se
   __syncthreads();
   for (int i = tid; i < 768; i += NT)
     if (dh[i >> 8][i & 255]) atomicAdd(&digit_hist[i], (unsigned long long)dh[i >> 8][i & 255]);
+}
+
+// ---- the keys of the group-bys, shared with the publish kernels of the windows counted beside the records ----
+// stage 1 (read_to_sdbg_s1.cpp:228-292): the strand of the (k-1)-mer — f forward, rc its reverse complement —, then head / tail
+__device__ __forceinline__ unsigned long long skm_s1_key(uint64_t f, uint64_t rc, unsigned head, unsigned tail) {
+  const bool rev = f > rc || (f == rc && head > 3u - tail);
+  const uint64_t kf = f | ((uint64_t)head << 3) | tail, kr = rc | ((uint64_t)(3u - tail) << 3) | (3u - head);
+  return rev ? kr : kf;
+}
+// count (kmer_counter.cpp:179): the smaller of the (k+1)-mer and its reverse complement; *strand: the key is the reverse complement
+__device__ __forceinline__ unsigned long long skm_count_key(uint64_t x, uint64_t rcx, bool *strand) {
+  *strand = rcx < x;  // rev_edge.cmp(edge) < 0
+  return *strand ? rcx : x;
+}
+// the (k+1)-mer head.S.tail of a stage-1 key, MSB first, and the aggregated stage-2 item of a (k+1)-mer with multiplicity mul
+__device__ __forceinline__ uint64_t skm_s1_key_kmer(unsigned long long key, int k, uint64_t kmask) {
+  return ((uint64_t)((key >> 3) & 7u) << 62) | ((key & kmask) >> 2) | ((uint64_t)(key & 7u) << (62 - 2 * k));
+}
+__device__ __forceinline__ uint64_t skm_s2_item(uint64_t x, int k, uint64_t mul) {
+  return ((x << 2) & (~0ull << (64 - 2 * k))) | (1ull << 19) | ((x >> 62) << 16) | mul;
+}
+
+// the (k+1)-mer of period <= 4 that entry e of the REP table names (k_skm_make): its first four (e < 256) or three bases repeated, MSB first
+__device__ __forceinline__ uint64_t skm_rep_window(uint32_t e, int K1) {
+  const int p = e < 256u ? 4 : 3;
+  const uint64_t unit = e < 256u ? (uint64_t)e << 56 : (uint64_t)(e - 256u) << 58;
+  uint64_t x = 0;
+  for (int i = 0; i < 32; i += p) x |= unit >> (2 * i);
+  return x & (~0ull << (64 - 2 * K1));
+}
+
+// REP, stage 1: the at most kSkmRepN entries -> keys (distinct entries may give ONE key: a window and its reverse complement; the key
+// expression decides, its tie rule included) -> per key what the walk over the table does: histogram, the mark at the only window of a key
+// of count 1 < m, else the aggregated stage-2 items.  One workgroup.  res[0] = the windows counted beside the records, res[1] = the keys
+__global__ __launch_bounds__(kSkmRepN) void k_skm_rep_publish(const unsigned long long *__restrict__ tab, int k, uint32_t m, uint8_t *__restrict__ solid_bytes,
+                                                              unsigned long long *__restrict__ hist, uint2 *__restrict__ agg_items, unsigned long long *__restrict__ agg_cursor,
+                                                              int agg, DigitSpecs agg_specs, unsigned long long *__restrict__ agg_hist, unsigned long long *__restrict__ res) {
+  __shared__ unsigned long long s_key[kSkmRepN], s_cnt[kSkmRepN], s_pos[kSkmRepN];
+  __shared__ unsigned long long s_tot[2];
+  const int e = threadIdx.x, K1 = k + 1;
+  const uint64_t kmask = ~0ull << (64 - 2 * (k - 1));
+  if (e < 2) s_tot[e] = 0;
+  {
+    const uint64_t win = skm_rep_window((uint32_t)e, K1);
+    const uint64_t f = (win << 2) & kmask, rc = (rc64(win, 32) << (2 * (32 - k))) & kmask;
+    const unsigned head = (unsigned)(win >> 62), tail = (unsigned)(win >> (62 - 2 * k)) & 3u;
+    s_key[e] = skm_s1_key(f, rc, head, tail);
+    s_cnt[e] = tab[e];
+    s_pos[e] = tab[kSkmRepN + e];
+  }
+  __syncthreads();
+  unsigned long long cnt = 0, pos = ~0ull;
+  bool lead = s_cnt[e] != 0;
+  for (int o = 0; o < kSkmRepN; ++o)
+    if (s_cnt[o] && s_key[o] == s_key[e]) {
+      if (o < e) lead = false;  // (the first entry of a key publishes it)
+      cnt += s_cnt[o];
+      pos = min(pos, s_pos[o]);
+    }
+  if (!lead) cnt = 0;
+  if (cnt) {
+    atomicAdd(&s_tot[0], cnt);
+    atomicAdd(&s_tot[1], 1ull);
+    const unsigned long long hb = cnt > MHX_MAX_MUL ? (unsigned long long)MHX_MAX_MUL : cnt;
+    atomicAdd(&hist[hb], 1ull);  // :430-436
+    if (cnt < m) {
+      solid_bytes[pos] = 1;  // its only window is a non-solid occurrence
+    } else if (agg) {
+      const uint64_t x = skm_s1_key_kmer(s_key[e], k, kmask), xr = rc64(x, K1);
+      const int n_out = x == xr ? 1 : 2;
+      const unsigned long long at = atomicAdd(agg_cursor, (unsigned long long)n_out);
+      for (int y = 0; y < n_out; ++y) {
+        const uint64_t f = skm_s2_item(y ? xr : x, k, hb);
+        agg_items[at + y] = make_uint2((uint32_t)(f >> 32), (uint32_t)f);
+        if (agg_hist) {  // the digit histograms of stage 2's sort (k_agg_compact took those of the items before these)
+          const uint32_t w[2] = {(uint32_t)(f >> 32), (uint32_t)f};
+          for (int p = 0; p < agg_specs.n; ++p) atomicAdd(&agg_hist[p * 256 + words_digit2<2>(w, agg_specs.d[p])], 1ull);
+        }
+      }
+    }
+  }
+  __syncthreads();
+  if (e < 2) res[e] = s_tot[e];
+}
+
+// REP, count: the entries -> canonical (k+1)-mers, the tallies of the bases either side moved into the key's orientation (an entry that is
+// its key's reverse complement: in front and behind swap and complement), equal keys merged -> what k_count_hp_publish does per key.
+// res[0] = edges appended, [1] = keys, [2] = a solid key lacks an in- or out-edge, [3] = the windows counted beside the records
+__global__ __launch_bounds__(kSkmRepN) void k_count_rep_publish(const unsigned long long *__restrict__ tab, int k, uint32_t m, unsigned long long *__restrict__ hist,
+                                                                unsigned long long *__restrict__ edges_at, unsigned long long *__restrict__ res) {
+  __shared__ unsigned long long s_key[kSkmRepN], s_t[kSkmRepN][9];
+  __shared__ unsigned long long s_res[4];
+  const int e = threadIdx.x, K1 = k + 1;
+  if (e < 4) s_res[e] = 0;
+  {
+    const uint64_t x = skm_rep_window((uint32_t)e, K1);
+    bool strand;
+    s_key[e] = skm_count_key(x, rc64(x, K1), &strand);
+    const unsigned long long *t = tab + 9 * e;
+    s_t[e][0] = t[0];
+    for (int c = 0; c < 4; ++c) {
+      s_t[e][1 + c] = strand ? t[5 + (3 - c)] : t[1 + c];
+      s_t[e][5 + c] = strand ? t[1 + (3 - c)] : t[5 + c];
+    }
+  }
+  __syncthreads();
+  unsigned long long t[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
+  bool lead = s_t[e][0] != 0;
+  for (int o = 0; o < kSkmRepN; ++o)
+    if (s_t[o][0] && s_key[o] == s_key[e]) {
+      if (o < e) lead = false;
+      for (int c = 0; c < 9; ++c) t[c] += s_t[o][c];
+    }
+  if (lead && t[0]) {
+    atomicAdd(&s_res[1], 1ull);
+    atomicAdd(&s_res[3], t[0]);
+    const unsigned long long hb = t[0] > MHX_MAX_MUL ? (unsigned long long)MHX_MAX_MUL : t[0];
+    atomicAdd(&hist[hb], 1ull);
+    if (t[0] >= m) {
+      bool has_in = false, has_out = false;
+      for (int c = 0; c < 4; ++c) {
+        has_in = has_in || t[1 + c] >= m;
+        has_out = has_out || t[5 + c] >= m;
+      }
+      if (!has_in || !has_out) s_res[2] = 1;
+      edges_at[atomicAdd(&s_res[0], 1ull)] = s_key[e] | hb;  // PackEdge, kmer_counter.cpp:32-52
+    }
+  }
+  __syncthreads();
+  if (e < 4) res[e] = s_res[e];
 }
 
 // the one or two keys the homopolymer windows are (A...A with T...T, C...C with G...G): histogram, the mark of a key seen once, the
@@ -524,8 +774,7 @@ __global__ __launch_bounds__(kSkmThreads) void k_s1_skm(SkmSrcs srcs, SkmArgs a,
     uint64_t x = 0, xr = 0;
     uint32_t n_out = 0;
     if (valid) {
-      const uint64_t smer = key & kmask;
-      x = ((uint64_t)((key >> 3) & 7u) << 62) | (smer >> 2) | ((uint64_t)(key & 7u) << (62 - 2 * k));
+      x = skm_s1_key_kmer(key, k, kmask);
       xr = rc64(x, K1);
       n_out = x == xr ? 1u : 2u;
     }
@@ -549,12 +798,11 @@ __global__ __launch_bounds__(kSkmThreads) void k_s1_skm(SkmSrcs srcs, SkmArgs a,
       return;
     }
     if (n_out) {
-      const uint64_t mask_k = ~0ull << (64 - 2 * k);
       const uint64_t mul = cnt > MHX_MAX_MUL ? (uint64_t)MHX_MAX_MUL : cnt;
-      const uint64_t f = ((x << 2) & mask_k) | (1ull << 19) | ((x >> 62) << 16) | mul;
+      const uint64_t f = skm_s2_item(x, k, mul);
       agg_end[-1 - (long)at] = make_uint2((uint32_t)(f >> 32), (uint32_t)f);
       if (n_out == 2) {
-        const uint64_t b = ((xr << 2) & mask_k) | (1ull << 19) | ((xr >> 62) << 16) | mul;
+        const uint64_t b = skm_s2_item(xr, k, mul);
         agg_end[-2 - (long)at] = make_uint2((uint32_t)(b >> 32), (uint32_t)b);
       }
     }
@@ -652,9 +900,7 @@ __global__ __launch_bounds__(kSkmThreads) void k_s1_skm(SkmSrcs srcs, SkmArgs a,
                 const uint64_t f = (win << 2) & kmask;
                 const uint64_t rc = ((((uint64_t)xqh << 32) | xql) << (2 * (32 - k - j))) & kmask;
                 const unsigned head = (unsigned)(win >> 62), tail = ((uint32_t)win >> (62 - 2 * k)) & 3u;  // (k <= 22: the tail sits in the low word)
-                const bool rev = f > rc || (f == rc && head > 3u - tail);  // read_to_sdbg_s1.cpp:228-292
-                const uint64_t kf = f | ((uint64_t)head << 3) | tail, kr = rc | ((uint64_t)(3u - tail) << 3) | (3u - head);
-                key[u] = rev ? kr : kf;
+                key[u] = skm_s1_key(f, rc, head, tail);
                 const uint32_t klo = (uint32_t)key[u], khi = (uint32_t)(key[u] >> 32);
                 bool mn = g < T;
                 if (sub) mn = mn && (skm_mix2((klo * 0xC2B2AE35u) ^ (khi * 0x27D4EB2Fu)) >> (32 - sub)) == rj;  // (uniform branch)
@@ -729,9 +975,7 @@ __global__ __launch_bounds__(kSkmThreads) void k_s1_skm(SkmSrcs srcs, SkmArgs a,
                 const uint64_t f = (win << 2) & kmask;
                 const uint64_t rc = (rec_r << (2 * (32 - k - j))) & kmask;
                 const unsigned head = (unsigned)(win >> 62), tail = (unsigned)(win >> (62 - 2 * k)) & 3u;
-                const bool rev = f > rc || (f == rc && head > 3u - tail);  // read_to_sdbg_s1.cpp:228-292
-                const uint64_t kf = f | ((uint64_t)head << 3) | tail, kr = rc | ((uint64_t)(3u - tail) << 3) | (3u - head);
-                key[u] = rev ? kr : kf;
+                key[u] = skm_s1_key(f, rc, head, tail);
                 const uint32_t klo = (uint32_t)key[u], khi = (uint32_t)(key[u] >> 32);
                 bool mn = (uint32_t)j < len;
                 if (sub) mn = mn && (skm_mix2((klo * 0xC2B2AE35u) ^ (khi * 0x27D4EB2Fu)) >> (32 - sub)) == rj;  // (uniform branch)
@@ -1082,9 +1326,9 @@ __global__ __launch_bounds__(kSkmThreads) void k_count_skm(SkmSrcs srcs, CountSk
     const uint64_t rcx = (R << (2 * (32 - 1 - K1 - j))) & kmask;     // its reverse complement: a sub-window of the record's
     const unsigned pb = (unsigned)(B >> (62 - 2 * j)) & 3u, nb = (unsigned)(B >> (60 - 2 * K1 - 2 * j)) & 3u;
     const unsigned prev = j == 0 && (mo & 16u) ? kSentinel : pb, next = j + 1 == (mo >> 8) && (mo & 8u) ? kSentinel : nb;
-    const bool strand = rcx < x;  // rev_edge.cmp(edge) < 0, kmer_counter.cpp:179
+    bool strand;
+    w.key = skm_count_key(x, rcx, &strand);
     w.fwd = !strand;
-    w.key = strand ? rcx : x;
     w.pv = strand ? comp_or_sentinel(next) : prev;
     w.nx = strand ? comp_or_sentinel(prev) : next;
     w.pos = pdo + g;
@@ -1455,12 +1699,19 @@ bool s1_skm_front(mhx_ctx *c, uint32_t k, SkmFront *f, int pass, int n_passes, i
   // path up.  count's tallies carry no position: on several GPUs the ranks add theirs up, comm.hip dist_count_skm)
   unsigned long long *hp = nullptr;
   if ((!c->global_bases || for_count) && c->opt("s1_skm_hp", 1)) hp = c->ws("skm_hp", 512).as<unsigned long long>();  // [0..3] stage 1: windows per class, a position each; [8 + 16 class + ..] count: windows, bases in front, bases behind
+  // s1_skm_rep: the windows of period <= 4 join them (k_skm_make<.., REP>) — looked at only where the homopolymer windows are counted aside,
+  // on one GPU; the table sits behind the homopolymer counters
+  const bool rep = hp && !c->global_bases && c->n_parts <= 1 && c->opt("s1_skm_rep", 0) != 0;
+  if (rep) hp = c->ws("skm_hp", (size_t)(kSkmRepAt + kSkmRepN * 9) * 8).as<unsigned long long>();
+  // (s1_skm_rep_slots: slots of a workgroup's LDS hash in use — tests: few or none, and the entries go to the global table from the registers)
+  const unsigned long long rep_slots = (unsigned long long)std::min<long long>(std::max<long long>(c->opt("s1_skm_rep_slots", 64), 0), 64);
   unsigned long long hp_init[48] = {0};
   hp_init[2] = hp_init[3] = ~0ull;
   unsigned long long h[4] = {0, 0, 0, 0};
   std::vector<unsigned long long> h_dh(passes.size() * 256), h_fill(256);
-#define MHX_MAKE(VARV, COUNTV, SPLITV)                                                                                                                                   \
-  hipLaunchKernelGGL((k_skm_make<NT, J, VARV, COUNTV, SPLITV>), dim3(grid), dim3(NT), 0, st, s.words.as<uint32_t>(), s.start.as<uint64_t>(), L, bpr, n_blocks, (int)k, \
+#define MHX_MAKE(VARV, COUNTV, SPLITV) MHX_MAKE_R(VARV, COUNTV, SPLITV, false)
+#define MHX_MAKE_R(VARV, COUNTV, SPLITV, REPV)                                                                                                                           \
+  hipLaunchKernelGGL((k_skm_make<NT, J, VARV, COUNTV, SPLITV, REPV>), dim3(grid), dim3(NT), 0, st, s.words.as<uint32_t>(), s.start.as<uint64_t>(), L, bpr, n_blocks, (int)k, \
                      bin_bits, bin_lo, bin_hi, pass == 0 ? 1 : 0, c->pos_base, hp, buf_a, (unsigned long long)cap, cursor, err, pre_hist,                            \
                      (unsigned long long)range_cap, split_cur, stage_n)
   // everything the kernel counts starts from zero — also when the records are made a second time
@@ -1469,8 +1720,23 @@ bool s1_skm_front(mhx_ctx *c, uint32_t k, SkmFront *f, int pass, int n_passes, i
     MHX_HIP(hipMemsetAsync(pre_hist, 0, (size_t)3 * 256 * 8, st));
     if (split_now) MHX_HIP(hipMemsetAsync(split_cur, 0, 256 * 8, st));
     if (hp && pass == 0) MHX_HIP(hipMemcpyAsync(hp, hp_init, sizeof hp_init, hipMemcpyHostToDevice, st));
+    if (rep && pass == 0) {  // counts from zero, positions (stage 1: the second kSkmRepN values) from the largest
+      MHX_HIP(hipMemsetAsync(hp + kSkmRepAt, 0, (size_t)kSkmRepN * 9 * 8, st));
+      MHX_HIP(hipMemcpyAsync(hp + kSkmRepAt - 1, &rep_slots, 8, hipMemcpyHostToDevice, st));
+      if (!for_count) MHX_HIP(hipMemsetAsync(hp + kSkmRepAt + kSkmRepN, 0xFF, (size_t)kSkmRepN * 8, st));
+    }
     MHX_LAUNCH(c, for_count ? "count_skm_make" : "s1_skm_make", (double)s.n_bases / 4 + (double)n_win * 16 / 3.5, {
-      if (split_now) {
+      if (rep && split_now) {
+        if (var && for_count) MHX_MAKE_R(true, true, true, true);
+        else if (var) MHX_MAKE_R(true, false, true, true);
+        else if (for_count) MHX_MAKE_R(false, true, true, true);
+        else MHX_MAKE_R(false, false, true, true);
+      } else if (rep) {
+        if (var && for_count) MHX_MAKE_R(true, true, false, true);
+        else if (var) MHX_MAKE_R(true, false, false, true);
+        else if (for_count) MHX_MAKE_R(false, true, false, true);
+        else MHX_MAKE_R(false, false, false, true);
+      } else if (split_now) {
         if (var && for_count) MHX_MAKE(true, true, true);
         else if (var) MHX_MAKE(true, false, true);
         else if (for_count) MHX_MAKE(false, true, true);
@@ -1493,12 +1759,14 @@ bool s1_skm_front(mhx_ctx *c, uint32_t k, SkmFront *f, int pass, int n_passes, i
     make(false);
   }
 #undef MHX_MAKE
+#undef MHX_MAKE_R
   if (split) {  // (no cursor of all records: they are what the ranges hold)
     h[0] = 0;
     for (int d = 0; d < 256; ++d) h[0] += h_fill[d];
   }
   f->n_records = 0;
   f->hp = hp;
+  f->rep = rep;
   if ((uint32_t)h[1] != 0 || h[0] > cap) return false;
   const uint64_t n = h[0];
   {  // a bin far over the limit shows in the digit histograms already — one value of EVERY digit stands out by its records: no need to
@@ -1682,6 +1950,7 @@ bool count_skm_groups(mhx_ctx *c, uint32_t k, uint32_t m, uint32_t *first_0_out,
   o->events = nullptr;
   o->n_events = 0;
   o->skm_hp = f.hp;
+  o->skm_rep = f.rep;
   o->skm_records = f.n_records;
   o->skm_windows = f.n_windows;
   o->skm_max_bin = f.max_bin;
@@ -1775,6 +2044,40 @@ void s1_skm_hp_publish(mhx_ctx *c, const SkmFront &f, uint32_t k, uint32_t m, ui
   if (agg_specs && agg_hist) specs = *agg_specs;
   MHX_LAUNCH(c, "s1_skm_hp", 64.0, hipLaunchKernelGGL(k_skm_hp_publish, dim3(1), dim3(64), 0, c->stream, f.hp, (int)k, m, solid_bytes, hist, agg_items, agg_cursor,
                                                        agg ? 1 : 0, specs, agg_specs ? agg_hist : nullptr));
+}
+
+// s1_skm_rep: the keys of the windows of period <= 4 counted by k_skm_make<.., REP> (after the last pass of the group-by; agg_items has room for
+// 2 kSkmRepN items).  -> the windows counted beside the records
+uint64_t s1_skm_rep_publish(mhx_ctx *c, const SkmFront &f, uint32_t k, uint32_t m, uint8_t *solid_bytes, unsigned long long *hist, uint2 *agg_items,
+                            uint64_t *agg_cursor, bool agg, const DigitSpecs *agg_specs, unsigned long long *agg_hist) {
+  if (!f.hp || !f.rep) return 0;
+  DigitSpecs specs;
+  specs.n = 0;
+  if (agg_specs && agg_hist) specs = *agg_specs;
+  unsigned long long *res = c->ws("skm_hp_res", 64).as<unsigned long long>();
+  MHX_LAUNCH(c, "s1_skm_rep", (double)kSkmRepN * 16,
+             hipLaunchKernelGGL(k_skm_rep_publish, dim3(1), dim3(kSkmRepN), 0, c->stream, f.hp + kSkmRepAt, (int)k, m, solid_bytes, hist, agg_items,
+                                reinterpret_cast<unsigned long long *>(agg_cursor), agg ? 1 : 0, specs, agg_specs ? agg_hist : nullptr, res));
+  unsigned long long h[2] = {0, 0};
+  MHX_HIP(hipMemcpyAsync(h, res, 16, hipMemcpyDeviceToHost, c->stream));
+  MHX_HIP(hipStreamSynchronize(c->stream));
+  return h[0];
+}
+
+// count: the same -> histogram, edges behind `edges_at` (room for kSkmRepN).  -> edges appended, keys, whether a solid one lacks an in- or
+// out-edge, and the windows counted beside the records
+void count_skm_rep_publish(mhx_ctx *c, const unsigned long long *hp, uint32_t k, uint32_t m, unsigned long long *hist, unsigned long long *edges_at,
+                           uint64_t *n_edges, uint64_t *n_keys, bool *flagged, uint64_t *n_windows) {
+  unsigned long long *res = c->ws("skm_hp_res", 64).as<unsigned long long>();
+  MHX_LAUNCH(c, "count_skm_rep", (double)kSkmRepN * 72,
+             hipLaunchKernelGGL(k_count_rep_publish, dim3(1), dim3(kSkmRepN), 0, c->stream, hp + kSkmRepAt, (int)k, m, hist, edges_at, res));
+  unsigned long long h[4] = {0, 0, 0, 0};
+  MHX_HIP(hipMemcpyAsync(h, res, 32, hipMemcpyDeviceToHost, c->stream));
+  MHX_HIP(hipStreamSynchronize(c->stream));
+  *n_edges = h[0];
+  *n_keys = h[1];
+  *flagged = h[2] != 0;
+  *n_windows = h[3];
 }
 
 // several GPUs: where the bins start in an array of records ordered by bin (a source of the owner's group-by)

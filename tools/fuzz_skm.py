@@ -1,11 +1,14 @@
 """Randomised libraries through stage 1 / count on super-k-mer records against the oracle (GPU).
 
-    python tools/fuzz_skm.py [seconds] [seed]
+    python tools/fuzz_skm.py [--repeats] [seconds] [seed]
 
 Every round draws a library (fixed or ragged read lengths, planted poly-X / short-period repeats / duplicated reads), k in 19..22,
 min count 1..2 and a set of knobs (bins, passes, table fill, probe limit, tags, dealing, cap), runs read2sdbg stage 1 + stage 2 and
 count through the C ABI and compares every output with oracle/ (is_solid, histogram, item count, SdBG bytes and tables; edges, per-bucket
-counts, first_0_out / last_0_in).  Prints a line per round; exits 1 at the first difference with the round's seed."""
+counts, first_0_out / last_0_in).  Prints a line per round; exits 1 at the first difference with the round's seed.
+--repeats: every round also plants tandem repeats of period 1..6 — reads that are one repeat throughout, at any phase, and stretches inside
+other reads — and draws s1_skm_rep (the windows of period <= 4 counted beside the records).  Drawn from a generator of their own: without
+the flag a seed gives the round it always gave."""
 import os
 import sys
 import time
@@ -20,7 +23,7 @@ from megahit_amd import lib, synth  # noqa: E402
 
 RESET = dict(s1_skm=1, s1_stream_fill=7168, s1_stream_probes=1024, s1_skm_max_bin=65536, s1_skm_bin_bits=0, s1_skm_tags=0, s1_skm_cap_pct=36, s1_var_min_fill=50,
              s1_skm_passes=0, s1_skm_deal=1, s1_skm_hp=1, count_skm=1, count_skm_group=2, s1_skm_split=1, s1_skm_split_stage=2560,
-             s1_skm_make_grid=0)
+             s1_skm_make_grid=0, s1_skm_rep=0)
 
 
 def library(rng):
@@ -37,6 +40,31 @@ def library(rng):
         reads += [reads[i].copy() for i in rng.integers(0, len(reads), size=int(rng.integers(1, 300)))]
     order = rng.permutation(len(reads))
     return [reads[i] for i in order]
+
+
+def plant_repeats(rng, reads):
+    """tandem repeats of period 1..6: whole reads at rotating phases, and stretches inside copies of the library's own reads"""
+    L = max(len(r) for r in reads)
+    out = list(reads)
+    for _ in range(int(rng.integers(1, 5))):
+        unit = rng.integers(0, 4, size=int(rng.integers(1, 7)), dtype=np.uint8)
+        n = int(rng.choice([1, 2, 3, 40, 700]))
+        if rng.random() < 0.5:
+            for i in range(n):
+                u = np.roll(unit, int(rng.integers(0, len(unit))) if rng.random() < 0.7 else 0)
+                r = np.tile(u, L)[: int(rng.integers(max(1, L // 2), L + 1))]
+                out.append((3 - r[::-1]).astype(np.uint8) if rng.random() < 0.3 else r)
+        else:
+            for i in range(min(n, 60)):
+                r = reads[int(rng.integers(0, len(reads)))].copy()
+                if len(r) < 8:
+                    continue
+                a = int(rng.integers(0, len(r)))
+                b = min(len(r), a + int(rng.integers(4, 60)))
+                r[a:b] = np.tile(unit, 64)[: b - a]
+                out.append(r)
+    order = rng.permutation(len(out))
+    return [out[i] for i in order]
 
 
 def knobs(rng):
@@ -71,8 +99,10 @@ def knobs(rng):
 
 
 def main():
-    seconds = float(sys.argv[1]) if len(sys.argv) > 1 else 60.0
-    seed0 = int(sys.argv[2]) if len(sys.argv) > 2 else 1
+    argv = [a for a in sys.argv[1:] if a != "--repeats"]
+    repeats = "--repeats" in sys.argv[1:]
+    seconds = float(argv[0]) if len(argv) > 0 else 60.0
+    seed0 = int(argv[1]) if len(argv) > 1 else 1
     e = lib.Engine(0)
     t0, rounds, on_path = time.time(), 0, 0
     while time.time() - t0 < seconds:
@@ -81,6 +111,10 @@ def main():
         reads = library(rng)
         k, m = int(rng.integers(19, 23)), int(rng.integers(1, 3))
         opts = knobs(rng)
+        if repeats:
+            rng_rep = np.random.default_rng([seed, 0x5EB])
+            reads = plant_repeats(rng_rep, reads)
+            opts["s1_skm_rep"] = int(rng_rep.random() < 0.8)
         pkg = ob.Package(reads, reverse=True)
         e.load_sequences(pkg.words(), pkg.n_seqs, 0, pkg.start())
         for n_, v in opts.items():
