@@ -268,7 +268,11 @@ enum mhx_buffer {
   MHX_BUF_UNITIG_OFFSET = 43,   /* uint64[n_vertices + 1]: where vertex v's text starts in MHX_BUF_UNITIG_SEQ */
   /* the --careful_bubble records of the last mhx_unitig_pop_bubbles call (below), in the order the reference writes them at -t 1 */
   MHX_BUF_UNITIG_BUBBLE_REC = 44, /* mhx_bubble_record[n_records] */
-  MHX_BUF_UNITIG_BUBBLE_SEQ = 45  /* char[]: the records' text ('ACGT'), back to back */
+  MHX_BUF_UNITIG_BUBBLE_SEQ = 45, /* char[]: the records' text ('ACGT'), back to back */
+  /* `local`, first half (mhx_local_map / mhx_local_collect, below) */
+  MHX_BUF_LOCAL_REC = 46,     /* mhx_local_record[n_reads] */
+  MHX_BUF_LOCAL_ITEMS = 47,   /* uint64[n_items]: the collector's encoded reads, grouped by contig, then end, ascending inside a group */
+  MHX_BUF_LOCAL_OFFSETS = 48  /* uint64[2 * n_contigs + 1]: the items of (contig c, end e) are [offsets[2c + e], offsets[2c + e + 1]) */
 };
 /* bytes currently held in a result buffer (0 if absent) */
 uint64_t mhx_buffer_bytes(const mhx_ctx *, int which);
@@ -508,6 +512,45 @@ typedef struct {
 } mhx_iterate_result;
 int mhx_iterate(mhx_ctx *, uint32_t k, uint32_t step, const uint32_t *contig_packed, uint64_t contig_words, uint64_t n_contigs,
                 const uint64_t *contig_start, mhx_iterate_result *out);
+
+/* ---- `local`, first half: reads mapped to contig ends for local assembly.  Replaces HashMapper (localasm/hash_mapper.cpp),
+ * MappingResultCollector (localasm/mapping_result_collector.h) and EstimateInsertSize / LocalRange / MapToContigs
+ * (localasm/local_assemble.cpp:83-223); AssembleAndOutput (the IDBA hash graph and contig graph, serial per contig end)
+ * stays with the caller.  Every result equals the reference's at any thread count (its single-end loop at -t 1: the
+ * `omp parallel` without `for` at :204 runs that loop once per thread).
+ *   mhx_local_index   the seed index over the contigs: packed as mhx_load_sequences takes them, forward, contigs shorter
+ *       than min_contig_len and loop contigs already dropped by the caller (ContigReader::SetMinLen / SetDiscardFlag); ids are
+ *       the indices.  Every sparsity-th seed of seed_kmer (1..32) bases, keyed by its canonical form; a key seen twice is never
+ *       used.  *index_size = distinct keys (the reference's "index size").  Contigs and table live in workspaces: mhx_trim and
+ *       mhx_reset drop the index.  Fewer than 2^31 contigs, each shorter than 2^30 bases.
+ *   mhx_local_map     HashMapper::TryMap of every loaded read (FORWARD orientation: mhx_load_bin_records(..., reverse = 0))
+ *       into MHX_BUF_LOCAL_REC; *n_valid = records with valid != 0.  Without an index: the error "run mhx_local_index first".
+ *       Read ids of 2^44 and more are an error.  Loading or appending sequences afterwards invalidates the records:
+ *       mhx_local_collect then fails until mhx_local_map ran again.
+ *   mhx_local_insert_size  EstimateInsertSize + LocalRange of one library [lib_begin, lib_end) on those records; read_len[i] =
+ *       length of read i (indexed like rec).  Pure host code without a device call: works on a machine without a GPU.
+ *       Unpaired: mean = sd = 0.  *local_range = min(650, paired && mean >= max_read_len ? (int32) min(2 mean, mean + 3 sd)
+ *       : max_read_len - 1).
+ *   mhx_local_collect MapToContigs' AddSingle / AddMate of n_libs libraries, each with its own range (at most 2^14: larger
+ *       contig offsets do not fit the items and are an error; paired libraries hold an even number of reads), into
+ *       MHX_BUF_LOCAL_ITEMS / _OFFSETS: what MappingResultCollector::GetMappingResults returns for every (contig, end), end 0 =
+ *       the contig's start ("fwd"), values offset | is_mate:1 | min(mismatch, 15):4 | strand:1 | read id:44.  n_mapped[l] /
+ *       n_added[l] = "aligned" / "added" of library l. ---- */
+typedef struct {
+  uint32_t contig_id;
+  int32_t contig_from, contig_to; /* clipped to the contig, inclusive */
+  int32_t query_from, query_to;
+  uint32_t mismatch;
+  uint32_t strand;
+  uint32_t valid; /* 0: every other field is 0 */
+} mhx_local_record;
+int mhx_local_index(mhx_ctx *, const uint32_t *contig_packed, uint64_t contig_words, uint64_t n_contigs, const uint64_t *contig_start,
+                    uint32_t seed_kmer, uint32_t sparsity, uint64_t *index_size);
+int mhx_local_map(mhx_ctx *, int32_t min_mapping_len, double similarity, uint64_t *n_valid);
+int mhx_local_insert_size(const mhx_local_record *rec, const uint32_t *read_len, uint64_t lib_begin, uint64_t lib_end, uint32_t max_read_len,
+                          int paired, double *mean, double *sd, int32_t *local_range);
+int mhx_local_collect(mhx_ctx *, uint32_t n_libs, const uint64_t *lib_begin, const uint64_t *lib_end, const int32_t *lib_paired,
+                      const int32_t *lib_local_range, uint64_t *n_mapped, uint64_t *n_added);
 
 /* B3: sort n fixed-width records in place on the GPU, ascending by the first key_words words
  * (lexicographic on uint32, as Substr::operator<, kmsort_selector.cpp:18-27); aux words ride

@@ -139,6 +139,7 @@ void upload_sequences(mhx_ctx *c, const uint32_t *packed, uint64_t n_words, uint
   SeqSet &s = c->seqs;
   hipStream_t st = c->stream;
   c->s1.drop();
+  c->lm_mapped = false;  // the records of mhx_local_map belong to the reads they were made from
   s.n_seqs = n_seqs;
   s.fixed_len = start_pos ? 0 : fixed_len;
   s.n_words = n_words;
@@ -205,6 +206,7 @@ void append_sequences(mhx_ctx *c, const uint32_t *packed, uint64_t n_words, uint
   SeqSet &s = c->seqs;
   hipStream_t st = c->stream;
   c->s1.drop();
+  c->lm_mapped = false;  // the records of mhx_local_map belong to the reads they were made from
   if (n_new == 0) return;
   const uint64_t add_bases = start_pos ? start_pos[n_new] : n_new * (uint64_t)fixed_len;
   if (add_bases > n_words * 16) throw Error("append_sequences: start_pos/n_seqs exceed the packed buffer");
@@ -307,6 +309,7 @@ void upload_edges(mhx_ctx *c, const uint32_t *raw, uint64_t n_edges, uint32_t k,
   hipStream_t st = c->stream;
   SeqSet &s = c->seqs;
   c->s1.drop();
+  c->lm_mapped = false;  // the records of mhx_local_map belong to the reads they were made from
   const uint32_t len = k + 1;
   if (wpe != (len * 2 + 16 + 31) / 32) throw Error("load_edges: words_per_edge does not match k");
   uint32_t *d_raw = c->ws("edges_raw", (n_edges * wpe + 4) * 4).as<uint32_t>();
@@ -438,6 +441,7 @@ static bool upload_bin_records_fixed(mhx_ctx *c, const uint32_t *records, uint64
 
 void upload_bin_records(mhx_ctx *c, const uint32_t *records, uint64_t n_words, uint64_t n_seqs, int reverse) {
   c->s1.drop();
+  c->lm_mapped = false;  // the records of mhx_local_map belong to the reads they were made from
   if (upload_bin_records_fixed(c, records, n_words, n_seqs, reverse)) return;
   // lengths (host): an empty read becomes a 1-base 'A' (sequence_package.h:275-281)
   std::vector<uint64_t> rec_off(n_seqs + 1), start(n_seqs + 1);
@@ -569,6 +573,7 @@ int mhx_trim(mhx_ctx *c) {
     c->s1.drop_hist();  // (their rows went with ws "s2_pre_hist": stage 2's sort takes its histograms itself)
     // the unitig graph's cleaning state (owner map, flags, the edge ranking the owner map comes from) lives in workspaces
     c->ut_ready = c->ut_owner = false;
+    c->lm_ready = c->lm_mapped = false;  // the contigs and the seed table of mhx_local_index were workspaces
     // the sorted-items view aliases a workspace
     auto it = c->results.find(MHX_BUF_SORTED_ITEMS);
     if (it != c->results.end()) c->results.erase(it);
@@ -590,6 +595,7 @@ int mhx_reset(mhx_ctx *c) {
     if (it != c->results.end()) c->results.erase(it);
     c->sorted_item_words = 0;
     c->ut_ready = c->ut_owner = false;  // the vertex table is forgotten with the other results
+    c->lm_ready = c->lm_mapped = false;  // ... and the index of mhx_local_index with the other inputs
     c->my_part = 0;
     c->n_parts = 1;
     c->part_begin.clear();
@@ -854,6 +860,36 @@ int mhx_iterate(mhx_ctx *c, uint32_t k, uint32_t step, const uint32_t *contig_pa
     if (!out || (!contig_start && n_contigs)) throw mhx::Error("iterate: bad arguments");
     static const uint64_t zero = 0;
     mhx::iterate_edges(c, k, step, contig_packed, contig_words, n_contigs, n_contigs ? contig_start : &zero, out);
+  })
+}
+int mhx_local_index(mhx_ctx *c, const uint32_t *contig_packed, uint64_t contig_words, uint64_t n_contigs, const uint64_t *contig_start,
+                    uint32_t seed_kmer, uint32_t sparsity, uint64_t *index_size) {
+  MHX_TRY({
+    MHX_HIP(hipSetDevice(c->device));
+    if ((!contig_start && n_contigs) || (!contig_packed && contig_words)) throw mhx::Error("local_index: bad arguments");
+    static const uint64_t zero = 0;
+    mhx::local_index(c, contig_packed, contig_words, n_contigs, n_contigs ? contig_start : &zero, seed_kmer, sparsity, index_size);
+  })
+}
+int mhx_local_map(mhx_ctx *c, int32_t min_mapping_len, double similarity, uint64_t *n_valid) {
+  MHX_TRY({
+    MHX_HIP(hipSetDevice(c->device));
+    mhx::local_map(c, min_mapping_len, similarity, n_valid);
+  })
+}
+int mhx_local_insert_size(const mhx_local_record *rec, const uint32_t *read_len, uint64_t lib_begin, uint64_t lib_end, uint32_t max_read_len,
+                          int paired, double *mean, double *sd, int32_t *local_range) {
+  MHX_TRY({
+    if (lib_begin > lib_end || ((!rec || !read_len) && lib_end > lib_begin && paired)) throw mhx::Error("local_insert_size: bad arguments");
+    mhx::local_insert_size(rec, read_len, lib_begin, lib_end, max_read_len, paired, mean, sd, local_range);
+  })
+}
+int mhx_local_collect(mhx_ctx *c, uint32_t n_libs, const uint64_t *lib_begin, const uint64_t *lib_end, const int32_t *lib_paired,
+                      const int32_t *lib_local_range, uint64_t *n_mapped, uint64_t *n_added) {
+  MHX_TRY({
+    MHX_HIP(hipSetDevice(c->device));
+    if (n_libs && (!lib_begin || !lib_end || !lib_paired || !lib_local_range)) throw mhx::Error("local_collect: bad arguments");
+    mhx::local_collect(c, n_libs, lib_begin, lib_end, lib_paired, lib_local_range, n_mapped, n_added);
   })
 }
 int mhx_fastx_to_records(mhx_ctx *c, const char *text1, uint64_t n1, const char *text2, uint64_t n2, mhx_fastx_result *out) {

@@ -109,6 +109,29 @@ void read_lib_info(const std::string &prefix, int64_t *total_bases, int64_t *tot
   if (!f || !(f >> *total_bases >> *total_reads)) fatal("cannot read %s.lib_info", prefix.c_str());
 }
 
+std::vector<LibInfo> read_lib_info_libs(const std::string &prefix) {
+  std::ifstream f(prefix + ".lib_info");
+  int64_t total_bases = 0, total_reads = 0;
+  if (!f || !(f >> total_bases >> total_reads)) fatal("cannot read %s.lib_info", prefix.c_str());
+  std::string line;
+  std::getline(f, line);  // the rest of the totals' line
+  std::vector<LibInfo> libs;
+  while (std::getline(f, line)) {
+    LibInfo lib;
+    lib.description = line;
+    int paired = 0;
+    if (!(f >> lib.start >> lib.end >> lib.max_len >> paired)) {
+      if (line.find_first_not_of(" \t\r") == std::string::npos) break;  // a blank tail
+      fatal("%s.lib_info: no \"start end max_len is_paired\" line behind \"%s\"", prefix.c_str(), line.c_str());
+    }
+    lib.paired = paired != 0;
+    if (lib.start < 0 || lib.end < lib.start || lib.end > total_reads) fatal("%s.lib_info: library %zu lies outside the reads", prefix.c_str(), libs.size());
+    libs.push_back(lib);
+    std::getline(f, line);  // the rest of that line
+  }
+  return libs;
+}
+
 std::vector<uint32_t> read_bin_file(const std::string &path) {
   FILE *f = fopen(path.c_str(), "rb");
   if (!f) fatal("Cannot open %s", path.c_str());

@@ -28,6 +28,15 @@ struct PackedSeqs {
 
 // <prefix>.lib_info: total_bases total_reads (sequence_lib.cpp:84-90,93-99)
 void read_lib_info(const std::string &prefix, int64_t *total_bases, int64_t *total_reads);
+// the libraries of <prefix>.lib_info: behind the totals, per library a line of free text and a line "start end max_len is_paired"
+// (read ids [start, end); SequenceLib::DumpMetadata, SequenceLibCollection::Read sequence_lib.cpp:93-108)
+struct LibInfo {
+  int64_t start = 0, end = 0;
+  unsigned max_len = 0;
+  bool paired = false;
+  std::string description;
+};
+std::vector<LibInfo> read_lib_info_libs(const std::string &prefix);
 // whole <prefix>.bin record stream: per read uint32 len + ceil(len/16) words (sequence_package.h:224-240)
 std::vector<uint32_t> read_bin_file(const std::string &path);
 // offsets (in words) of each record in a .bin stream

@@ -104,6 +104,11 @@ struct mhx_ctx {
   // MHX_BUF_UNITIG_SEQ / _OFFSET describe the vertex table as it is now (no Refresh ran since they were written)
   bool ut_text_fresh = false;
   uint64_t ub_stats[4] = {0, 0, 0, 0};  // the last mhx_unitig_pop_bubbles: candidates, pairs passed, pairs failed, mid-run finishes
+  // `local`, first half (local_map.hip): the contigs and seed table of mhx_local_index live in workspaces "lm_*" (lm_ready: they are
+  // there); lm_mapped: MHX_BUF_LOCAL_REC holds the records of lm_n_reads loaded reads against that index
+  bool lm_ready = false, lm_mapped = false;
+  uint64_t lm_n_ctg = 0, lm_cap = 0, lm_n_reads = 0;
+  uint32_t lm_seed = 0;
   // tuning knobs (mhx_set_option): explicit value, else environment MHX_<NAME>, else the default
   std::map<std::string, long long> options;
   // tuned defaults of this installation: `name = value` lines of mhx_tuning.conf beside libmhx.so (MHX_TUNING_FILE names
@@ -323,6 +328,13 @@ int unitig_pop_bubbles(mhx_ctx *c, const mhx_sdbg_index_info *info, uint32_t max
 int unitig_similarity(mhx_ctx *c, const char *a, uint32_t n, const char *b, uint32_t m, double sim, double *out);
 int iterate_edges(mhx_ctx *c, uint32_t k, uint32_t step, const uint32_t *ctg_words, uint64_t ctg_n_words, uint64_t n_ctg, const uint64_t *ctg_start,
                   mhx_iterate_result *out);
+int local_index(mhx_ctx *c, const uint32_t *ctg_words, uint64_t ctg_n_words, uint64_t n_ctg, const uint64_t *ctg_start, uint32_t seed,
+                uint32_t sparsity, uint64_t *index_size);
+int local_map(mhx_ctx *c, int32_t min_mapping_len, double similarity, uint64_t *n_valid);
+int local_collect(mhx_ctx *c, uint32_t n_libs, const uint64_t *lib_begin, const uint64_t *lib_end, const int32_t *lib_paired,
+                  const int32_t *lib_local_range, uint64_t *n_mapped, uint64_t *n_added);
+int local_insert_size(const mhx_local_record *rec, const uint32_t *read_len, uint64_t lib_begin, uint64_t lib_end, uint32_t max_read_len,
+                      int paired, double *mean, double *sd, int32_t *local_range);
 int fastx_to_records(mhx_ctx *c, const char *text1, uint64_t n1, const char *text2, uint64_t n2, mhx_fastx_result *out);
 int sdbg_load_bytes(mhx_ctx *c, const uint8_t *bytes, uint64_t n_bytes, const uint64_t *off, const uint64_t *items, const uint64_t *tips,
                     const uint64_t *large);

@@ -37,7 +37,13 @@ BUF_UNITIG_SEQ = 42
 BUF_UNITIG_OFFSET = 43
 BUF_UNITIG_BUBBLE_REC = 44
 BUF_UNITIG_BUBBLE_SEQ = 45
+BUF_LOCAL_REC = 46
+BUF_LOCAL_ITEMS = 47
+BUF_LOCAL_OFFSETS = 48
 SIM_MAX_LEN, SIM_MAX_INDEL = 16384, 2047
+# one mhx_local_record (include/mhx.h)
+LOCAL_RECORD_DTYPE = np.dtype([("contig_id", np.uint32), ("contig_from", np.int32), ("contig_to", np.int32), ("query_from", np.int32),
+                               ("query_to", np.int32), ("mismatch", np.uint32), ("strand", np.uint32), ("valid", np.uint32)])
 # one mhx_bubble_record (include/mhx.h)
 BUBBLE_RECORD_DTYPE = np.dtype([("offset", np.uint64), ("length", np.uint32), ("vertex", np.uint32), ("avg_depth", np.float64)])
 UNITIG_LOOP, UNITIG_PALINDROME, UNITIG_STANDALONE, UNITIG_CHANGED = 1, 2, 4, 8
@@ -144,6 +150,11 @@ SYMBOLS = {
     "mhx_device_pointer": (_P, [_P, C.c_int]),
     "mhx_adopt_is_solid_slice": (C.c_int, [_P, _P, C.c_uint64]),
     "mhx_iterate": (C.c_int, [_P, C.c_uint32, C.c_uint32, _P, C.c_uint64, C.c_uint64, _P, C.POINTER(IterateResult)]),
+    "mhx_local_index": (C.c_int, [_P, _P, C.c_uint64, C.c_uint64, _P, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint64)]),
+    "mhx_local_map": (C.c_int, [_P, C.c_int32, C.c_double, C.POINTER(C.c_uint64)]),
+    "mhx_local_insert_size": (C.c_int, [_P, _P, C.c_uint64, C.c_uint64, C.c_uint32, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double),
+                                        C.POINTER(C.c_int32)]),
+    "mhx_local_collect": (C.c_int, [_P, C.c_uint32, _P, _P, _P, _P, _P, _P]),
     "mhx_fastx_to_records": (C.c_int, [_P, C.c_char_p, C.c_uint64, C.c_char_p, C.c_uint64, C.POINTER(FastxResult)]),
     "mhx_sdbg_build_index": (C.c_int, [_P, C.c_uint32, C.POINTER(SdbgIndexInfo)]),
     "mhx_sdbg_load_bytes": (C.c_int, [_P, _P, C.c_uint64, _P, _P, _P, _P]),
@@ -214,6 +225,20 @@ def load():
 
 def _ptr(a):
     return a.ctypes.data_as(C.c_void_p) if a is not None else None
+
+
+def local_insert_size(rec, read_len, lib_begin, lib_end, max_read_len, paired):
+    """EstimateInsertSize + LocalRange of one library on the records of Engine.local_map (include/mhx.h: mhx_local_insert_size);
+    host code only, needs no GPU.  rec: LOCAL_RECORD_DTYPE [n_reads], read_len: [n_reads].  -> (mean, sd, local_range)"""
+    L = load()
+    rec = np.ascontiguousarray(rec, dtype=LOCAL_RECORD_DTYPE)
+    read_len = np.ascontiguousarray(read_len, dtype=np.uint32)
+    assert lib_end <= rec.size and lib_end <= read_len.size
+    mean, sd, rng = C.c_double(0), C.c_double(0), C.c_int32(0)
+    if L.mhx_local_insert_size(_ptr(rec), _ptr(read_len), int(lib_begin), int(lib_end), int(max_read_len), int(bool(paired)), C.byref(mean),
+                               C.byref(sd), C.byref(rng)) != 0:
+        raise MhxError(L.mhx_last_error().decode())
+    return mean.value, sd.value, int(rng.value)
 
 
 class Engine:
@@ -425,6 +450,35 @@ class Engine:
         r = FastxResult()
         self._chk(self.lib.mhx_fastx_to_records(self.h, text1, len(text1), text2, len(text2) if text2 is not None else 0, C.byref(r)))
         return r, (self.fetch(BUF_LIB_RECORDS, np.uint32) if r.status == 0 else None)
+
+    # ---- `local`, first half (include/mhx.h: mhx_local_*)
+    def local_index(self, contig_packed, n_contigs, contig_start, seed_kmer=31, sparsity=8):
+        """the seed index over the (kept, forward) contigs; returns the number of distinct keys"""
+        contig_packed = np.ascontiguousarray(contig_packed, dtype=np.uint32)
+        contig_start = np.ascontiguousarray(contig_start, dtype=np.uint64)
+        n = C.c_uint64(0)
+        self._chk(self.lib.mhx_local_index(self.h, _ptr(contig_packed), contig_packed.size, int(n_contigs), _ptr(contig_start), int(seed_kmer),
+                                           int(sparsity), C.byref(n)))
+        return int(n.value)
+
+    def local_map(self, min_mapping_len=75, similarity=0.8):
+        """TryMap of every loaded (forward) read into BUF_LOCAL_REC; returns the number of valid records"""
+        n = C.c_uint64(0)
+        self._chk(self.lib.mhx_local_map(self.h, int(min_mapping_len), float(similarity), C.byref(n)))
+        return int(n.value)
+
+    def local_records(self):
+        return self.fetch(BUF_LOCAL_REC, np.uint8).view(LOCAL_RECORD_DTYPE)
+
+    def local_collect(self, libs):
+        """libs: [(begin, end, paired, local_range)] -> (aligned per library, added per library, items uint64, offsets uint64)"""
+        b = np.array([l[0] for l in libs], dtype=np.uint64)
+        e = np.array([l[1] for l in libs], dtype=np.uint64)
+        p = np.array([int(bool(l[2])) for l in libs], dtype=np.int32)
+        r = np.array([l[3] for l in libs], dtype=np.int32)
+        nm, na = np.zeros(len(libs), dtype=np.uint64), np.zeros(len(libs), dtype=np.uint64)
+        self._chk(self.lib.mhx_local_collect(self.h, len(libs), _ptr(b), _ptr(e), _ptr(p), _ptr(r), _ptr(nm), _ptr(na)))
+        return nm, na, self.fetch(BUF_LOCAL_ITEMS, np.uint64), self.fetch(BUF_LOCAL_OFFSETS, np.uint64)
 
     def sdbg_build_index(self, k):
         """W/last/tip/mul arrays + rank/select tables on the device (include/mhx.h: mhx_sdbg_build_index)."""
