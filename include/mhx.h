@@ -161,8 +161,13 @@ int mhx_set_option(mhx_ctx *, const char *name, long long value);
  *                          s1_skm_max_bin (65536): a bin of more records hands the job to the prefix plan (low-complexity reads);
  *                          s1_skm_pass_gb (48): both record arrays of a pass together — larger jobs run in passes over ranges of bins,
  *                          s1_skm_passes (0) forces their number; s1_skm_bin_bits (0 = by density: 16..20) the bins; s1_skm_tags (0) 1: the
- *                          kernel of read sets beyond 2^32 bases on any read set (tests); s1_skm_deal (1) 0: every lane expands its own
- *                          record instead of the wavefront's windows being dealt to the lanes (measured 7 % slower); s1_skm_hp (1) 0: the
+ *                          kernel of read sets beyond 2^32 bases on any read set (tests); s1_skm_deal (2): how the group-by hands a
+ *                          wavefront's windows to its lanes — 0: every lane expands its own record (measured 14 % slower than 2); 1: the
+ *                          windows are dealt to the lanes, 64 at a time, and a window's record comes over with six shuffles, the records'
+ *                          starts from a prefix sum of six more (8 % slower); 2: dealt, with three shuffles — the record's lane and the
+ *                          window's index in it come from the bitmap of run heads, the reverse complement from the window itself
+ *                          (csrc/skm_deal.h) — and the prefix sum and the trip's total from ballots, without the LDS (a value below 0 runs form
+ *                          0, one above 2 form 2); s1_skm_hp (1) 0: the
  *                          windows of one base (poly-A, poly-G) stay in the records instead of being counted beside them (one GPU);
  *                          s1_skm_rep (0) 1: the windows of period 2, 3 and 4 — (AC)n, (AAG)n, (AGAT)n microsatellites — are counted
  *                          beside the records too, per entry of a table of 320 (the first four or three bases name the window), and

@@ -32,6 +32,7 @@
 #include <cstring>
 
 #include "s1_shared.h"
+#include "skm_deal.h"
 
 namespace mhx {
 
@@ -729,8 +730,23 @@ struct SkmSrcs {
 
 constexpr int kSkmThreads = 1024, kSkmLogSlots = 13;
 
+// exclusive prefix sum over the wavefront of a value below 16, its total in *total (uniform): one ballot per bit, counted below the lane
+// and over the wavefront — a dozen vector and scalar instructions, where wave_inclusive_sum / wave_sum take six LDS round trips in a row
+__device__ __forceinline__ uint32_t wave_exclusive_sum_4bit(uint32_t v, uint32_t *total) {
+  uint32_t ex = 0, tot = 0;
+#pragma unroll
+  for (int b = 0; b < 4; ++b) {
+    const unsigned long long has = __ballot((v >> b) & 1u);
+    ex += __builtin_amdgcn_mbcnt_hi((uint32_t)(has >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)has, 0u)) << b;
+    tot += (uint32_t)__builtin_popcountll(has) << b;
+  }
+  *total = tot;
+  return ex;
+}
+
 // TAGS: read sets of 2^32 bases and more — the position bits above 32 ride in the record's first word and next to the key in the table
-template <bool AGG, bool TAGS, bool DEAL>
+// DEAL: 0 every lane expands its own record, 1 the windows are dealt to the lanes with six shuffles, 2 with three (skm_deal.h)
+template <bool AGG, bool TAGS, int DEAL>
 __global__ __launch_bounds__(kSkmThreads) void k_s1_skm(SkmSrcs srcs, SkmArgs a, uint32_t *__restrict__ ticket) {
   constexpr int NT = kSkmThreads, NSLOT = 1 << kSkmLogSlots, W = NSLOT / NT;
   constexpr unsigned long long kEmpty = ~0ull;  // never a key: head / tail bits 63 do not occur
@@ -858,15 +874,19 @@ __global__ __launch_bounds__(kSkmThreads) void k_s1_skm(SkmSrcs srcs, SkmArgs a,
             return true;
           };
           const uint64_t rec_b = ((uint64_t)r.y << 32) | r.z;
-          const uint64_t rec_r = rc64(rec_b, 32);  // (of the record's 32 base slots, once: a window's reverse complement is a sub-window of it)
-          if constexpr (DEAL) {
+          if constexpr (DEAL != 0) {
             // The windows of the wavefront's 64 records (~225) are DEALT to the lanes, 64 at a time: window g belongs to the record whose
             // run of windows starts at or before g — a bitmap of run heads per wavefront, one population count per window — and comes
-            // over with six shuffles.  All lanes work on every step (own-record expansion: 44 % of the lane steps, below); four steps
-            // share one round of compare-and-swaps and one retry loop.
-            const uint32_t incl = wave_inclusive_sum(len);
-            const uint32_t T = (uint32_t)__builtin_amdgcn_readlane((int)incl, kWave - 1);
-            const uint32_t start = incl - len;
+            // over with six shuffles (DEAL 1) or three (DEAL 2).  All lanes work on every step (own-record expansion: 44 % of the lane
+            // steps, below); four steps share one round of compare-and-swaps and one retry loop.
+            uint32_t start, T;  // the record's first window, and the windows of the trip (uniform)
+            if constexpr (DEAL == 2) {
+              start = wave_exclusive_sum_4bit(len, &T);  // (from ballots: DEAL 1 takes six dependent shuffles here, and six more for the claims below)
+            } else {
+              const uint32_t incl = wave_inclusive_sum(len);
+              T = (uint32_t)__builtin_amdgcn_readlane((int)incl, kWave - 1);
+              start = incl - len;
+            }
             // (the LDS executes a wavefront's operations in order: clear, set, read — no barrier between them)
             if (lane < 8) heads[wv][lane] = 0ull;
             __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
@@ -876,9 +896,17 @@ __global__ __launch_bounds__(kSkmThreads) void k_s1_skm(SkmSrcs srcs, SkmArgs a,
             __builtin_amdgcn_wave_barrier();
             const unsigned long long hv = __hip_atomic_load(&heads[wv][lane & 7], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
             const uint32_t hv_lo = (uint32_t)hv, hv_hi = (uint32_t)(hv >> 32);
-            const uint32_t bh = r.y, bl = r.z, qh = (uint32_t)(rec_r >> 32), ql = (uint32_t)rec_r;
-            const uint32_t pd = r.w - start;  // position of window g of the trip = pd + g
-            uint32_t cbase_m1 = 0xFFFFFFFFu;  // heads in front of this step's windows, minus one
+            const uint32_t bh = r.y, bl = r.z;
+            // DEAL 1 shuffles the record's reverse complement (of its 32 base slots, once: a window's is a sub-window of it) and its
+            // position less its start (position of window g of the trip = pd + g), and counts the heads in front of a step's windows,
+            // minus one; DEAL 2 carries that count and the windows behind the last head (skm_deal.h)
+            [[maybe_unused]] uint32_t qh = 0, ql = 0, pd = 0, cbase_m1 = 0xFFFFFFFFu;
+            [[maybe_unused]] SkmDealCarry dc;
+            if constexpr (DEAL == 1) {
+              const uint64_t rec_r = rc64(rec_b, 32);
+              qh = (uint32_t)(rec_r >> 32), ql = (uint32_t)rec_r;
+              pd = r.w - start;
+            }
 #pragma unroll
             for (int grp = 0; grp < 2; ++grp) {
               if ((uint32_t)(grp * 4 * kWave) >= T) break;  // (uniform)
@@ -888,27 +916,44 @@ __global__ __launch_bounds__(kSkmThreads) void k_s1_skm(SkmSrcs srcs, SkmArgs a,
 #pragma unroll
               for (int u = 0; u < 4; ++u) {
                 const int c = grp * 4 + u;
-                const uint32_t g = (uint32_t)(c * kWave) + (uint32_t)lane;
                 const uint32_t w_lo = (uint32_t)__builtin_amdgcn_readlane((int)hv_lo, c), w_hi = (uint32_t)__builtin_amdgcn_readlane((int)hv_hi, c);
-                const uint32_t o = cbase_m1 + (uint32_t)__builtin_popcount(w_lo & le_lo) + (uint32_t)__builtin_popcount(w_hi & le_hi);
-                cbase_m1 += (uint32_t)__builtin_popcount(w_lo) + (uint32_t)__builtin_popcount(w_hi);
-                const uint32_t xbh = __shfl(bh, (int)o, kWave), xbl = __shfl(bl, (int)o, kWave);
-                const uint32_t xqh = __shfl(qh, (int)o, kWave), xql = __shfl(ql, (int)o, kWave);
-                const uint32_t so = __shfl(start, (int)o, kWave), pdo = __shfl(pd, (int)o, kWave);
-                const uint32_t j = g - so;
-                const uint64_t win = (((uint64_t)xbh << 32) | xbl) << (2 * j);  // the (k+1)-mer head.S.tail, MSB first
+                // DEAL 2: the record's lane and the window's index in it come from the bitmap, the reverse complement from the window:
+                // three shuffles (the base bits, the position) where DEAL 1 has six
+                uint32_t o, j, xbh, xbl, p0;
+                uint64_t win, rc;
+                bool mn;  // the window is one of the trip's
+                if constexpr (DEAL == 2) {
+                  const SkmDealAt d = skm_deal_at(((uint64_t)w_hi << 32) | w_lo, (uint32_t)lane, dc);
+                  o = d.o;
+                  j = d.j & 7u;  // (a window past the end of the trip: any shift that is defined)
+                  xbh = __shfl(bh, (int)o, kWave), xbl = __shfl(bl, (int)o, kWave);
+                  p0 = __shfl(r.w, (int)o, kWave);
+                  win = (((uint64_t)xbh << 32) | xbl) << (2 * j);
+                  rc = skm_win_rc(win, k, kmask);
+                  pos[u] = p0 + j;
+                  mn = lane < (int)T - c * kWave;  // (g < T, against a scalar)
+                } else {
+                  const uint32_t g = (uint32_t)(c * kWave) + (uint32_t)lane;
+                  o = cbase_m1 + (uint32_t)__builtin_popcount(w_lo & le_lo) + (uint32_t)__builtin_popcount(w_hi & le_hi);
+                  cbase_m1 += (uint32_t)__builtin_popcount(w_lo) + (uint32_t)__builtin_popcount(w_hi);
+                  xbh = __shfl(bh, (int)o, kWave), xbl = __shfl(bl, (int)o, kWave);
+                  const uint32_t xqh = __shfl(qh, (int)o, kWave), xql = __shfl(ql, (int)o, kWave);
+                  const uint32_t so = __shfl(start, (int)o, kWave), pdo = __shfl(pd, (int)o, kWave);
+                  j = g - so;
+                  win = (((uint64_t)xbh << 32) | xbl) << (2 * j);  // the (k+1)-mer head.S.tail, MSB first
+                  rc = ((((uint64_t)xqh << 32) | xql) << (2 * (32 - k - j))) & kmask;
+                  pos[u] = pdo + g;
+                  p0 = pdo + so;
+                  mn = g < T;
+                }
                 const uint64_t f = (win << 2) & kmask;
-                const uint64_t rc = ((((uint64_t)xqh << 32) | xql) << (2 * (32 - k - j))) & kmask;
                 const unsigned head = (unsigned)(win >> 62), tail = ((uint32_t)win >> (62 - 2 * k)) & 3u;  // (k <= 22: the tail sits in the low word)
                 key[u] = skm_s1_key(f, rc, head, tail);
                 const uint32_t klo = (uint32_t)key[u], khi = (uint32_t)(key[u] >> 32);
-                bool mn = g < T;
                 if (sub) mn = mn && (skm_mix2((klo * 0xC2B2AE35u) ^ (khi * 0x27D4EB2Fu)) >> (32 - sub)) == rj;  // (uniform branch)
                 mine |= mn ? 1u << u : 0u;
                 h1[u] = ((klo * 0x9E3779B1u) ^ (khi * 0x85EBCA6Bu)) >> (32 - kSkmLogSlots);
-                pos[u] = pdo + g;
-                if constexpr (TAGS) {
-                  const uint32_t p0 = pdo + so;  // the record's own position word: a run across a multiple of 2^32 carries into the tag
+                if constexpr (TAGS) {  // (p0, the record's own position word: a run across a multiple of 2^32 carries into the tag)
                   tg[u] = (uint8_t)(__shfl((uint32_t)tag, (int)o, kWave) + (pos[u] < p0 ? 1u : 0u));
                 } else {
                   tg[u] = 0;
@@ -963,6 +1008,7 @@ __global__ __launch_bounds__(kSkmThreads) void k_s1_skm(SkmSrcs srcs, SkmArgs a,
           } else {
             // Every lane expands its own record, four windows at a time: the keys are independent of each other, so their compare-and-swaps
             // go out back to back and one LDS round trip serves four windows; lanes whose record is shorter idle.
+            const uint64_t rec_r = rc64(rec_b, 32);  // (of the record's 32 base slots, once: a window's reverse complement is a sub-window of it)
   #pragma unroll
             for (int half = 0; half < 2; ++half) {
               if (half == 1 && __ballot(len > 4u) == 0) break;  // (uniform)
@@ -1034,7 +1080,9 @@ __global__ __launch_bounds__(kSkmThreads) void k_s1_skm(SkmSrcs srcs, SkmArgs a,
             }
           }
           {
-            const uint32_t c = wave_sum(claims);
+            uint32_t c;
+            if constexpr (DEAL == 2) wave_exclusive_sum_4bit(claims, &c);  // (a lane deals with eight windows a trip at the most)
+            else c = wave_sum(claims);
             if (lane == 0 && c) atomicAdd(&s_nclaimed2[rp], c);
             seen = __hip_atomic_load(&s_nclaimed2[rp], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
             seen = (uint32_t)__builtin_amdgcn_readfirstlane((int)seen);
@@ -1850,11 +1898,12 @@ void s1_skm_groups_launch(mhx_ctx *c, bool agg, unsigned grid, const SkmFront &f
   }
   const uint64_t n_bits = c->global_bases ? c->global_bases : c->seqs.n_bases;
   const bool tags = (n_bits >> 32) != 0 || c->opt("s1_skm_tags", 0) != 0;
-  const bool deal = c->opt("s1_skm_deal", 1) != 0;
+  const long long deal = std::min<long long>(std::max<long long>(c->opt("s1_skm_deal", 2), 0), 2);  // (a value outside 0..2: the nearest form)
 #define MHX_SKM(AGGV, TAGV)                                                                                                  \
   do {                                                                                                                       \
-    if (deal) hipLaunchKernelGGL((k_s1_skm<AGGV, TAGV, true>), dim3(grid), dim3(kSkmThreads), 0, st, srcs, a, ticket);        \
-    else hipLaunchKernelGGL((k_s1_skm<AGGV, TAGV, false>), dim3(grid), dim3(kSkmThreads), 0, st, srcs, a, ticket);            \
+    if (deal == 2) hipLaunchKernelGGL((k_s1_skm<AGGV, TAGV, 2>), dim3(grid), dim3(kSkmThreads), 0, st, srcs, a, ticket);      \
+    else if (deal == 1) hipLaunchKernelGGL((k_s1_skm<AGGV, TAGV, 1>), dim3(grid), dim3(kSkmThreads), 0, st, srcs, a, ticket); \
+    else hipLaunchKernelGGL((k_s1_skm<AGGV, TAGV, 0>), dim3(grid), dim3(kSkmThreads), 0, st, srcs, a, ticket);                \
   } while (0)
   MHX_LAUNCH(c, "s1_skm_groups", (double)f.n_records * 16, {
     if (agg && tags) MHX_SKM(true, true);

@@ -22,7 +22,7 @@ import oracle_binding as ob  # noqa: E402
 from megahit_amd import lib, synth  # noqa: E402
 
 RESET = dict(s1_skm=1, s1_stream_fill=7168, s1_stream_probes=1024, s1_skm_max_bin=65536, s1_skm_bin_bits=0, s1_skm_tags=0, s1_skm_cap_pct=36, s1_var_min_fill=50,
-             s1_skm_passes=0, s1_skm_deal=1, s1_skm_hp=1, count_skm=1, count_skm_group=2, s1_skm_split=1, s1_skm_split_stage=2560,
+             s1_skm_passes=0, s1_skm_deal=2, s1_skm_hp=1, count_skm=1, count_skm_group=2, s1_skm_split=1, s1_skm_split_stage=2560,
              s1_skm_make_grid=0, s1_skm_rep=0)
 
 
@@ -80,7 +80,7 @@ def knobs(rng):
     if rng.random() < 0.3:
         o["s1_skm_tags"] = 1
     if rng.random() < 0.3:
-        o["s1_skm_deal"] = 0
+        o["s1_skm_deal"] = int(rng.integers(0, 2))  # (2 is the default)
     if rng.random() < 0.2:
         o["s1_skm_hp"] = 0
     if rng.random() < 0.2:

@@ -50,7 +50,7 @@ def main():
         if rng.random() < 0.3:
             opts["s1_skm_tags"] = 1
         if rng.random() < 0.3:
-            opts["s1_skm_deal"] = 0
+            opts["s1_skm_deal"] = int(rng.integers(0, 2))  # (2 is the default)
         if rng.random() < 0.15:
             opts["s1_skm_max_bin"] = int(rng.choice([8, 500]))
         if rng.random() < 0.3:
