@@ -175,6 +175,17 @@ int mhx_set_option(mhx_ctx *, const char *name, long long value);
  *                          (stage 1 and count; looked at only where s1_skm_hp is on, on one GPU; the plan line says how many windows);
  *                          s1_skm_rep_slots (64 = all): slots of the LDS hash in which a workgroup of the make kernel tallies those
  *                          windows (48 in stage 1, 16 in count) — tests: few or 0, and the tallies go to the global table directly;
+ *                          s1_skm_giant (0) 1: a bin of more than s1_skm_max_bin records — the non-periodic windows across the edges of
+ *                          microsatellite stretches inside reads share the repeat's minimizer — no longer costs the job the path: the bin's
+ *                          rounds are dealt to several workgroups, 2^d slices of it, each the rounds from (d, j) on (csrc/skm_giant.h);
+ *                          stage 1 without mercy and count, one GPU (ignored on several); the plan line ends in "[G giant bins in S slices,
+ *                          largest R records]".  s1_skm_giant_keys (4096): windows a slice should hold — the slices of a bin are its estimated
+ *                          windows over this, up to a power of two, at most 1024; s1_skm_giant_work_pct (25): every slice reads its whole bin,
+ *                          and all slices together may read this many per cent of the job's records once more — the costliest bin's slices
+ *                          are halved until they do; not even with one slice each: the prefix plan; s1_skm_giant_max (2097152): a bin of
+ *                          more records hands the job to the prefix plan, as do more than 1024 such bins (the plan line says which);
+ *                          s1_skm_giant_slices (0 = as above): the slices of every giant bin, a power of two up to 1024, not halved to fit
+ *                          the work budget (tests);
  *                          s1_skm_split (1): the make kernel puts every record into the range of its bin's low digit (256 ranges of the
  *                          array), so the sort starts at the second digit: one 16-byte pass fewer (bins of two digits or more; a range
  *                          that overflows — skewed bins — makes the records again, unsplit); 0: one cursor and all passes;

@@ -1011,12 +1011,13 @@ static bool count_run_stream(mhx_ctx *c, uint32_t k, uint32_t m, mhx_count_resul
   // super-k-mer records first where they serve (one GPU, no memory plan, k <= 21: s1_skm.hip); a job they give up on — low-complexity reads —
   // goes on below from clean arrays
   bool skm_done = false;
+  std::string skm_why;     // s1_skm_giant: why its plan gave the job up (the plan line of the prefix plan says so)
   uint64_t skm_edges = 0;  // the passes' edges, packed behind each other in ws "cs_edges_a"
   if (!pre && !acc && count_skm_applies(c, k, m)) {
     bool touched = false;
     const int n_passes = s1_skm_passes(c, k);
     uint64_t n_dist = 0, skm_records = 0;
-    uint32_t skm_max_bin = 0;
+    uint32_t skm_max_bin = 0, giant_bins = 0, giant_slices = 0, giant_largest = 0;
     skm_done = true;
     for (int p = 0; p < n_passes && skm_done; ++p) {
       skm_done = count_skm_groups(c, k, m, first, last, hist, &o, &touched, p, n_passes);
@@ -1037,7 +1038,11 @@ static bool count_run_stream(mhx_ctx *c, uint32_t k, uint32_t m, mhx_count_resul
       n_dist += o.n_distinct;
       skm_records += o.skm_records;
       skm_max_bin = std::max(skm_max_bin, o.skm_max_bin);
+      giant_bins += o.skm_giant_bins;
+      giant_slices += o.skm_giant_slices;
+      giant_largest = std::max(giant_largest, o.skm_giant_largest);
     }
+    skm_why = o.skm_why;
     if (skm_done && o.skm_hp) {  // the one or two keys of the homopolymer windows, behind the passes' edges
       unsigned long long *dense = grow_preserving(c, c->work["cs_edges_a"], (skm_edges + 3) * 8, skm_edges * 8).as<unsigned long long>();
       uint64_t ne = 0, nk = 0;
@@ -1066,6 +1071,8 @@ static bool count_run_stream(mhx_ctx *c, uint32_t k, uint32_t m, mhx_count_resul
       o.plan = txt;
       if (n_passes > 1) o.plan += " [" + std::to_string(n_passes) + " passes over ranges of bins]";
       if (o.skm_rep) o.plan += " [" + std::to_string(n_rep) + " windows of period <= 4 beside the records]";
+      if (giant_bins)
+        o.plan += " [" + std::to_string(giant_bins) + " giant bins in " + std::to_string(giant_slices) + " slices, largest " + std::to_string(giant_largest) + " records]";
     }
     if (!skm_done) {
       // count_skm = 3: a caller that left the memory plan to this path (mhx_count_self_planned) hears that it did not serve
@@ -1129,6 +1136,7 @@ static bool count_run_stream(mhx_ctx *c, uint32_t k, uint32_t m, mhx_count_resul
   c->count_acc_k = k;
   c->count_acc_m = m;
   c->last_s1_plan = "count: " + o.plan;
+  if (!skm_done && !skm_why.empty()) c->last_s1_plan += " [super-k-mer records given up: " + skm_why + "]";
   MHX_HIP(hipStreamSynchronize(st));
   if (out) {
     out->n_items = o.n_items;

@@ -248,6 +248,12 @@ struct SkmFront {
   int bin_bits;
   unsigned long long *hp;   // the homopolymer windows counted beside the records (stage 1, one GPU: [0..1] counts, [2..3] a position each; count: [8..]), else nullptr
   bool rep;                 // s1_skm_rep: the windows of period <= 4 were counted beside the records too, in the table behind hp (s1_skm.hip kSkmRepAt)
+  // s1_skm_giant (one GPU; skm_giant.h): the bins of more than giant_limit records leave the batches and are worked in slices — giants[i] =
+  // (bin, sub0 << 16 | rj0), n_giant_items of them on the device, the largest bins first; 0 items: no such bin, or the option is off
+  const uint2 *giants;
+  uint32_t n_giant_items, giant_limit;
+  uint32_t giant_bins, giant_largest;  // for the plan line: giant bins of this pass, the records of the largest
+  const char *why;                     // the front returned false for a reason of the option's (cap, work budget, list), else nullptr
 };
 bool s1_skm_applies(const mhx_ctx *c, uint32_t k, uint32_t m, int want_mercy);
 bool s1_skm_dist_applies(const mhx_ctx *c, uint32_t k, uint32_t m);
@@ -363,6 +369,8 @@ struct CountStreamOut {
   uint64_t skm_records = 0, skm_windows = 0;
   uint32_t skm_max_bin = 0;
   int skm_bin_bits = 0;
+  uint32_t skm_giant_bins = 0, skm_giant_slices = 0, skm_giant_largest = 0;  // s1_skm_giant: the pass's giant bins, their slices, the largest
+  std::string skm_why;  // ... and why the option's plan gave the job up (empty: for no reason of the option's)
 };
 // edges_only: only the solid edges are wanted (no first_0_out / last_0_in: positions do not matter)
 bool count_stream_applies(const mhx_ctx *c, uint32_t k, uint32_t m, bool edges_only = false);

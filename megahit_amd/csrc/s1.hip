@@ -840,7 +840,8 @@ struct S1Stage {
     if (!sparse) ensure_byte_map();
     const uint64_t cus = c->n_cus > 0 ? (uint64_t)c->n_cus : 256;
     // (a workgroup takes tickets of kSkmBatch bins: no more workgroups than tickets, so that a small job's regions are not cut thinner than its work)
-    const unsigned grid = (unsigned)std::min<uint64_t>(cus, std::max<uint64_t>(1, div_ceil((uint64_t)(f.bin_hi - f.bin_lo), (uint64_t)kSkmBatch)));
+    // (s1_skm_giant: the slices of the giant bins are tickets too, in front of the batches)
+    const unsigned grid = (unsigned)std::min<uint64_t>(cus, std::max<uint64_t>(1, f.n_giant_items + div_ceil((uint64_t)(f.bin_hi - f.bin_lo), (uint64_t)kSkmBatch)));
     // per-workgroup output regions in the spare sort buffer: aggregated items in its first half, (several GPUs) marks in its second
     const uint64_t region8 = f.spare_bytes / 8 / 2 / std::max(1u, grid);
     uint2 *raw = nullptr;
@@ -1290,10 +1291,11 @@ static bool s1_skm_try(mhx_ctx *c, uint32_t k, uint32_t m, mhx_s1_result *out, s
   S1Stage stage(c, k, m, 0, nullptr, nullptr, 0, nullptr);
   stage.sorted = nullptr;
   uint64_t n_records = 0;
-  uint32_t max_bin = 0;
+  uint32_t max_bin = 0, giant_bins = 0, giant_slices = 0, giant_largest = 0;
   for (int p = 0; p < n_passes; ++p) {
     if (!s1_skm_front(c, k, &f, p, n_passes)) {
       *why = f.n_records ? "a bin of " + std::to_string(f.max_bin) + " records" : "more records than the array holds";
+      if (f.why) *why += std::string(", ") + f.why;  // (s1_skm_giant: the cap, the work budget or the list)
       return false;
     }
     stage.set_spare(f.spare);
@@ -1304,6 +1306,9 @@ static bool s1_skm_try(mhx_ctx *c, uint32_t k, uint32_t m, mhx_s1_result *out, s
     }
     n_records += f.n_records;
     max_bin = std::max(max_bin, f.max_bin);
+    giant_bins += f.giant_bins;
+    giant_slices += f.n_giant_items;
+    giant_largest = std::max(giant_largest, f.giant_largest);
   }
   stage.publish_skm_hp(f);
   const uint64_t n_rep = stage.publish_skm_rep(f);
@@ -1316,6 +1321,8 @@ static bool s1_skm_try(mhx_ctx *c, uint32_t k, uint32_t m, mhx_s1_result *out, s
   c->last_s1_plan = txt;
   if (n_passes > 1) c->last_s1_plan += " [" + std::to_string(n_passes) + " passes over ranges of bins]";
   if (f.rep) c->last_s1_plan += " [" + std::to_string(n_rep) + " windows of period <= 4 beside the records]";
+  if (giant_bins)
+    c->last_s1_plan += " [" + std::to_string(giant_bins) + " giant bins in " + std::to_string(giant_slices) + " slices, largest " + std::to_string(giant_largest) + " records]";
   stage.publish(out);
   return true;
 }

@@ -28,11 +28,14 @@
 // Shapes: no mercy, no lv1 bucket filter (the path cuts large jobs into passes over ranges of its OWN bins), reads of one length or of
 // several, min count <= 2, 19 <= k <= 22 (count: 21), positions below 2^36; everything else — and any input with a bin that outgrows what
 // one workgroup should stream (repeats other than homopolymers; with s1_skm_rep: other than reads of period <= 4 throughout) — takes the
-// prefix plan (s1_stream.hip).  DESIGN.md 4o.
+// prefix plan (s1_stream.hip).  With s1_skm_giant (one GPU) such a bin, up to s1_skm_giant_max records, is listed by k_skm_giants and worked
+// in SLICES: the rounds of the bin from a depth on are work items of their own, tickets in front of the batches of bins (skm_giant.h; the
+// GIANT forms of k_s1_skm / k_count_skm).  DESIGN.md 4o.
 #include <cstring>
 
 #include "s1_shared.h"
 #include "skm_deal.h"
+#include "skm_giant.h"
 
 namespace mhx {
 
@@ -703,6 +706,19 @@ __global__ __launch_bounds__(256) void k_skm_bounds(const uint4 *__restrict__ re
   }
 }
 
+// s1_skm_giant: the bins [bin_lo, bin_hi) of more than `limit` records -> out[1 + i] = (bin, records), in any order, through the cursor in
+// the first word of out[0] (zero at launch; it counts every such bin, the list holds the first list_cap); a thread per bin
+__global__ __launch_bounds__(256) void k_skm_giants(const uint64_t *__restrict__ bounds, uint32_t bin_lo, uint32_t bin_hi, uint64_t limit, uint2 *__restrict__ out,
+                                                    uint32_t list_cap) {
+  const uint64_t b = (uint64_t)bin_lo + (uint64_t)blockIdx.x * 256 + threadIdx.x;
+  if (b >= bin_hi) return;
+  const uint64_t d = bounds[b + 1] - bounds[b];
+  if (d > limit) {
+    const uint32_t at = atomicAdd(reinterpret_cast<uint32_t *>(out), 1u);
+    if (at < list_cap) out[1 + at] = make_uint2((uint32_t)b, d > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)d);
+  }
+}
+
 struct SkmArgs {
   int k;
   uint32_t m;
@@ -720,6 +736,10 @@ struct SkmArgs {
   unsigned long long *marks_raw;
   uint32_t marks_cap;
   uint32_t *marks_counts;
+  // GIANT (s1_skm_giant, one source): tickets 0 .. n_giant - 1 are the work items giants[] = (bin, sub0 << 16 | rj0) — the rounds of a bin
+  // of more than giant_limit records from (sub0, rj0) on (skm_giant.h); the tickets behind them are the batches, which skip those bins
+  const uint2 *giants;
+  uint32_t n_giant, giant_limit;
 };
 // the records of a bin arrive as one sub-range per source: one array on a single GPU; on several, one per sending rank (each ordered by bin)
 struct SkmSrcs {
@@ -746,7 +766,8 @@ __device__ __forceinline__ uint32_t wave_exclusive_sum_4bit(uint32_t v, uint32_t
 
 // TAGS: read sets of 2^32 bases and more — the position bits above 32 ride in the record's first word and next to the key in the table
 // DEAL: 0 every lane expands its own record, 1 the windows are dealt to the lanes with six shuffles, 2 with three (skm_deal.h)
-template <bool AGG, bool TAGS, int DEAL>
+// GIANT: the first a.n_giant tickets are slices of giant bins (one source); the other forms are the code they were without it
+template <bool AGG, bool TAGS, int DEAL, bool GIANT = false>
 __global__ __launch_bounds__(kSkmThreads) void k_s1_skm(SkmSrcs srcs, SkmArgs a, uint32_t *__restrict__ ticket) {
   constexpr int NT = kSkmThreads, NSLOT = 1 << kSkmLogSlots, W = NSLOT / NT;
   constexpr unsigned long long kEmpty = ~0ull;  // never a key: head / tail bits 63 do not occur
@@ -830,11 +851,24 @@ __global__ __launch_bounds__(kSkmThreads) void k_s1_skm(SkmSrcs srcs, SkmArgs a,
   for (;;) {
     if (tid == 0) s_tk = atomicAdd(ticket, 1u);
     __syncthreads();
-    const uint64_t bin0 = (uint64_t)a.bin_lo + (uint64_t)s_tk * kSkmBatch;
-    if (bin0 >= a.bin_hi) break;
-    if (tid < n_src * (kSkmBatch + 1)) {
-      const int q = tid / (kSkmBatch + 1), x = tid - q * (kSkmBatch + 1);
-      s_lo[q][x] = srcs.bounds[q][min(bin0 + x, (uint64_t)a.bin_hi)];
+    // GIANT: the first tickets are slices of giant bins — the bin alone in the batch, its rounds from (sub0, rj0) on
+    uint32_t sub0 = 0, rj0 = 0;
+    bool slice = false;
+    if constexpr (GIANT) slice = s_tk < a.n_giant;  // (uniform)
+    if (slice) {
+      // (the item is the same in every lane: kept in scalar registers through the rounds)
+      const uint2 item = a.giants[(uint32_t)__builtin_amdgcn_readfirstlane((int)s_tk)];
+      const uint32_t depth_at = (uint32_t)__builtin_amdgcn_readfirstlane((int)item.y);
+      sub0 = depth_at >> 16;
+      rj0 = depth_at & 0xFFFFu;
+      if (tid <= kSkmBatch) s_lo[0][tid] = srcs.bounds[0][item.x + (tid ? 1u : 0u)];
+    } else {
+      const uint64_t bin0 = (uint64_t)a.bin_lo + (uint64_t)(s_tk - (GIANT ? a.n_giant : 0u)) * kSkmBatch;
+      if (bin0 >= a.bin_hi) break;
+      if (tid < n_src * (kSkmBatch + 1)) {
+        const int q = tid / (kSkmBatch + 1), x = tid - q * (kSkmBatch + 1);
+        s_lo[q][x] = srcs.bounds[q][min(bin0 + x, (uint64_t)a.bin_hi)];
+      }
     }
     __syncthreads();
     for (int bb = 0; bb < kSkmBatch; ++bb) {
@@ -842,9 +876,11 @@ __global__ __launch_bounds__(kSkmThreads) void k_s1_skm(SkmSrcs srcs, SkmArgs a,
       for (int q = 0; q < n_src; ++q) any = any || s_lo[q][bb] != s_lo[q][bb + 1];
       if (!any) continue;
       const uint64_t lo0 = s_lo[0][bb], hi0 = s_lo[0][bb + 1];
+      if constexpr (GIANT)
+        if (!slice && hi0 - lo0 > (uint64_t)a.giant_limit) continue;  // (uniform) a giant bin inside a batch: its slices are tickets of their own
       // the bin in rounds: round (sub, rj) takes the keys whose top `sub` bits of a second hash are rj (a round that overflows the
-      // table is redone in two halves)
-      uint32_t sub = 0, rj = 0;
+      // table is redone in two halves; skm_giant.h) — a slice of a giant bin: the rounds from (sub0, rj0) on
+      uint32_t sub = sub0, rj = rj0;
       for (;;) {
         uint32_t seen = 0;
         // A: insert, source by source (the round's first trip was requested before the walk of the round before it)
@@ -950,7 +986,7 @@ __global__ __launch_bounds__(kSkmThreads) void k_s1_skm(SkmSrcs srcs, SkmArgs a,
                 const unsigned head = (unsigned)(win >> 62), tail = ((uint32_t)win >> (62 - 2 * k)) & 3u;  // (k <= 22: the tail sits in the low word)
                 key[u] = skm_s1_key(f, rc, head, tail);
                 const uint32_t klo = (uint32_t)key[u], khi = (uint32_t)(key[u] >> 32);
-                if (sub) mn = mn && (skm_mix2((klo * 0xC2B2AE35u) ^ (khi * 0x27D4EB2Fu)) >> (32 - sub)) == rj;  // (uniform branch)
+                if (sub) mn = mn && skm_in_round(skm_mix2((klo * 0xC2B2AE35u) ^ (khi * 0x27D4EB2Fu)), sub, rj);  // (uniform branch)
                 mine |= mn ? 1u << u : 0u;
                 h1[u] = ((klo * 0x9E3779B1u) ^ (khi * 0x85EBCA6Bu)) >> (32 - kSkmLogSlots);
                 if constexpr (TAGS) {  // (p0, the record's own position word: a run across a multiple of 2^32 carries into the tag)
@@ -1024,7 +1060,7 @@ __global__ __launch_bounds__(kSkmThreads) void k_s1_skm(SkmSrcs srcs, SkmArgs a,
                 key[u] = skm_s1_key(f, rc, head, tail);
                 const uint32_t klo = (uint32_t)key[u], khi = (uint32_t)(key[u] >> 32);
                 bool mn = (uint32_t)j < len;
-                if (sub) mn = mn && (skm_mix2((klo * 0xC2B2AE35u) ^ (khi * 0x27D4EB2Fu)) >> (32 - sub)) == rj;  // (uniform branch)
+                if (sub) mn = mn && skm_in_round(skm_mix2((klo * 0xC2B2AE35u) ^ (khi * 0x27D4EB2Fu)), sub, rj);  // (uniform branch)
                 mine |= mn ? 1u << u : 0u;
                 h1[u] = ((klo * 0x9E3779B1u) ^ (khi * 0x85EBCA6Bu)) >> (32 - kSkmLogSlots);
               }
@@ -1096,31 +1132,17 @@ __global__ __launch_bounds__(kSkmThreads) void k_s1_skm(SkmSrcs srcs, SkmArgs a,
           s_nclaimed2[rp ^ 1] = 0;
           s_list_n2[rp ^ 1] = 0;
         }
-        uint32_t nsub = sub, nrj = rj;
-        bool done = false, give_up = false;
-        if (bad) {
-          if (sub >= 31) {
-            give_up = true;
-            done = true;
-          } else {
-            nsub = sub + 1;
-            nrj = rj << 1;
-          }
-        } else {
-          nrj = rj + 1;
-          while (nsub > 0 && (nrj & 1u) == 0) {
-            --nsub;
-            nrj >>= 1;
-          }
-          done = nsub == 0 && nrj == 1u;
-        }
+        uint32_t nsub, nrj;
+        bool done, give_up;
+        skm_next_round(sub, rj, bad, sub0, rj0, &nsub, &nrj, &done, &give_up);
         if (give_up && tid == 0) atomicOr(a.err, 1u);
-        {  // the first trip of what comes next — this bin again, or the next bin of the batch that holds records — is requested here (first source)
+        {  // the first trip of what comes next — this bin again, or the next bin of the batch that holds records — is requested here (first source;
+           // used only where the next insert starts at pre_at: a ticket of the other kind, or a bin that is skipped, asks again)
           uint64_t nlo = lo0, nhi = hi0;
           if (done) {
             nlo = nhi = 0;
             for (int nb = bb + 1; nb < kSkmBatch; ++nb)
-              if (s_lo[0][nb] != s_lo[0][nb + 1]) {
+              if (s_lo[0][nb] != s_lo[0][nb + 1] && !(GIANT && !slice && s_lo[0][nb + 1] - s_lo[0][nb] > (uint64_t)a.giant_limit)) {
                 nlo = s_lo[0][nb];
                 nhi = s_lo[0][nb + 1];
                 break;
@@ -1288,9 +1310,12 @@ struct CountSkmArgs {
   unsigned long long *ev_raw;
   uint32_t ev_cap;
   uint32_t *ev_counts;
+  // GIANT: as in SkmArgs — the work items of the giant bins (the first n_giant tickets), the records above which a batch skips a bin
+  const uint2 *giants;
+  uint32_t n_giant, giant_limit;
 };
 
-template <bool TAGS, int G, bool EVENTS = false>
+template <bool TAGS, int G, bool EVENTS = false, bool GIANT = false>
 __global__ __launch_bounds__(kSkmThreads) void k_count_skm(SkmSrcs srcs, CountSkmArgs a, uint32_t *__restrict__ ticket) {
   constexpr int NT = kSkmThreads, NSLOT = 1 << kSkmLogSlots, W = NSLOT / NT;
   constexpr unsigned long long kEmpty = ~0ull;  // never a key: the bits below the (k+1)-mer are zero
@@ -1392,24 +1417,39 @@ __global__ __launch_bounds__(kSkmThreads) void k_count_skm(SkmSrcs srcs, CountSk
   auto in_round = [&](unsigned long long key, uint32_t sub, uint32_t rj) -> bool {
     if (!sub) return true;
     const uint32_t klo = (uint32_t)key, khi = (uint32_t)(key >> 32);
-    return (skm_mix2((klo * 0xC2B2AE35u) ^ (khi * 0x27D4EB2Fu)) >> (32 - sub)) == rj;
+    return skm_in_round(skm_mix2((klo * 0xC2B2AE35u) ^ (khi * 0x27D4EB2Fu)), sub, rj);
   };
 
   for (;;) {
     if (tid == 0) s_tk = atomicAdd(ticket, 1u);
     __syncthreads();
-    const uint64_t bin0 = (uint64_t)a.bin_lo + (uint64_t)s_tk * kSkmBatch;
-    if (bin0 >= a.bin_hi) break;
-    if (tid < n_src * (kSkmBatch + 1)) {
-      const int q = tid / (kSkmBatch + 1), x = tid - q * (kSkmBatch + 1);
-      s_lo[q][x] = srcs.bounds[q][min(bin0 + x, (uint64_t)a.bin_hi)];
+    // GIANT: the first tickets are slices of giant bins — the bin alone in the batch, its rounds from (sub0, rj0) on
+    uint32_t sub0 = 0, rj0 = 0;
+    bool slice = false;
+    if constexpr (GIANT) slice = s_tk < a.n_giant;  // (uniform)
+    if (slice) {
+      // (the item is the same in every lane: kept in scalar registers through the rounds)
+      const uint2 item = a.giants[(uint32_t)__builtin_amdgcn_readfirstlane((int)s_tk)];
+      const uint32_t depth_at = (uint32_t)__builtin_amdgcn_readfirstlane((int)item.y);
+      sub0 = depth_at >> 16;
+      rj0 = depth_at & 0xFFFFu;
+      if (tid <= kSkmBatch) s_lo[0][tid] = srcs.bounds[0][item.x + (tid ? 1u : 0u)];
+    } else {
+      const uint64_t bin0 = (uint64_t)a.bin_lo + (uint64_t)(s_tk - (GIANT ? a.n_giant : 0u)) * kSkmBatch;
+      if (bin0 >= a.bin_hi) break;
+      if (tid < n_src * (kSkmBatch + 1)) {
+        const int q = tid / (kSkmBatch + 1), x = tid - q * (kSkmBatch + 1);
+        s_lo[q][x] = srcs.bounds[q][min(bin0 + x, (uint64_t)a.bin_hi)];
+      }
     }
     __syncthreads();
     for (int bb = 0; bb < kSkmBatch; ++bb) {
       bool any = false;
       for (int q = 0; q < n_src; ++q) any = any || s_lo[q][bb] != s_lo[q][bb + 1];
       if (!any) continue;
-      uint32_t sub = 0, rj = 0;
+      if constexpr (GIANT)
+        if (!slice && s_lo[0][bb + 1] - s_lo[0][bb] > (uint64_t)a.giant_limit) continue;  // (uniform) a giant bin inside a batch: its slices are tickets of their own
+      uint32_t sub = sub0, rj = rj0;  // (a slice of a giant bin: the rounds from (sub0, rj0) on; skm_giant.h)
       for (;;) {
         uint32_t seen = 0;
         // A: insert
@@ -1505,24 +1545,9 @@ __global__ __launch_bounds__(kSkmThreads) void k_count_skm(SkmSrcs srcs, CountSk
         }
         __syncthreads();  // the table is complete
         const bool bad = s_bad != 0 || s_nclaimed > a.max_fill;
-        uint32_t nsub = sub, nrj = rj;
-        bool done = false, give_up = false;
-        if (bad) {
-          if (sub >= 31) {
-            give_up = true;
-            done = true;
-          } else {
-            nsub = sub + 1;
-            nrj = rj << 1;
-          }
-        } else {
-          nrj = rj + 1;
-          while (nsub > 0 && (nrj & 1u) == 0) {
-            --nsub;
-            nrj >>= 1;
-          }
-          done = nsub == 0 && nrj == 1u;
-        }
+        uint32_t nsub, nrj;
+        bool done, give_up;
+        skm_next_round(sub, rj, bad, sub0, rj0, &nsub, &nrj, &done, &give_up);
         if (give_up && tid == 0) atomicOr(a.err, 1u);
         // C: one walk over the table — per distinct (k+1)-mer: histogram, has_in / has_out from the seen-twice (m = 2) or seen-once (m = 1)
         // bits, the packed edge of a solid key -> this workgroup's region; a solid key without an in- or out-edge keeps two flag bits
@@ -1815,12 +1840,23 @@ bool s1_skm_front(mhx_ctx *c, uint32_t k, SkmFront *f, int pass, int n_passes, i
   f->n_records = 0;
   f->hp = hp;
   f->rep = rep;
+  f->giants = nullptr;
+  f->n_giant_items = f->giant_limit = f->giant_bins = f->giant_largest = 0;
+  f->why = nullptr;
   if ((uint32_t)h[1] != 0 || h[0] > cap) return false;
   const uint64_t n = h[0];
+  // s1_skm_giant: a bin over the limit is worked in slices by several workgroups (skm_giant.h) instead of costing the job the path — one GPU
+  const bool giant = !c->global_bases && c->n_parts <= 1 && c->opt("s1_skm_giant", 0) != 0;
+  SkmGiantKnobs gk;
+  gk.max_records = (uint64_t)std::max<long long>(c->opt("s1_skm_giant_max", 1 << 21), 1);
+  gk.keys = (uint64_t)std::max<long long>(c->opt("s1_skm_giant_keys", 4096), 1);
+  gk.work_pct = (uint64_t)std::max<long long>(c->opt("s1_skm_giant_work_pct", 25), 0);
+  gk.slices = (uint64_t)std::min<long long>(std::max<long long>(c->opt("s1_skm_giant_slices", 0), 0), 1 << kSkmGiantMaxDepth);
   {  // a bin far over the limit shows in the digit histograms already — one value of EVERY digit stands out by its records: no need to
      // order the records to find it (low-complexity reads: 1 % of (AC)n reads put 1.7 M records behind one minimizer)
     const uint64_t n_bins_pass = std::max<uint64_t>(1, ((1ull << bin_bits) + n_passes - 1) / n_passes);
-    const uint64_t limit = std::max<uint64_t>((uint64_t)c->opt("s1_skm_max_bin", 1 << 16), 16 * (n / n_bins_pass + 1));
+    // (s1_skm_giant: a bin over the limit is served — up to s1_skm_giant_max records, which is what must still be found here)
+    const uint64_t limit = giant ? gk.max_records : std::max<uint64_t>((uint64_t)c->opt("s1_skm_max_bin", 1 << 16), 16 * (n / n_bins_pass + 1));
     bool all = n > 0;
     uint64_t smallest_excess = ~0ull;
     for (size_t p = 0; p < passes.size() && all; ++p) {
@@ -1835,6 +1871,7 @@ bool s1_skm_front(mhx_ctx *c, uint32_t k, SkmFront *f, int pass, int n_passes, i
     if (all) {
       f->n_records = n;
       f->max_bin = (uint32_t)std::min<uint64_t>(smallest_excess, 0xFFFFFFFFu);
+      if (giant) f->why = "beyond s1_skm_giant_max";
       return false;
     }
   }
@@ -1859,6 +1896,16 @@ bool s1_skm_front(mhx_ctx *c, uint32_t k, SkmFront *f, int pass, int n_passes, i
   uint64_t *bounds = c->ws("s1_bucket_bounds", ((size_t)n_bins + 1) * 8 + 64).as<uint64_t>();
   MHX_LAUNCH(c, "s1_skm_bounds", (double)n_bins * 8 * 30,
              hipLaunchKernelGGL(k_skm_bounds, dim3((n_bins + 1 + 255) / 256), dim3(256), 0, st, reinterpret_cast<const uint4 *>(sorted), n, n_bins, bounds, max_bin));
+  // a bin of many times the mean is low-complexity sequence (one minimizer for millions of windows): the prefix plan has the giant path
+  const uint64_t limit = std::max<uint64_t>((uint64_t)c->opt("s1_skm_max_bin", 1 << 16), 16 * (n / (bin_hi - bin_lo) + 1));
+  constexpr uint32_t kListCap = (uint32_t)kSkmGiantMaxBins + 1;  // (one more than is served: the cursor says how many there were)
+  uint2 *giant_list = nullptr;
+  if (giant && bin_hi > bin_lo) {  // the bins over the limit, listed behind the bounds (read back only when there is one)
+    giant_list = c->ws("skm_giant_list", (size_t)(1 + kListCap) * 8).as<uint2>();
+    MHX_HIP(hipMemsetAsync(giant_list, 0, 8, st));
+    MHX_LAUNCH(c, "s1_skm_giants", (double)(bin_hi - bin_lo) * 8,
+               hipLaunchKernelGGL(k_skm_giants, dim3((bin_hi - bin_lo + 255) / 256), dim3(256), 0, st, bounds, bin_lo, bin_hi, limit, giant_list, kListCap));
+  }
   uint32_t h_max = 0;
   MHX_HIP(hipMemcpyAsync(&h_max, max_bin, 4, hipMemcpyDeviceToHost, st));
   MHX_HIP(hipStreamSynchronize(st));
@@ -1875,9 +1922,37 @@ bool s1_skm_front(mhx_ctx *c, uint32_t k, SkmFront *f, int pass, int n_passes, i
   f->bin_hi = bin_hi;
   f->bin_bits = bin_bits;
   f->max_bin = h_max;
-  // a bin of many times the mean is low-complexity sequence (one minimizer for millions of windows): the prefix plan has the giant path
-  const uint64_t limit = std::max<uint64_t>((uint64_t)c->opt("s1_skm_max_bin", 1 << 16), 16 * (n / (bin_hi - bin_lo) + 1));
-  return h_max <= limit;
+  if (h_max <= limit) return true;
+  if (!giant_list) return false;
+  // s1_skm_giant: the plan of the giant bins (skm_giant.h) and their work items, the largest bins first, a bin's slices in a row
+  std::vector<uint2> h_list(1 + kListCap);
+  MHX_HIP(hipMemcpyAsync(h_list.data(), giant_list, h_list.size() * 8, hipMemcpyDeviceToHost, st));
+  MHX_HIP(hipStreamSynchronize(st));
+  const uint32_t n_listed = h_list[0].x;
+  std::vector<uint2> bins(h_list.begin() + 1, h_list.begin() + 1 + std::min(n_listed, kListCap));
+  std::sort(bins.begin(), bins.end(), [](const uint2 &x, const uint2 &y) { return x.y != y.y ? x.y > y.y : x.x < y.x; });
+  std::vector<uint64_t> recs(bins.size());
+  for (size_t g = 0; g < bins.size(); ++g) recs[g] = bins[g].y;
+  std::vector<uint8_t> depth(bins.size() + 1, 0);
+  const double win_per_rec = n ? (double)n_win / (double)n_passes / (double)n : 1.0;
+  switch (skm_giant_plan(recs.data(), (int)recs.size(), n, win_per_rec, gk, depth.data())) {
+    case kSkmGiantServed: break;
+    case kSkmGiantCap: f->why = "beyond s1_skm_giant_max"; return false;
+    case kSkmGiantBudget: f->why = "its slices beyond s1_skm_giant_work_pct"; return false;
+    default: f->why = "more than 1024 such bins"; return false;
+  }
+  std::vector<uint2> items;
+  for (size_t g = 0; g < bins.size(); ++g)
+    for (uint32_t rj0 = 0; rj0 < (1u << depth[g]); ++rj0) items.push_back(make_uint2(bins[g].x, ((uint32_t)depth[g] << 16) | rj0));
+  uint2 *d_items = c->ws("skm_giant_items", items.size() * 8 + 64).as<uint2>();
+  MHX_HIP(hipMemcpyAsync(d_items, items.data(), items.size() * 8, hipMemcpyHostToDevice, st));
+  MHX_HIP(hipStreamSynchronize(st));  // (items leaves scope)
+  f->giants = d_items;
+  f->n_giant_items = (uint32_t)items.size();
+  f->giant_limit = (uint32_t)std::min<uint64_t>(limit, 0xFFFFFFFFu);
+  f->giant_bins = (uint32_t)bins.size();
+  f->giant_largest = bins.empty() ? 0u : bins[0].y;
+  return true;
 }
 
 void s1_skm_groups_launch(mhx_ctx *c, bool agg, unsigned grid, const SkmFront &f, uint32_t k, uint32_t m, uint8_t *solid_bytes, unsigned long long *hist,
@@ -1889,7 +1964,8 @@ void s1_skm_groups_launch(mhx_ctx *c, bool agg, unsigned grid, const SkmFront &f
   const uint32_t nslot = 1u << kSkmLogSlots;
   SkmArgs a{(int)k, m, solid_bytes, hist, agg_raw, agg_cap, agg_counts, err,
             (uint32_t)std::min<long long>(std::max<long long>(c->opt("s1_stream_fill", nslot * 7 / 8), 1), nslot), (int)std::min<long long>(c->opt("s1_stream_probes", 1024), 1024),
-            f.bin_lo, f.bin_hi, marks_raw, marks_cap, marks_counts};
+            f.bin_lo, f.bin_hi, marks_raw, marks_cap, marks_counts, f.giants, f.n_giant_items, f.giant_limit};
+  const bool giant = f.n_giant_items != 0 && f.n_src == 1;  // (the front lists giant bins on one GPU only)
   SkmSrcs srcs{};
   srcs.n = f.n_src;
   for (int q = 0; q < f.n_src; ++q) {
@@ -1899,11 +1975,16 @@ void s1_skm_groups_launch(mhx_ctx *c, bool agg, unsigned grid, const SkmFront &f
   const uint64_t n_bits = c->global_bases ? c->global_bases : c->seqs.n_bases;
   const bool tags = (n_bits >> 32) != 0 || c->opt("s1_skm_tags", 0) != 0;
   const long long deal = std::min<long long>(std::max<long long>(c->opt("s1_skm_deal", 2), 0), 2);  // (a value outside 0..2: the nearest form)
-#define MHX_SKM(AGGV, TAGV)                                                                                                  \
-  do {                                                                                                                       \
-    if (deal == 2) hipLaunchKernelGGL((k_s1_skm<AGGV, TAGV, 2>), dim3(grid), dim3(kSkmThreads), 0, st, srcs, a, ticket);      \
-    else if (deal == 1) hipLaunchKernelGGL((k_s1_skm<AGGV, TAGV, 1>), dim3(grid), dim3(kSkmThreads), 0, st, srcs, a, ticket); \
-    else hipLaunchKernelGGL((k_s1_skm<AGGV, TAGV, 0>), dim3(grid), dim3(kSkmThreads), 0, st, srcs, a, ticket);                \
+#define MHX_SKM_G(AGGV, TAGV, GV)                                                                                                \
+  do {                                                                                                                           \
+    if (deal == 2) hipLaunchKernelGGL((k_s1_skm<AGGV, TAGV, 2, GV>), dim3(grid), dim3(kSkmThreads), 0, st, srcs, a, ticket);      \
+    else if (deal == 1) hipLaunchKernelGGL((k_s1_skm<AGGV, TAGV, 1, GV>), dim3(grid), dim3(kSkmThreads), 0, st, srcs, a, ticket); \
+    else hipLaunchKernelGGL((k_s1_skm<AGGV, TAGV, 0, GV>), dim3(grid), dim3(kSkmThreads), 0, st, srcs, a, ticket);                \
+  } while (0)
+#define MHX_SKM(AGGV, TAGV)                  \
+  do {                                       \
+    if (giant) MHX_SKM_G(AGGV, TAGV, true);  \
+    else MHX_SKM_G(AGGV, TAGV, false);       \
   } while (0)
   MHX_LAUNCH(c, "s1_skm_groups", (double)f.n_records * 16, {
     if (agg && tags) MHX_SKM(true, true);
@@ -1912,6 +1993,7 @@ void s1_skm_groups_launch(mhx_ctx *c, bool agg, unsigned grid, const SkmFront &f
     else MHX_SKM(false, false);
   });
 #undef MHX_SKM
+#undef MHX_SKM_G
 }
 
 // ---- `count` on super-k-mer records: one GPU, 19 <= k <= 21 (k + 10 bases and two flags in a record), min count <= 2, one pass ----
@@ -1943,7 +2025,9 @@ static uint32_t count_skm_launch(mhx_ctx *c, uint32_t k, uint32_t m, const SkmFr
   const uint32_t nslot = 1u << kSkmLogSlots;
   CountSkmArgs a{(int)k, m, hist, ctr, edges_raw, region, counts, seg_err,
                  (uint32_t)std::min<long long>(std::max<long long>(c->opt("s1_stream_fill", nslot * 7 / 8), 1), nslot), (int)std::min<long long>(c->opt("s1_stream_probes", 1024), 1024),
-                 f.bin_lo, f.bin_hi, s.start.as<uint64_t>(), s.n_seqs, s.fixed_len, first_0_out, last_0_in_p1, ev_raw, ev_cap, ev_counts};
+                 f.bin_lo, f.bin_hi, s.start.as<uint64_t>(), s.n_seqs, s.fixed_len, first_0_out, last_0_in_p1, ev_raw, ev_cap, ev_counts,
+                 f.giants, f.n_giant_items, f.giant_limit};
+  const bool giant = f.n_giant_items != 0 && f.n_src == 1 && !ev_raw;  // (the front lists giant bins on one GPU only)
   SkmSrcs srcs{};
   srcs.n = f.n_src;
   for (int q = 0; q < f.n_src; ++q) {
@@ -1953,16 +2037,17 @@ static uint32_t count_skm_launch(mhx_ctx *c, uint32_t k, uint32_t m, const SkmFr
   const uint64_t n_bits = c->global_bases ? c->global_bases : s.n_bases;
   const bool tags = (n_bits >> 32) != 0 || c->opt("s1_skm_tags", 0) != 0;
   const bool g2 = c->opt("count_skm_group", 2) == 2;  // (four chunks per round of compare-and-swaps spill registers here: measured 13.6 against 13.1 ms)
-#define MHX_CSKM(EV)                                                                                                                     \
+#define MHX_CSKM(EV, GV)                                                                                                                 \
   do {                                                                                                                                   \
-    if (tags && g2) hipLaunchKernelGGL((k_count_skm<true, 2, EV>), dim3(grid), dim3(kSkmThreads), 0, st, srcs, a, ticket);                \
-    else if (tags) hipLaunchKernelGGL((k_count_skm<true, 4, EV>), dim3(grid), dim3(kSkmThreads), 0, st, srcs, a, ticket);                 \
-    else if (g2) hipLaunchKernelGGL((k_count_skm<false, 2, EV>), dim3(grid), dim3(kSkmThreads), 0, st, srcs, a, ticket);                  \
-    else hipLaunchKernelGGL((k_count_skm<false, 4, EV>), dim3(grid), dim3(kSkmThreads), 0, st, srcs, a, ticket);                          \
+    if (tags && g2) hipLaunchKernelGGL((k_count_skm<true, 2, EV, GV>), dim3(grid), dim3(kSkmThreads), 0, st, srcs, a, ticket);            \
+    else if (tags) hipLaunchKernelGGL((k_count_skm<true, 4, EV, GV>), dim3(grid), dim3(kSkmThreads), 0, st, srcs, a, ticket);             \
+    else if (g2) hipLaunchKernelGGL((k_count_skm<false, 2, EV, GV>), dim3(grid), dim3(kSkmThreads), 0, st, srcs, a, ticket);              \
+    else hipLaunchKernelGGL((k_count_skm<false, 4, EV, GV>), dim3(grid), dim3(kSkmThreads), 0, st, srcs, a, ticket);                      \
   } while (0)
   MHX_LAUNCH(c, "count_skm_groups", (double)f.n_records * 16, {
-    if (ev_raw) MHX_CSKM(true);
-    else MHX_CSKM(false);
+    if (ev_raw) MHX_CSKM(true, false);
+    else if (giant) MHX_CSKM(false, true);
+    else MHX_CSKM(false, false);
   });
 #undef MHX_CSKM
   uint32_t e = 0;
@@ -1980,9 +2065,13 @@ static uint32_t count_skm_launch(mhx_ctx *c, uint32_t k, uint32_t m, const SkmFr
 bool count_skm_groups(mhx_ctx *c, uint32_t k, uint32_t m, uint32_t *first_0_out, uint32_t *last_0_in_p1, unsigned long long *hist, CountStreamOut *o, bool *touched,
                       int pass, int n_passes) {
   SkmFront f{};
-  if (!s1_skm_front(c, k, &f, pass, n_passes, 0, true)) return false;
+  if (!s1_skm_front(c, k, &f, pass, n_passes, 0, true)) {
+    if (f.why) o->skm_why = "a bin of " + std::to_string(f.max_bin) + " records, " + f.why;
+    return false;
+  }
   const uint64_t cus = c->n_cus > 0 ? (uint64_t)c->n_cus : 256;
-  const unsigned grid = (unsigned)std::min<uint64_t>(cus, std::max<uint64_t>(1, div_ceil((uint64_t)(f.bin_hi - f.bin_lo), (uint64_t)kSkmBatch)));
+  // (tickets: the slices of the giant bins, then the batches)
+  const unsigned grid = (unsigned)std::min<uint64_t>(cus, std::max<uint64_t>(1, f.n_giant_items + div_ceil((uint64_t)(f.bin_hi - f.bin_lo), (uint64_t)kSkmBatch)));
   const uint32_t region = (uint32_t)std::min<uint64_t>(f.spare_bytes / 8 / grid, 0xFFFFFFF0u);
   uint32_t *counts = c->ws("cs_edge_counts", (size_t)grid * 4).as<uint32_t>();
   *touched = true;
@@ -2004,6 +2093,9 @@ bool count_skm_groups(mhx_ctx *c, uint32_t k, uint32_t m, uint32_t *first_0_out,
   o->skm_windows = f.n_windows;
   o->skm_max_bin = f.max_bin;
   o->skm_bin_bits = f.bin_bits;
+  o->skm_giant_bins = f.giant_bins;
+  o->skm_giant_slices = f.n_giant_items;
+  o->skm_giant_largest = f.giant_largest;
   return true;
 }
 

@@ -1,6 +1,6 @@
 """Randomised libraries through stage 1 / count on super-k-mer records against the oracle (GPU).
 
-    python tools/fuzz_skm.py [--repeats] [seconds] [seed]
+    python tools/fuzz_skm.py [--repeats] [--giants] [seconds] [seed]
 
 Every round draws a library (fixed or ragged read lengths, planted poly-X / short-period repeats / duplicated reads), k in 19..22,
 min count 1..2 and a set of knobs (bins, passes, table fill, probe limit, tags, dealing, cap), runs read2sdbg stage 1 + stage 2 and
@@ -8,7 +8,9 @@ count through the C ABI and compares every output with oracle/ (is_solid, histog
 counts, first_0_out / last_0_in).  Prints a line per round; exits 1 at the first difference with the round's seed.
 --repeats: every round also plants tandem repeats of period 1..6 — reads that are one repeat throughout, at any phase, and stretches inside
 other reads — and draws s1_skm_rep (the windows of period <= 4 counted beside the records).  Drawn from a generator of their own: without
-the flag a seed gives the round it always gave."""
+the flag a seed gives the round it always gave.
+--giants: every round also draws s1_skm_giant (giant bins in slices), a small s1_skm_max_bin — so that bins of ordinary reads are giant
+bins, many of them — and forced slice counts, from a third generator.  The line of a round counts the plans that used slices."""
 import os
 import sys
 import time
@@ -23,7 +25,7 @@ from megahit_amd import lib, synth  # noqa: E402
 
 RESET = dict(s1_skm=1, s1_stream_fill=7168, s1_stream_probes=1024, s1_skm_max_bin=65536, s1_skm_bin_bits=0, s1_skm_tags=0, s1_skm_cap_pct=36, s1_var_min_fill=50,
              s1_skm_passes=0, s1_skm_deal=2, s1_skm_hp=1, count_skm=1, count_skm_group=2, s1_skm_split=1, s1_skm_split_stage=2560,
-             s1_skm_make_grid=0, s1_skm_rep=0)
+             s1_skm_make_grid=0, s1_skm_rep=0, s1_skm_giant=0, s1_skm_giant_slices=0, s1_skm_giant_work_pct=25, s1_skm_giant_keys=4096, s1_skm_giant_max=1 << 21)
 
 
 def library(rng):
@@ -99,12 +101,12 @@ def knobs(rng):
 
 
 def main():
-    argv = [a for a in sys.argv[1:] if a != "--repeats"]
-    repeats = "--repeats" in sys.argv[1:]
+    argv = [a for a in sys.argv[1:] if a not in ("--repeats", "--giants")]
+    repeats, giants = "--repeats" in sys.argv[1:], "--giants" in sys.argv[1:]
     seconds = float(argv[0]) if len(argv) > 0 else 60.0
     seed0 = int(argv[1]) if len(argv) > 1 else 1
     e = lib.Engine(0)
-    t0, rounds, on_path = time.time(), 0, 0
+    t0, rounds, on_path, sliced = time.time(), 0, 0, 0
     while time.time() - t0 < seconds:
         seed = seed0 + rounds
         rng = np.random.default_rng(seed)
@@ -115,6 +117,18 @@ def main():
             rng_rep = np.random.default_rng([seed, 0x5EB])
             reads = plant_repeats(rng_rep, reads)
             opts["s1_skm_rep"] = int(rng_rep.random() < 0.8)
+        if giants:  # (a generator of their own again: the rounds of a seed without the flag stay what they were)
+            rng_g = np.random.default_rng([seed, 0x61A])
+            opts["s1_skm_giant"] = int(rng_g.random() < 0.85)
+            opts["s1_skm_max_bin"] = int(rng_g.choice([8, 40, 200, 1000]))  # (small: bins of ordinary reads are giants too)
+            opts["s1_skm_giant_slices"] = int(rng_g.choice([0, 0, 1, 2, 4, 16, 64, 1024]))
+            if opts["s1_skm_giant_slices"] or rng_g.random() < 0.5:  # (a forced count is not halved to fit: room for it)
+                opts["s1_skm_giant_work_pct"] = 100000000
+            if rng_g.random() < 0.3:
+                opts["s1_skm_giant_keys"] = int(rng_g.choice([16, 300, 2048]))
+            if rng_g.random() < 0.1:
+                opts["s1_skm_giant_max"] = int(rng_g.choice([100, 3000]))
+            opts["s1_skm_cap_pct"] = 1000  # (thin output regions of a small job: room for a whole bin's items in one)
         pkg = ob.Package(reads, reverse=True)
         e.load_sequences(pkg.words(), pkg.n_seqs, 0, pkg.start())
         for n_, v in opts.items():
@@ -147,12 +161,14 @@ def main():
             for n_, v in RESET.items():
                 e.set_option(n_, v)
         on_path += plan1.startswith("super-k-mers") + planc.startswith("count: super-k-mers")
-        print("seed %d: %d reads, k %d, m %d, %s | %s | %s%s" % (seed, len(reads), k, m, " ".join("%s=%d" % kv for kv in sorted(opts.items()) if kv[0] not in ("s1_skm", "s1_var_min_fill")),
-                                                                  plan1[:28], planc[:34], "  *** " + bad if bad else ""), flush=True)
+        sliced += ("giant bins in" in plan1) + ("giant bins in" in planc)
+        print("seed %d: %d reads, k %d, m %d, %s | %s%s | %s%s%s" % (seed, len(reads), k, m, " ".join("%s=%d" % kv for kv in sorted(opts.items()) if kv[0] not in ("s1_skm", "s1_var_min_fill")),
+                                                                      plan1[:28], plan1[plan1.find(" giant bins in") - 6:] if "giant bins in" in plan1 else "", planc[:34],
+                                                                      planc[planc.find(" giant bins in") - 6:] if "giant bins in" in planc else "", "  *** " + bad if bad else ""), flush=True)
         if bad:
             sys.exit(1)
         rounds += 1
-    print("%d rounds, %d of %d stages on super-k-mer records, all equal to the oracle" % (rounds, on_path, 2 * rounds))
+    print("%d rounds, %d of %d stages on super-k-mer records%s, all equal to the oracle" % (rounds, on_path, 2 * rounds, ", %d of them with giant bins in slices" % sliced if giants else ""))
 
 
 if __name__ == "__main__":

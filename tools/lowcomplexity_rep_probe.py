@@ -6,8 +6,13 @@ each, per-step times (their spread is the yardstick of the comparison with anoth
 of the outputs.  read2sdbg (stage 1 + stage 2) and count.
 
     python tools/lowcomplexity_rep_probe.py [--off-only] [--label TEXT] [reads] [planted_fractions] > profiles/r13_lowcomplexity_rep.json
+    python tools/lowcomplexity_rep_probe.py --giant --embedded-only [--set NAME=VALUE,...] [--label TEXT] [reads] > one entry of profiles/r16_lowcomplexity_giant.json
 
---off-only: only the rows with the option off (what a build without the option can run: the parent's half of a comparison)."""
+--off-only: only the rows with the option off (what a build without the option can run: the parent's half of a comparison).
+--giant: the rows with s1_skm_rep = 1 also set s1_skm_giant = 1 (giant bins in slices; a build that does not know the option ignores it:
+the parent's half).  --set: further options for those rows (the grid over s1_skm_giant_keys / _work_pct / _max).
+--embedded-only: the clean library and the embedded-stretch rows alone — row 7 (1 % of the reads), 9 (0.1 %) and 10 (5 %) — with s1_skm_rep = 1;
+--whole-ac: and row 11, 1 % of the reads replaced by (AC)n with s1_skm_rep = 0 and the other options as set (a bin of 1.7 M records)."""
 import hashlib
 import json
 import os
@@ -37,8 +42,11 @@ def unpack(words):
 def main():
     argv = sys.argv[1:]
     off_only = "--off-only" in argv
+    giant, embedded_only, whole_ac = "--giant" in argv, "--embedded-only" in argv, "--whole-ac" in argv
+    extra = dict((kv.split("=")[0], int(kv.split("=")[1])) for kv in argv[argv.index("--set") + 1].split(",")) if "--set" in argv else {}
+    on = dict(extra, s1_skm_giant=1) if giant else dict(extra)  # (what a row with the options on sets beside s1_skm_rep)
     label = argv[argv.index("--label") + 1] if "--label" in argv else "this build"
-    pos = [a for i, a in enumerate(argv) if not a.startswith("--") and (i == 0 or argv[i - 1] != "--label")]
+    pos = [a for i, a in enumerate(argv) if not a.startswith("--") and (i == 0 or argv[i - 1] not in ("--label", "--set", "--rows"))]
     n_reads = int(float(pos[0])) if len(pos) > 0 else 10000000
     fracs = [float(x) for x in pos[1].split(",")] if len(pos) > 1 else [0.001, 0.01, 0.05]
     n_reads = n_reads // 16 * 16
@@ -61,12 +69,16 @@ def main():
             return plan
         return eng.last_s1_plan()
 
-    def measure(words, row, what, rep):
+    def measure(words, row, what, rep, with_on=None):
         eng.load_sequences(words, n_reads, bench.READ_LEN, None)
         runs = []
+        with_on = rep if with_on is None else with_on
         for engine_name in ("read2sdbg", "count"):
             if rep:
                 eng.set_option("s1_skm_rep", 1)
+            if with_on:
+                for name, v in on.items():
+                    eng.set_option(name, v)
             try:
                 for _ in range(2):
                     plan = step(engine_name)
@@ -84,13 +96,16 @@ def main():
             finally:
                 if rep:
                     eng.set_option("s1_skm_rep", 0)
+                if with_on:  # (back to the defaults of include/mhx.h)
+                    for name in on:
+                        eng.set_option(name, {"s1_skm_giant_max": 1 << 21, "s1_skm_giant_keys": 4096, "s1_skm_giant_work_pct": 25}.get(name, 0))
             if engine_name == "count":
                 d = digest(((lib.BUF_EDGES, np.uint32), (lib.BUF_BUCKET_COUNT, np.uint64), (lib.BUF_MUL_HIST, np.int64), (lib.BUF_FIRST_0_OUT, np.uint32),
                             (lib.BUF_LAST_0_IN, np.uint32)))
             else:
                 d = digest(((lib.BUF_SDBG_BYTES, np.uint8), (lib.BUF_BUCKET_COUNT, np.uint64), (lib.BUF_BUCKET_TIPS, np.uint64), (lib.BUF_IS_SOLID, np.uint64),
                             (lib.BUF_MUL_HIST, np.int64)))
-            runs.append({"row": row, "library": what, "s1_skm_rep": int(rep), "engine": engine_name, "ms_per_step": round(sum(ms) / STEPS, 3), "ms_steps": ms,
+            runs.append({"row": row, "library": what, "s1_skm_rep": int(rep), **({"options": on} if with_on and on else {}), "engine": engine_name, "ms_per_step": round(sum(ms) / STEPS, 3), "ms_steps": ms,
                          "spread_ms": round(max(ms) - min(ms), 3), "plan": plan, "digest": d,
                          "kernel_ms_per_step": {k: round(v["ms"] / STEPS, 3) for k, v in sorted(st.items(), key=lambda kv: -kv[1]["ms"]) if v["ms"] / STEPS > 0.3}})
             print("%s | %s | rep %d | %s: %.3f ms (%s)" % (label, what, rep, engine_name, runs[-1]["ms_per_step"], plan[:60]), file=sys.stderr, flush=True)
@@ -109,6 +124,20 @@ def main():
         return out
 
     out = {"build": label, "reads": n_reads, "planted_fractions": fracs, "steps": STEPS, "runs": []}
+    if embedded_only:
+        rows = [int(x) for x in argv[argv.index("--rows") + 1].split(",")] if "--rows" in argv else [2, 9, 7, 10, 11]
+        if 2 in rows:
+            out["runs"] += measure(packed, 2, "the bench library", True)
+        for row, frac in ((9, 0.001), (7, 0.01), (10, 0.05)):
+            if row not in rows:
+                continue
+            n_plant = int(n_reads * frac) // 16 * 16
+            out["runs"] += measure(embedded(n_plant, [0, 1], 55, 40), row, "%d reads (%g %%) with a 40-base (AC) stretch at base 55" % (n_plant, frac * 100), True)
+        if whole_ac and 11 in rows:
+            n_plant = int(n_reads * 0.01) // 16 * 16
+            out["runs"] += measure(replaced(n_plant, [0, 1]), 11, "%d reads (1 %%) replaced by (AC)n" % n_plant, False, True)
+        print(json.dumps(out, indent=1))
+        return
     out["runs"] += measure(packed, 1, "the bench library", False)
     if not off_only:
         out["runs"] += measure(packed, 2, "the bench library", True)
