@@ -154,7 +154,7 @@ int mhx_set_option(mhx_ctx *, const char *name, long long value);
  *   fetch_pinned (1)       0: mhx_fetch is one hipMemcpy into the caller's (pageable) memory; 1: results of >= 16 MB leave through two
  *                          pinned staging buffers, the copy off the device overlapped with the copy into the destination
  *   s1_skm (1)             stage 1 on super-k-mer records (csrc/s1_skm.hip): 0 never; 1 where the shape is served (one GPU, no mercy, no bucket
- *                          filter, 19 <= k <= 22, min count <= 2, fewer than 2^36 bases, reads of one length or at least s1_var_min_fill per cent
+ *                          filter, 19 <= k <= 22, min count <= 2 (s1_skm_max_m: up to 4), fewer than 2^36 bases, reads of one length or at least s1_var_min_fill per cent
  *                          of the padded blocks filled) and the job has s1_skm_min_windows (2^22) windows; 2 whatever the size (tests);
  *                          3 as 1, but a job the path gives up on FAILS instead of taking the prefix plan (mhx_s1_self_planned).
  *                          s1_skm_cap_pct (36): records the arrays hold per 100 windows (0.284 per window in random sequence);
@@ -186,6 +186,17 @@ int mhx_set_option(mhx_ctx *, const char *name, long long value);
  *                          more records hands the job to the prefix plan, as do more than 1024 such bins (the plan line says which);
  *                          s1_skm_giant_slices (0 = as above): the slices of every giant bin, a power of two up to 1024, not halved to fit
  *                          the work budget (tests);
+ *                          s1_skm_max_m (2): the largest min count that stage 1 and count serve on super-k-mer records on ONE GPU — 2, or
+ *                          3 / 4 (a value below 2 means 2, one above 4 means 4; several GPUs keep min count <= 2).  Stage 1 at min count
+ *                          3 and 4: a key of count 1 < c < m has c windows to mark and its slot keeps the position of one, so a round
+ *                          that holds such a key expands its records a second time (the LOOK form of k_s1_skm); count: the tallies of
+ *                          the bases either side climb to four (the four-level form of k_count_skm).  There s1_skm_deal, s1_skm_giant
+ *                          and count_skm_group are NOT consulted: the windows are dealt with three shuffles, two chunks a round, and a
+ *                          bin beyond s1_skm_max_bin gives the job up.  A key counted beside the records (a homopolymer; s1_skm_rep: of
+ *                          period <= 4) keeps one position: with 1 < count < m windows it cannot be marked, and stage 1 takes the prefix
+ *                          plan ("[super-k-mer records given up: a key beside the records has N windows, below the min count]"; an
+ *                          error under s1_skm = 3); count's tallies are exact and it stays.  mhx_s1_self_planned and
+ *                          mhx_count_self_planned follow the knob;
  *                          s1_skm_split (1): the make kernel puts every record into the range of its bin's low digit (256 ranges of the
  *                          array), so the sort starts at the second digit: one 16-byte pass fewer (bins of two digits or more; a range
  *                          that overflows — skewed bins — makes the records again, unsplit); 0: one cursor and all passes;
@@ -193,7 +204,7 @@ int mhx_set_option(mhx_ctx *, const char *name, long long value);
  *                          (at most 2560; a trip that makes more writes them from the registers; tests shrink it);
  *                          s1_skm_make_grid (0 = 8 per CU): workgroups of the make kernel (tests: few workgroups, several trips each)
  *   count_skm (1)          `count` on super-k-mer records (k_skm_make<.., COUNT>, k_count_skm: a record carries one more base either side of its run,
- *                          the table the in / out characters): one GPU, 19 <= k <= 21, min count <= 2; jobs of more than s1_skm_pass_gb of
+ *                          the table the in / out characters): one GPU, 19 <= k <= 21, min count <= 2 (s1_skm_max_m: up to 4); jobs of more than s1_skm_pass_gb of
  *                          records in passes over ranges of bins (mhx_count_self_planned); 0: never; 3: fail instead of falling back;
  *                          count_skm_group (2): chunks of 64 windows per round of compare-and-swaps (4 spills registers: measured slower)
  *   dist_skm (1)           several GPUs: 0: stage 1 never exchanges super-k-mer records by bin (comm.hip dist_s1_skm; the pre-sorted exchange

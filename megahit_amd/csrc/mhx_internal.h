@@ -258,7 +258,12 @@ struct SkmFront {
 bool s1_skm_applies(const mhx_ctx *c, uint32_t k, uint32_t m, int want_mercy);
 bool s1_skm_dist_applies(const mhx_ctx *c, uint32_t k, uint32_t m);
 int s1_skm_passes(const mhx_ctx *c, uint32_t k);
-bool s1_skm_front(mhx_ctx *c, uint32_t k, SkmFront *f, int pass, int n_passes, int bin_bits_agreed = 0, bool for_count = false);
+// (bins_whole: no bin is cut into slices, whatever s1_skm_giant says — min count 3 and 4)
+bool s1_skm_front(mhx_ctx *c, uint32_t k, SkmFront *f, int pass, int n_passes, int bin_bits_agreed = 0, bool for_count = false, bool bins_whole = false);
+uint32_t s1_skm_max_m(const mhx_ctx *c);  // s1_skm_max_m: the largest min count served on super-k-mer records on one GPU (2 .. 4)
+// min count 3 and 4: a key counted beside the records (a homopolymer; s1_skm_rep: of period <= 4) keeps ONE position — one of 1 < count < m
+// windows cannot be marked.  -> that count, 0: none (asked behind pass 0's front, before anything is published)
+uint64_t s1_skm_beside_below(mhx_ctx *c, const SkmFront &f, uint32_t k, uint32_t m);
 void s1_skm_bounds_of(mhx_ctx *c, const uint4 *recs, uint64_t n, uint32_t n_bins, uint64_t *bounds);
 void s1_skm_groups_launch(mhx_ctx *c, bool agg, unsigned grid, const SkmFront &f, uint32_t k, uint32_t m, uint8_t *solid_bytes, unsigned long long *hist,
                           uint2 *agg_raw, uint32_t agg_cap, uint32_t *agg_counts, uint32_t *err, unsigned long long *marks_raw, uint32_t marks_cap,
@@ -374,7 +379,7 @@ struct CountStreamOut {
 };
 // edges_only: only the solid edges are wanted (no first_0_out / last_0_in: positions do not matter)
 bool count_stream_applies(const mhx_ctx *c, uint32_t k, uint32_t m, bool edges_only = false);
-// `count` on super-k-mer records (s1_skm.hip): one GPU, 19 <= k <= 21, min count <= 2.  *touched: the caller's arrays may hold partial results
+// `count` on super-k-mer records (s1_skm.hip): one GPU, 19 <= k <= 21, min count <= 2 (s1_skm_max_m: up to 4).  *touched: the caller's arrays may hold partial results
 bool count_skm_applies(const mhx_ctx *c, uint32_t k, uint32_t m);
 bool count_skm_groups(mhx_ctx *c, uint32_t k, uint32_t m, uint32_t *first_0_out, uint32_t *last_0_in_p1, unsigned long long *hist, CountStreamOut *o, bool *touched,
                       int pass, int n_passes);

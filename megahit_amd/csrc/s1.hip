@@ -509,6 +509,7 @@ struct S1Stage {
   uint64_t agg_sig = 0;
   uint32_t seg_grid = 0, seg_cap = 0, seg_mcap = 0;
   uint32_t *seg_err = nullptr;
+  uint64_t skm_rounds = 0, skm_looks = 0;  // super-k-mer records at min count 3 and 4: the rounds of the group-by, and those that took the second look
   int mark_mode = 0, mark_mode_used = 0;
 
   S1Stage(mhx_ctx *c_, uint32_t k_, uint32_t m_, int wm, uint32_t *a, uint32_t *b, uint64_t n, const S1Sources *pre_)
@@ -858,14 +859,19 @@ struct S1Stage {
       mraw = reinterpret_cast<unsigned long long *>(spare) + f.spare_bytes / 8 / 2;
       mcounts = c->ws("s1_mark_counts", (size_t)grid * 4).as<uint32_t>();
     }
-    MHX_HIP(hipMemsetAsync(seg_err, 0, 4, st));
+    MHX_HIP(hipMemsetAsync(seg_err, 0, 12, st));  // (the error bits; min count 3 and 4: rounds, rounds with a second look)
     s1_skm_groups_launch(c, agg, grid, f, k, m, solid_bytes, hist, raw, seg_cap, counts, seg_err, mraw, seg_mcap, mcounts);
-    uint32_t e = 0;
+    uint32_t e3[3] = {0, 0, 0};
     std::vector<uint32_t> h_counts(agg ? seg_grid : 0), h_mcounts(sparse ? seg_grid : 0);
-    MHX_HIP(hipMemcpyAsync(&e, seg_err, 4, hipMemcpyDeviceToHost, st));
+    MHX_HIP(hipMemcpyAsync(e3, seg_err, 12, hipMemcpyDeviceToHost, st));
     if (agg) MHX_HIP(hipMemcpyAsync(h_counts.data(), counts, (size_t)seg_grid * 4, hipMemcpyDeviceToHost, st));
     if (sparse) MHX_HIP(hipMemcpyAsync(h_mcounts.data(), mcounts, (size_t)seg_grid * 4, hipMemcpyDeviceToHost, st));
     MHX_HIP(hipStreamSynchronize(st));
+    const uint32_t e = e3[0];
+    skm_rounds += e3[1];
+    skm_looks += e3[2];
+    // (min count 3 and 4: the second look met a window whose key the table does not hold — a fault of the kernel, never of the input)
+    if (e & 4u) throw Error("read2sdbg_s1: the second look of the group-by on super-k-mer records did not find a window's key");
     if (e) return false;
     if (sparse) {  // pack the workgroups' mark regions behind the earlier passes' marks (run_partial's way)
       for (uint32_t v : h_mcounts) seg_marks += v;
@@ -1293,10 +1299,18 @@ static bool s1_skm_try(mhx_ctx *c, uint32_t k, uint32_t m, mhx_s1_result *out, s
   uint64_t n_records = 0;
   uint32_t max_bin = 0, giant_bins = 0, giant_slices = 0, giant_largest = 0;
   for (int p = 0; p < n_passes; ++p) {
-    if (!s1_skm_front(c, k, &f, p, n_passes)) {
+    if (!s1_skm_front(c, k, &f, p, n_passes, 0, false, m >= 3)) {
       *why = f.n_records ? "a bin of " + std::to_string(f.max_bin) + " records" : "more records than the array holds";
       if (f.why) *why += std::string(", ") + f.why;  // (s1_skm_giant: the cap, the work budget or the list)
       return false;
+    }
+    // min count 3 and 4 (s1_skm_max_m): a key counted beside the records keeps one position, so one of 1 < count < m windows cannot be
+    // marked — decided here, behind the first front (which counted them) and before anything is published
+    if (p == 0 && m >= 3) {
+      if (const uint64_t n_below = s1_skm_beside_below(c, f, k, m)) {
+        *why = "a key beside the records has " + std::to_string(n_below) + " windows, below the min count";
+        return false;
+      }
     }
     stage.set_spare(f.spare);
     if (p == 0) stage.open_outputs();
@@ -1323,6 +1337,7 @@ static bool s1_skm_try(mhx_ctx *c, uint32_t k, uint32_t m, mhx_s1_result *out, s
   if (f.rep) c->last_s1_plan += " [" + std::to_string(n_rep) + " windows of period <= 4 beside the records]";
   if (giant_bins)
     c->last_s1_plan += " [" + std::to_string(giant_bins) + " giant bins in " + std::to_string(giant_slices) + " slices, largest " + std::to_string(giant_largest) + " records]";
+  if (m >= 3) c->last_s1_plan += " [a second look in " + std::to_string(stage.skm_looks) + " of " + std::to_string(stage.skm_rounds) + " rounds]";
   stage.publish(out);
   return true;
 }

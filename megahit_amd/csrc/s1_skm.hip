@@ -26,7 +26,7 @@
 //                 (EVENTS, several GPUs: those windows leave as a list of events for the ranks that hold the reads)
 // 6.0 GB of records at 10 M reads instead of 16: the sort and the read of the group-by move 2.7 x fewer bytes.
 // Shapes: no mercy, no lv1 bucket filter (the path cuts large jobs into passes over ranges of its OWN bins), reads of one length or of
-// several, min count <= 2, 19 <= k <= 22 (count: 21), positions below 2^36; everything else — and any input with a bin that outgrows what
+// several, min count <= 2 (one GPU, s1_skm_max_m: 3 and 4 — the LOOK form of k_s1_skm, the LV 4 form of k_count_skm), 19 <= k <= 22 (count: 21), positions below 2^36; everything else — and any input with a bin that outgrows what
 // one workgroup should stream (repeats other than homopolymers; with s1_skm_rep: other than reads of period <= 4 throughout) — takes the
 // prefix plan (s1_stream.hip).  With s1_skm_giant (one GPU) such a bin, up to s1_skm_giant_max records, is listed by k_skm_giants and worked
 // in SLICES: the rounds of the bin from a depth on are work items of their own, tickets in front of the batches of bins (skm_giant.h; the
@@ -677,6 +677,37 @@ __global__ void k_skm_hp_publish(const unsigned long long *__restrict__ hp, int 
   }
 }
 
+// min count 3 and 4 (s1_skm_max_m): the keys counted beside the records keep the smallest position of their windows and nothing more, so one
+// of 1 < count < m windows cannot get its marks.  *res = the count of such a key (the largest of them), 0: none — the entries of the REP
+// table that are one key summed first, as k_skm_rep_publish sums them.  One workgroup; writes nothing else
+__global__ __launch_bounds__(kSkmRepN) void k_skm_beside_check(const unsigned long long *__restrict__ hp, int rep, int k, uint32_t m, unsigned long long *__restrict__ res) {
+  __shared__ unsigned long long s_key[kSkmRepN], s_cnt[kSkmRepN];
+  __shared__ unsigned long long s_worst;
+  const int e = threadIdx.x, K1 = k + 1;
+  const uint64_t kmask = ~0ull << (64 - 2 * (k - 1));
+  if (e == 0) s_worst = 0;
+  {
+    const uint64_t win = skm_rep_window((uint32_t)e, K1);
+    const uint64_t f = (win << 2) & kmask, rc = (rc64(win, 32) << (2 * (32 - k))) & kmask;
+    const unsigned head = (unsigned)(win >> 62), tail = (unsigned)(win >> (62 - 2 * k)) & 3u;
+    s_key[e] = skm_s1_key(f, rc, head, tail);
+    s_cnt[e] = rep ? hp[kSkmRepAt + e] : 0ull;
+  }
+  __syncthreads();
+  unsigned long long cnt = 0;
+  bool lead = s_cnt[e] != 0;
+  for (int o = 0; o < kSkmRepN; ++o)
+    if (s_cnt[o] && s_key[o] == s_key[e]) {
+      if (o < e) lead = false;
+      cnt += s_cnt[o];
+    }
+  if (!lead) cnt = 0;
+  if (e < 2 && !rep) cnt = hp[e];  // (without REP: the two homopolymer classes, a key each)
+  if (cnt > 1 && cnt < m) atomicMax(&s_worst, cnt);
+  __syncthreads();
+  if (e == 0) *res = s_worst;
+}
+
 // (Natural super-k-mers — runs cut at eight windows from their OWN start, the windows' minimizer hashes exchanged between the threads of a
 //  workgroup through LDS — were built and measured in round 6: 0.23 instead of 0.28 records per window, the two sort passes 5.7 -> 4.8 ms,
 //  but the make kernel 3.1 -> 7.9 ms (three barriers, a walk back and a walk forward through LDS per block, 1024-thread workgroups) and the
@@ -767,8 +798,12 @@ __device__ __forceinline__ uint32_t wave_exclusive_sum_4bit(uint32_t v, uint32_t
 // TAGS: read sets of 2^32 bases and more — the position bits above 32 ride in the record's first word and next to the key in the table
 // DEAL: 0 every lane expands its own record, 1 the windows are dealt to the lanes with six shuffles, 2 with three (skm_deal.h)
 // GIANT: the first a.n_giant tickets are slices of giant bins (one source); the other forms are the code they were without it
-template <bool AGG, bool TAGS, int DEAL, bool GIANT = false>
+// LOOK (s1_skm_max_m, min count 3 and 4; DEAL 2, one GPU): a key of count 1 < c < m has c windows to mark and the slot keeps the position of
+// ONE — a round that holds such a key expands its records a second time, and every window whose key's count is below m marks itself.  The
+// table is cleared behind that look instead of during the walk: three more barriers a round.  The other forms are the code they were
+template <bool AGG, bool TAGS, int DEAL, bool GIANT = false, bool LOOK = false>
 __global__ __launch_bounds__(kSkmThreads) void k_s1_skm(SkmSrcs srcs, SkmArgs a, uint32_t *__restrict__ ticket) {
+  static_assert(!LOOK || (DEAL == 2 && !GIANT), "the second look is built on the three-shuffle deal, bins whole");
   constexpr int NT = kSkmThreads, NSLOT = 1 << kSkmLogSlots, W = NSLOT / NT;
   constexpr unsigned long long kEmpty = ~0ull;  // never a key: head / tail bits 63 do not occur
   constexpr int NLIST = 1024;
@@ -782,6 +817,7 @@ __global__ __launch_bounds__(kSkmThreads) void k_s1_skm(SkmSrcs srcs, SkmArgs a,
   __shared__ unsigned long long heads[DEAL ? kSkmThreads / kWave : 1][8];  // DEAL, per wavefront: bit g set = window g of the trip is the first of its record
   __shared__ uint32_t s_bad2[2], s_nclaimed2[2], s_list_n2[2];  // per round, double-buffered: the next round's are cleared while this round's are read
   __shared__ uint32_t s_agg_cur, s_mark_cur, s_tk;
+  __shared__ uint32_t s_look;  // LOOK (touched by no other form): the round holds a key of count 1 < c < m (set in the walk, cleared with the table)
   __shared__ uint64_t s_lo[kSkmSrcMax][kSkmBatch + 1];
   const int tid = threadIdx.x, lane = tid & (kWave - 1), wv = DEAL ? tid / kWave : 0;
   const uint32_t le_lo = lane >= 31 ? 0xFFFFFFFFu : (2u << lane) - 1u, le_hi = lane < 32 ? 0u : (lane == 63 ? 0xFFFFFFFFu : (2u << (lane - 32)) - 1u);  // lanes <= this one
@@ -800,6 +836,7 @@ __global__ __launch_bounds__(kSkmThreads) void k_s1_skm(SkmSrcs srcs, SkmArgs a,
     s_list_n2[0] = s_list_n2[1] = 0;
     s_agg_cur = 0;
     s_mark_cur = 0;
+    if constexpr (LOOK) s_look = 0;
   }
   const int n_src = srcs.n;
   unsigned long long *const marks_out = a.marks_raw ? a.marks_raw + (size_t)blockIdx.x * a.marks_cap : nullptr;
@@ -1166,13 +1203,16 @@ __global__ __launch_bounds__(kSkmThreads) void k_s1_skm(SkmSrcs srcs, SkmArgs a,
           wp[it] = fpos[sl];
           wt[it] = TAGS ? ftag[sl] : (uint8_t)0;
         }
+        if constexpr (!LOOK) {
 #pragma unroll
         for (int it = 0; it < W; ++it) {
           const int sl = it * NT + tid;
           keys[sl] = kEmpty;
           cnts[sl] = 0;
         }
+        }  // (LOOK: the second look reads the table; it is cleared behind that)
         uint32_t want_bits = 0, mark_bits = 0;
+        [[maybe_unused]] bool look_mine = false;
 #pragma unroll
         for (int it = 0; it < W; ++it) {
           if (wk[it] != kEmpty && !bad) {
@@ -1182,7 +1222,13 @@ __global__ __launch_bounds__(kSkmThreads) void k_s1_skm(SkmSrcs srcs, SkmArgs a,
             else atomicAdd(&a.hist[hb], 1ull);
             if (cnt < m) mark_bits |= 1u << it;  // count 1 < m <= 2: the key's only window is a non-solid occurrence
             else if (AGG) want_bits |= 1u << it;
+            // (LOOK, m = 3 or 4: a key of count 1 is marked here all the same — a round of such keys alone needs no look; one of count 2 or
+            //  3 below m gets ONE of its marks here, the window that claimed the slot, and all of them in the look)
+            if constexpr (LOOK) look_mine = look_mine || (cnt > 1u && cnt < m);
           }
+        }
+        if constexpr (LOOK) {  // (one flag for the workgroup, from a ballot: as s_flagged of k_count_skm)
+          if (__ballot(look_mine) && lane == 0) s_look = 1;
         }
         if (!marks_out) {  // (uniform)
 #pragma unroll
@@ -1236,6 +1282,76 @@ __global__ __launch_bounds__(kSkmThreads) void k_s1_skm(SkmSrcs srcs, SkmArgs a,
             const bool v = i < n_list;
             emit_items(v ? slist_k[i] : 0ull, v ? slist_c[i] : 0u, true, v);
           }
+        }
+        if constexpr (LOOK) {
+          // The second look.  (Barrier between walk and look: the one above — behind it s_look is written and every thread has taken its
+          // slots into registers; the look only READS keys and cnts, which nobody writes until the clear below.)
+          if (tid == 0 && !bad) {  // (for the plan line: a.err[1] the rounds walked, a.err[2] those that took the look)
+            atomicAdd(a.err + 1, 1u);
+            if (s_look) atomicAdd(a.err + 2, 1u);
+          }
+          if (s_look && !bad) {  // (uniform; a round that was not bad holds every one of its windows in the table)
+            for (int q = 0; q < n_src; ++q) {
+              const uint64_t lo = s_lo[q][bb], hi = s_lo[q][bb + 1];
+              const uint4 *__restrict__ recs = srcs.ptr[q];
+              for (uint64_t base = lo; base < hi; base += NT) {
+                const bool in = base + tid < hi;
+                const uint4 r = in ? recs[base + tid] : make_uint4(0u, 0u, 0u, 0u);
+                const uint32_t len = in ? (r.z & 7u) + 1u : 0u;
+                const uint8_t tag = TAGS ? (uint8_t)(r.x >> 28) : (uint8_t)0;
+                uint32_t T;
+                const uint32_t start = wave_exclusive_sum_4bit(len, &T);
+                // (the bitmap of run heads, as the insert makes it: clear, set, read, in the wavefront's own order)
+                if (lane < 8) heads[wv][lane] = 0ull;
+                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+                __builtin_amdgcn_wave_barrier();
+                if (len) atomicOr(&heads[wv][start >> 6], 1ull << (start & 63u));
+                __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+                __builtin_amdgcn_wave_barrier();
+                const unsigned long long hv = __hip_atomic_load(&heads[wv][lane & 7], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                const uint32_t hv_lo = (uint32_t)hv, hv_hi = (uint32_t)(hv >> 32);
+                SkmDealCarry dc;
+                for (uint32_t c = 0; c * kWave < T; ++c) {  // (uniform)
+                  const uint32_t w_lo = (uint32_t)__builtin_amdgcn_readlane((int)hv_lo, (int)c), w_hi = (uint32_t)__builtin_amdgcn_readlane((int)hv_hi, (int)c);
+                  const SkmDealAt d = skm_deal_at(((uint64_t)w_hi << 32) | w_lo, (uint32_t)lane, dc);
+                  const uint32_t o = d.o, j = d.j & 7u;
+                  const uint32_t xbh = __shfl(r.y, (int)o, kWave), xbl = __shfl(r.z, (int)o, kWave), p0 = __shfl(r.w, (int)o, kWave);
+                  const uint64_t win = (((uint64_t)xbh << 32) | xbl) << (2 * j);
+                  const uint64_t rc = skm_win_rc(win, k, kmask), f = (win << 2) & kmask;
+                  const unsigned head = (unsigned)(win >> 62), tail = ((uint32_t)win >> (62 - 2 * k)) & 3u;
+                  const unsigned long long key = skm_s1_key(f, rc, head, tail);
+                  const uint32_t klo = (uint32_t)key, khi = (uint32_t)(key >> 32), pos = p0 + j;
+                  [[maybe_unused]] uint32_t tg = 0;
+                  if constexpr (TAGS) tg = (uint8_t)(__shfl((uint32_t)tag, (int)o, kWave) + (pos < p0 ? 1u : 0u));  // (the carry across 2^32, as the insert has it)
+                  bool mn = c * kWave + (uint32_t)lane < T;
+                  // (a redone half takes its own windows only: those of the other half are not in the table)
+                  if (sub) mn = mn && skm_in_round(skm_mix2((klo * 0xC2B2AE35u) ^ (khi * 0x27D4EB2Fu)), sub, rj);
+                  if (mn) {
+                    uint32_t h = ((klo * 0x9E3779B1u) ^ (khi * 0x85EBCA6Bu)) >> (32 - kSkmLogSlots);
+                    // the window's key IS in the table; a fault of the logic must not spin: NSLOT steps at the most, then an error the host throws on
+                    int n = 0;
+                    while (keys[h] != key && n < NSLOT) {
+                      h = (h + 1) & (NSLOT - 1);
+                      ++n;
+                    }
+                    if (n >= NSLOT) atomicOr(a.err, 4u);
+                    else if (cnts[h] < m) a.solid_bytes[((uint64_t)tg << 32) | pos] = 1;
+                  }
+                }
+              }
+            }
+          }
+          __syncthreads();  // between look and clear: every wavefront has finished its look-ups (and read s_look) before a slot is emptied
+#pragma unroll
+          for (int it = 0; it < W; ++it) {
+            const int sl = it * NT + tid;
+            keys[sl] = kEmpty;
+            cnts[sl] = 0;
+          }
+          if (tid == 0) s_look = 0;
+          // between clear and the next round's inserts: a slot is emptied by ONE thread, and another wavefront's compare-and-swap on it must
+          // come behind that (the other forms clear a slot in the walk, in front of the barrier above the list)
+          __syncthreads();
         }
         // (no barrier here: the next round's inserts touch the table and the other parity's counters only; its walk, which writes the
         //  list again, comes behind that round's first barrier — by then every thread has left this loop)
@@ -1315,13 +1431,17 @@ struct CountSkmArgs {
   uint32_t n_giant, giant_limit;
 };
 
-template <bool TAGS, int G, bool EVENTS = false, bool GIANT = false>
+// LV: the levels of the thermometer per neighbouring base — 2 (min count <= 2), or 4 (s1_skm_max_m, min count 3 and 4: base in front x
+// bits 4x .. 4x + 3, base behind x bits 16 + 4x .. 19 + 4x of chw, bit l of a field = "seen l + 1 times"; all 32 bits, the two flags written
+// over the word after the walk as in the other form).  LV 4 is built for G 2, one GPU, bins whole; the LV 2 forms are the code they were
+template <bool TAGS, int G, bool EVENTS = false, bool GIANT = false, int LV = 2>
 __global__ __launch_bounds__(kSkmThreads) void k_count_skm(SkmSrcs srcs, CountSkmArgs a, uint32_t *__restrict__ ticket) {
+  static_assert(LV == 2 || (LV == 4 && G == 2 && !EVENTS && !GIANT), "four levels: one GPU, bins whole");
   constexpr int NT = kSkmThreads, NSLOT = 1 << kSkmLogSlots, W = NSLOT / NT;
   constexpr unsigned long long kEmpty = ~0ull;  // never a key: the bits below the (k+1)-mer are zero
   __shared__ unsigned long long keys[NSLOT];
   __shared__ uint32_t cnts[NSLOT];
-  __shared__ uint32_t chw[NSLOT];  // base in front x: bit 2x seen once, 2x + 1 seen twice; base behind x: bits 8 + 2x, 9 + 2x; after the walk: flags << 30
+  __shared__ uint32_t chw[NSLOT];  // base in front x: bit 2x seen once, 2x + 1 seen twice; base behind x: bits 8 + 2x, 9 + 2x (LV 4: four bits a base, above); after the walk: flags << 30
   __shared__ uint32_t lhist[kSegHist];
   __shared__ unsigned long long heads[kSkmThreads / kWave][8];
   __shared__ uint32_t s_bad, s_nclaimed, s_edge_cur, s_flagged, s_tk;
@@ -1467,11 +1587,24 @@ __global__ __launch_bounds__(kSkmThreads) void k_count_skm(SkmSrcs srcs, CountSk
               if (old != kEmpty && old != key) return false;
               atomicAdd(&cnts[hh], 1u);
               if (old == kEmpty) ++claims;
+              if constexpr (LV == 4) {
+                // an occurrence climbs its base's field until it sets a bit that was clear: every occurrence sets ONE bit, whatever the
+                // order the lanes arrive in, so bit l is set once l + 1 occurrences have been here (at most four operations; a fifth
+                // occurrence finds the field full and leaves it)
+                uint32_t add = (pv < 4 ? 1u << (4 * pv) : 0u) | (nx < 4 ? 1u << (16 + 4 * nx) : 0u);  // ('$' counts for nothing)
+#pragma unroll
+                for (int l = 0; l < LV; ++l) {
+                  if (!add) break;
+                  const uint32_t o = atomicOr(&chw[hh], add);
+                  add = (o & add & 0x77777777u) << 1;  // the bits that were set already: one level up (not out of the field)
+                }
+              } else {
               const uint32_t add1 = (pv < 4 ? 1u << (2 * pv) : 0u) | (nx < 4 ? 1u << (8 + 2 * nx) : 0u);  // ('$' counts for nothing)
               if (add1) {
                 const uint32_t o = atomicOr(&chw[hh], add1);
                 const uint32_t again = ((o & add1) << 1) & ~o;  // a base seen before and now again: seen twice
                 if (again) atomicOr(&chw[hh], again);
+              }
               }
               return true;
             };
@@ -1560,7 +1693,7 @@ __global__ __launch_bounds__(kSkmThreads) void k_count_skm(SkmSrcs srcs, CountSk
           wc[it] = cnts[sl];
           wf[it] = chw[sl];
         }
-        const uint32_t lvl = m >= 2 ? 0xAAu : 0x55u;
+        [[maybe_unused]] const uint32_t lvl = m >= 2 ? 0xAAu : 0x55u;
         uint32_t solid_bits = 0, n_dist = 0;
         bool any_flag = false;
 #pragma unroll
@@ -1574,7 +1707,13 @@ __global__ __launch_bounds__(kSkmThreads) void k_count_skm(SkmSrcs srcs, CountSk
             else atomicAdd(&a.hist[hb], 1ull);
             if (cnt >= m) {
               solid_bits |= 1u << it;
-              const bool has_in = (wf[it] & lvl) != 0, has_out = ((wf[it] >> 8) & lvl) != 0;
+              bool has_in, has_out;
+              if constexpr (LV == 4) {  // bit m - 1 of every field
+                has_in = (wf[it] & (0x1111u << (m - 1u))) != 0;
+                has_out = (wf[it] & (0x11110000u << (m - 1u))) != 0;
+              } else {
+                has_in = (wf[it] & lvl) != 0, has_out = ((wf[it] >> 8) & lvl) != 0;
+              }
               fb = (has_in ? 0u : 1u) | (has_out ? 0u : 2u);
               any_flag = any_flag || fb != 0;
             }
@@ -1688,11 +1827,15 @@ __global__ __launch_bounds__(kSkmThreads) void k_count_skm(SkmSrcs srcs, CountSk
 }
 
 // ---- host ----
+// s1_skm_max_m: the largest min count served on super-k-mer records on ONE GPU — 2, or 3 / 4 with the LOOK form of k_s1_skm and the LV 4 form
+// of k_count_skm (values outside 2..4: the nearest)
+uint32_t s1_skm_max_m(const mhx_ctx *c) { return (uint32_t)std::min<long long>(std::max<long long>(c->opt("s1_skm_max_m", 2), 2), 4); }
+
 bool s1_skm_applies(const mhx_ctx *c, uint32_t k, uint32_t m, int want_mercy) {
   const SeqSet &s = c->seqs;
   const long long knob = c->opt("s1_skm", 1);
   if (!knob || want_mercy || c->global_bases || c->n_parts > 1 || c->filter_on || c->accumulate || c->pos_base) return false;
-  if (k < 19 || k > 22 || m < 1 || m > 2) return false;
+  if (k < 19 || k > 22 || m < 1 || m > s1_skm_max_m(c)) return false;
   if (!s.n_seqs || s.max_len < k + 1 || (s.n_bases >> 36)) return false;
   // (reads of several lengths: every read takes the blocks of the longest — while at least s1_var_min_fill per cent of them hold windows)
   if (!s.fixed_len && (double)s.n_bases * 100.0 < (double)c->opt("s1_var_min_fill", 50) * (double)s.n_seqs * s.max_len) return false;
@@ -1726,7 +1869,7 @@ int s1_skm_passes(const mhx_ctx *c, uint32_t k) {
   return (int)std::min(64.0, std::max(1.0, std::ceil(need / budget)));
 }
 
-bool s1_skm_front(mhx_ctx *c, uint32_t k, SkmFront *f, int pass, int n_passes, int bin_bits_agreed, bool for_count) {
+bool s1_skm_front(mhx_ctx *c, uint32_t k, SkmFront *f, int pass, int n_passes, int bin_bits_agreed, bool for_count, bool bins_whole) {
   SeqSet &s = c->seqs;
   hipStream_t st = c->stream;
   const bool var = s.fixed_len == 0;
@@ -1846,7 +1989,8 @@ bool s1_skm_front(mhx_ctx *c, uint32_t k, SkmFront *f, int pass, int n_passes, i
   if ((uint32_t)h[1] != 0 || h[0] > cap) return false;
   const uint64_t n = h[0];
   // s1_skm_giant: a bin over the limit is worked in slices by several workgroups (skm_giant.h) instead of costing the job the path — one GPU
-  const bool giant = !c->global_bases && c->n_parts <= 1 && c->opt("s1_skm_giant", 0) != 0;
+  // (bins_whole: min count 3 and 4 — the forms of the group-by that serve them take a bin whole; one beyond s1_skm_max_bin gives the job up)
+  const bool giant = !bins_whole && !c->global_bases && c->n_parts <= 1 && c->opt("s1_skm_giant", 0) != 0;
   SkmGiantKnobs gk;
   gk.max_records = (uint64_t)std::max<long long>(c->opt("s1_skm_giant_max", 1 << 21), 1);
   gk.keys = (uint64_t)std::max<long long>(c->opt("s1_skm_giant_keys", 4096), 1);
@@ -1986,22 +2130,31 @@ void s1_skm_groups_launch(mhx_ctx *c, bool agg, unsigned grid, const SkmFront &f
     if (giant) MHX_SKM_G(AGGV, TAGV, true);  \
     else MHX_SKM_G(AGGV, TAGV, false);       \
   } while (0)
+  // min count 3 and 4 (s1_skm_max_m): the LOOK form, whatever s1_skm_deal says — one GPU (the marks go to the byte map), bins whole
+  const bool look = m >= 3;
+  if (look && (marks_raw || giant)) throw Error("s1_skm_groups: min count 3 and 4 are served on one GPU, bins whole");
+#define MHX_SKM_LOOK(AGGV, TAGV) hipLaunchKernelGGL((k_s1_skm<AGGV, TAGV, 2, false, true>), dim3(grid), dim3(kSkmThreads), 0, st, srcs, a, ticket)
   MHX_LAUNCH(c, "s1_skm_groups", (double)f.n_records * 16, {
-    if (agg && tags) MHX_SKM(true, true);
+    if (look && agg && tags) MHX_SKM_LOOK(true, true);
+    else if (look && agg) MHX_SKM_LOOK(true, false);
+    else if (look && tags) MHX_SKM_LOOK(false, true);
+    else if (look) MHX_SKM_LOOK(false, false);
+    else if (agg && tags) MHX_SKM(true, true);
     else if (agg) MHX_SKM(true, false);
     else if (tags) MHX_SKM(false, true);
     else MHX_SKM(false, false);
   });
+#undef MHX_SKM_LOOK
 #undef MHX_SKM
 #undef MHX_SKM_G
 }
 
-// ---- `count` on super-k-mer records: one GPU, 19 <= k <= 21 (k + 10 bases and two flags in a record), min count <= 2, one pass ----
+// ---- `count` on super-k-mer records: one GPU, 19 <= k <= 21 (k + 10 bases and two flags in a record), min count <= 2 (s1_skm_max_m: up to 4), one pass ----
 bool count_skm_applies(const mhx_ctx *c, uint32_t k, uint32_t m) {
   const SeqSet &s = c->seqs;
   const long long knob = c->opt("count_skm", 1);
   if (!knob || !c->opt("s1_skm", 1) || c->global_bases || c->n_parts > 1 || c->filter_on || c->accumulate || c->pos_base) return false;
-  if (k < 19 || k > 21 || m < 1 || m > 2) return false;
+  if (k < 19 || k > 21 || m < 1 || m > s1_skm_max_m(c)) return false;
   if (!s.n_seqs || s.max_len < k + 1 || (s.n_bases >> 36)) return false;
   if (!s.fixed_len && (double)s.n_bases * 100.0 < (double)c->opt("s1_var_min_fill", 50) * (double)s.n_seqs * s.max_len) return false;
   const uint64_t n_win = s.n_bases > s.n_seqs * (uint64_t)k ? s.n_bases - s.n_seqs * (uint64_t)k : 0;
@@ -2044,8 +2197,13 @@ static uint32_t count_skm_launch(mhx_ctx *c, uint32_t k, uint32_t m, const SkmFr
     else if (g2) hipLaunchKernelGGL((k_count_skm<false, 2, EV, GV>), dim3(grid), dim3(kSkmThreads), 0, st, srcs, a, ticket);              \
     else hipLaunchKernelGGL((k_count_skm<false, 4, EV, GV>), dim3(grid), dim3(kSkmThreads), 0, st, srcs, a, ticket);                      \
   } while (0)
+  // min count 3 and 4 (s1_skm_max_m): four thermometer levels, whatever count_skm_group says — one GPU, bins whole
+  const bool lv4 = m >= 3;
+  if (lv4 && (ev_raw || giant)) throw Error("count_skm_groups: min count 3 and 4 are served on one GPU, bins whole");
   MHX_LAUNCH(c, "count_skm_groups", (double)f.n_records * 16, {
-    if (ev_raw) MHX_CSKM(true, false);
+    if (lv4 && tags) hipLaunchKernelGGL((k_count_skm<true, 2, false, false, 4>), dim3(grid), dim3(kSkmThreads), 0, st, srcs, a, ticket);
+    else if (lv4) hipLaunchKernelGGL((k_count_skm<false, 2, false, false, 4>), dim3(grid), dim3(kSkmThreads), 0, st, srcs, a, ticket);
+    else if (ev_raw) MHX_CSKM(true, false);
     else if (giant) MHX_CSKM(false, true);
     else MHX_CSKM(false, false);
   });
@@ -2065,7 +2223,7 @@ static uint32_t count_skm_launch(mhx_ctx *c, uint32_t k, uint32_t m, const SkmFr
 bool count_skm_groups(mhx_ctx *c, uint32_t k, uint32_t m, uint32_t *first_0_out, uint32_t *last_0_in_p1, unsigned long long *hist, CountStreamOut *o, bool *touched,
                       int pass, int n_passes) {
   SkmFront f{};
-  if (!s1_skm_front(c, k, &f, pass, n_passes, 0, true)) {
+  if (!s1_skm_front(c, k, &f, pass, n_passes, 0, true, m >= 3)) {
     if (f.why) o->skm_why = "a bin of " + std::to_string(f.max_bin) + " records, " + f.why;
     return false;
   }
@@ -2185,6 +2343,16 @@ void s1_skm_hp_publish(mhx_ctx *c, const SkmFront &f, uint32_t k, uint32_t m, ui
   if (agg_specs && agg_hist) specs = *agg_specs;
   MHX_LAUNCH(c, "s1_skm_hp", 64.0, hipLaunchKernelGGL(k_skm_hp_publish, dim3(1), dim3(64), 0, c->stream, f.hp, (int)k, m, solid_bytes, hist, agg_items, agg_cursor,
                                                        agg ? 1 : 0, specs, agg_specs ? agg_hist : nullptr));
+}
+
+uint64_t s1_skm_beside_below(mhx_ctx *c, const SkmFront &f, uint32_t k, uint32_t m) {
+  if (!f.hp || m < 3) return 0;
+  unsigned long long *res = c->ws("skm_hp_res", 64).as<unsigned long long>();
+  hipLaunchKernelGGL(k_skm_beside_check, dim3(1), dim3(kSkmRepN), 0, c->stream, f.hp, f.rep ? 1 : 0, (int)k, m, res);
+  unsigned long long h = 0;
+  MHX_HIP(hipMemcpyAsync(&h, res, 8, hipMemcpyDeviceToHost, c->stream));
+  MHX_HIP(hipStreamSynchronize(c->stream));
+  return h;
 }
 
 // s1_skm_rep: the keys of the windows of period <= 4 counted by k_skm_make<.., REP> (after the last pass of the group-by; agg_items has room for

@@ -1,6 +1,6 @@
 """Randomised libraries through stage 1 / count on super-k-mer records against the oracle (GPU).
 
-    python tools/fuzz_skm.py [--repeats] [--giants] [seconds] [seed]
+    python tools/fuzz_skm.py [--repeats] [--giants] [--min-count] [seconds] [seed]
 
 Every round draws a library (fixed or ragged read lengths, planted poly-X / short-period repeats / duplicated reads), k in 19..22,
 min count 1..2 and a set of knobs (bins, passes, table fill, probe limit, tags, dealing, cap), runs read2sdbg stage 1 + stage 2 and
@@ -10,7 +10,9 @@ counts, first_0_out / last_0_in).  Prints a line per round; exits 1 at the first
 other reads — and draws s1_skm_rep (the windows of period <= 4 counted beside the records).  Drawn from a generator of their own: without
 the flag a seed gives the round it always gave.
 --giants: every round also draws s1_skm_giant (giant bins in slices), a small s1_skm_max_bin — so that bins of ordinary reads are giant
-bins, many of them — and forced slice counts, from a third generator.  The line of a round counts the plans that used slices."""
+bins, many of them — and forced slice counts, from a third generator.  The line of a round counts the plans that used slices.
+--min-count: every round draws min count 3..4 instead of 1..2, and s1_skm_max_m (the largest min count served on super-k-mer records: mostly
+4, sometimes 3 — then a round at 4 takes the prefix plan — or 2), from a fourth generator: without the flag a seed gives the round it always gave."""
 import os
 import sys
 import time
@@ -25,7 +27,8 @@ from megahit_amd import lib, synth  # noqa: E402
 
 RESET = dict(s1_skm=1, s1_stream_fill=7168, s1_stream_probes=1024, s1_skm_max_bin=65536, s1_skm_bin_bits=0, s1_skm_tags=0, s1_skm_cap_pct=36, s1_var_min_fill=50,
              s1_skm_passes=0, s1_skm_deal=2, s1_skm_hp=1, count_skm=1, count_skm_group=2, s1_skm_split=1, s1_skm_split_stage=2560,
-             s1_skm_make_grid=0, s1_skm_rep=0, s1_skm_giant=0, s1_skm_giant_slices=0, s1_skm_giant_work_pct=25, s1_skm_giant_keys=4096, s1_skm_giant_max=1 << 21)
+             s1_skm_make_grid=0, s1_skm_rep=0, s1_skm_giant=0, s1_skm_giant_slices=0, s1_skm_giant_work_pct=25, s1_skm_giant_keys=4096, s1_skm_giant_max=1 << 21,
+             s1_skm_max_m=2)
 
 
 def library(rng):
@@ -101,8 +104,8 @@ def knobs(rng):
 
 
 def main():
-    argv = [a for a in sys.argv[1:] if a not in ("--repeats", "--giants")]
-    repeats, giants = "--repeats" in sys.argv[1:], "--giants" in sys.argv[1:]
+    argv = [a for a in sys.argv[1:] if a not in ("--repeats", "--giants", "--min-count")]
+    repeats, giants, min_count = "--repeats" in sys.argv[1:], "--giants" in sys.argv[1:], "--min-count" in sys.argv[1:]
     seconds = float(argv[0]) if len(argv) > 0 else 60.0
     seed0 = int(argv[1]) if len(argv) > 1 else 1
     e = lib.Engine(0)
@@ -129,6 +132,10 @@ def main():
             if rng_g.random() < 0.1:
                 opts["s1_skm_giant_max"] = int(rng_g.choice([100, 3000]))
             opts["s1_skm_cap_pct"] = 1000  # (thin output regions of a small job: room for a whole bin's items in one)
+        if min_count:  # (and again: min count 3 and 4 on super-k-mer records, s1_skm_max_m)
+            rng_m = np.random.default_rng([seed, 0x3C4])
+            m = int(rng_m.integers(3, 5))
+            opts["s1_skm_max_m"] = int(rng_m.choice([4, 4, 4, 4, 3, 2]))
         pkg = ob.Package(reads, reverse=True)
         e.load_sequences(pkg.words(), pkg.n_seqs, 0, pkg.start())
         for n_, v in opts.items():
