@@ -423,6 +423,15 @@ class Engine:
             self._chk(self.lib.mhx_fetch(self.h, which, _ptr(out), 0, nbytes))
         return out
 
+    def fetch_range(self, which, dtype, offset, count):
+        """`count` elements of `dtype` from element `offset` of a result buffer (the offset argument of mhx_fetch): a look at a part of
+        a buffer too large to bring over whole; a range beyond the buffer raises"""
+        size = np.dtype(dtype).itemsize
+        out = np.empty(int(count), dtype=dtype)
+        if count:
+            self._chk(self.lib.mhx_fetch(self.h, which, _ptr(out), int(offset) * size, int(count) * size))
+        return out
+
     def synchronize(self):
         self._chk(self.lib.mhx_synchronize(self.h))
 

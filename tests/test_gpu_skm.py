@@ -121,7 +121,7 @@ def test_homopolymer_windows_are_counted_beside_the_records(engine, case):
 @pytest.mark.parametrize("kind,k,m", [("pe100", 21, 2), ("repeats100", 22, 2), ("short30", 19, 1)])
 def test_three_sort_passes_and_position_tags(engine, kind, k, m, opts):
     """2^17..2^20 bins take a third sort pass (jobs beyond 14 M reads); s1_skm_tags: the kernel of read sets beyond 2^32 bases (tag 0 here;
-    tests/test_gpu_fullsize_100M.py has 1.5 x 10^10 bases)"""
+    tests/test_gpu_skm_past_2_32.py has a read across 2^32 under every form, tests/test_gpu_fullsize_100M.py 1.5 x 10^10 bases)"""
     run(engine, fixed_library(kind, seed=k + m), k, m, dict(opts, s1_skm=2, s1_skm_max_bin=1 << 30))
 
 
