@@ -137,6 +137,14 @@ int mhx_set_option(mhx_ctx *, const char *name, long long value);
  *   s1_stream_wide (1)     0: stage 1 at k = 23..29 takes the segment group-by (k_s1_seg); 1: the bucket streaming with 64-bit table keys
  *   s2_agg_from_count (1)  0: stage 2 always makes its solid items per occurrence where stage 1 left no aggregated ones; 1: min count 1
  *                          (k <= 27) and min count >= 2 at k = 23..27 take them from a count of the (k+1)-mers (s2.hip s2_agg_from_count)
+ *                          3: as 1, and a job the route gives up on fails mhx_read2sdbg_s2 ("... stage 2 from a count given up (why)", nothing
+ *                          published) instead of running per occurrence — for a caller that left the memory plan to s2_count_pass_items
+ *   s2_count_pass_items (0)  > 0: that count runs in passes of at most so many records over contiguous ranges of its own lv1 buckets (a
+ *                          bucket above it: a pass of its own), every pass appends its aggregated items to one array, the '$' items are
+ *                          added once, one sort, one emission — the 24.5 bytes per record of the count are what a large job cannot hold
+ *                          at once.  More than 64 passes: the route declines.  0: one count over everything
+ *   s2_count_budget_mb (0)   > 0: the route in passes checks its exact need (mhx_s2_from_count_bytes with the items counted so far, plus
+ *                          a 16th) against so many MiB after every pass and gives up beyond them: the per-occurrence path runs
  *   s2_dummy_list (1)      the '$' items of aggregated stage 2 (csrc/s2.hip k_s2d_emit): 1: the run ends of a workgroup's bitmap words are
  *                          compacted into an LDS list and dealt one per lane, so that the gathers from the reads are in flight together;
  *                          0: every thread walks the run ends of its own words one after the other (same items, other order);
@@ -726,6 +734,16 @@ uint64_t mhx_stage_pass_bytes(mhx_ctx *, int stage, uint32_t k, uint32_t min_cou
  * decides only whether one run fits; the ranges of several passes are sized with mhx_stage_pass_bytes).  n_items: the caller's
  * estimate of the stage's per-occurrence items.  0: no such route, ask mhx_stage_pass_bytes. */
 uint64_t mhx_stage_once_bytes(mhx_ctx *, int stage, uint32_t k, uint32_t min_count, uint64_t n_items);
+/* Device bytes stage 2 from a count of the (k+1)-mers holds besides the stage's fixed state when its count runs in passes of at most
+ * pass_records records over its own lv1 bucket ranges (option s2_count_pass_items; 0: everything at once): the count's lean figure for
+ * one pass (that of mhx_stage_pass_bytes(MHX_STAGE_COUNT) without the solid-edge outputs), its per-read scratch and bitmap, and the
+ * accumulated items at sort time, 25 bytes each (two 8-byte buffers, the first grown by a quarter with old and new held during the
+ * copy; the emission's word per item; status words and records).  The items are not known before the count: the figure takes ONE
+ * aggregated or '$' item per record of the count plus 4 per read, at most est_items (the caller's estimate of the per-occurrence items,
+ * as for mhx_stage_once_bytes) — every second record a new edge; the metagenome shard has 0.45 per record.  A library of less
+ * redundancy exceeds it: the route checks its exact need after every pass against s2_count_budget_mb and gives up beyond it.
+ * The allocator's headroom (a 16th) is the caller's to add.  0: the route does not apply (or an error). */
+uint64_t mhx_s2_from_count_bytes(mhx_ctx *, uint32_t k, uint32_t min_count, uint64_t est_items, uint64_t pass_records);
 int mhx_set_bucket_filter(mhx_ctx *, const uint8_t *keep, uint64_t expected_items, uint64_t batch_bytes, int accumulate);
 
 /* ---- measurement ---- */

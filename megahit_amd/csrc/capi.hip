@@ -601,6 +601,13 @@ int mhx_reset(mhx_ctx *c) {
     c->part_begin.clear();
     c->pos_base = c->global_bases = 0;
     c->s1 = mhx::S1Handoff();  // (behind the synchronisation above: no count is on its way any more)
+    {  // the items a stage 2 from a count in passes accumulated (s2.hip): a job's data, not a buffer the next job wants
+      auto acc = c->work.find("s2c_items_acc");
+      if (acc != c->work.end()) {
+        acc->second.release();
+        c->work.erase(acc);
+      }
+    }
     c->n_route = 0;
     c->s1_density = 0;
     c->filter_kept = 0;
@@ -1260,6 +1267,17 @@ uint64_t mhx_stage_once_bytes(mhx_ctx *c, int stage, uint32_t k, uint32_t min_co
     // base, where the caller's item estimate (per-occurrence items) is ~2.2 per base — and the few aggregated items behind them
     if (stage == MHX_STAGE_S2 && c->seqs.n_seqs && !c->filter_on && mhx::s2_agg_from_count_applies(c, k, min_count)) return n_items * 13;
     return 0;
+  } catch (...) {
+    return 0;
+  }
+}
+uint64_t mhx_s2_from_count_bytes(mhx_ctx *c, uint32_t k, uint32_t min_count, uint64_t est_items, uint64_t pass_records) {
+  try {
+    if (!c->seqs.n_seqs || c->filter_on || !mhx::s2_agg_from_count_applies(c, k, min_count)) return 0;
+    const uint64_t records = mhx::s2_count_records(c, k);
+    // (the items are not known before the count: one per record and four per read, at most the caller's per-occurrence estimate)
+    const uint64_t items = std::min<uint64_t>(records + 4 * c->seqs.n_seqs, est_items);
+    return mhx::s2_from_count_need(c, min_count, pass_records ? std::min(pass_records, records) : records, items);
   } catch (...) {
     return 0;
   }

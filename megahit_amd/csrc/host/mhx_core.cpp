@@ -443,10 +443,81 @@ void report_rank_memory(mhx_comm *cm) {
          (unsigned long long)peak, (unsigned long long)budget);
   }
 }
+// Plan by TIME as well as by space: -> the passes P that minimise P * t_scan + working_set / P * rate (0: by space alone), logged.
+// (see plan_ranges; MHX_PLAN_BY_TIME=0 switches it off, MHX_ALLOC_S_PER_GB sets the rate: tests)
+int plan_passes_by_time(mhx_ctx *c, double working_set) {
+  if (getenv("MHX_PLAN_BY_TIME") && atoi(getenv("MHX_PLAN_BY_TIME")) == 0) return 0;
+  double malloc_s = 0;
+  uint64_t abytes = 0;
+  mhx_alloc_stats(&malloc_s, nullptr, &abytes, nullptr);
+  // (seconds per byte.  The first few GB of a process come fast whatever the box — at 100 M reads the 4.6 GB of the read store
+  //  took 0.1 s, the 239 GB behind them 6.1 s — so what has been seen so far is only a lower bound: a working set of more than
+  //  64 GB is planned with at least 5 ms per GB — the boxes of this pool showed 0.03 (one box), 2-4, 17 and 25 ms per GB for the
+  //  same 239 GB: a plan for 5 costs a fast box 0.25 s of extra read scans and saves a slow one 2-3 s.  A resident server keeps
+  //  its buffers between requests: nothing to plan for there.)
+  double rate = abytes >= (1ull << 30) ? malloc_s / (double)abytes : 0.0;
+  if (working_set > 64e9 && !g_serving) rate = std::max(rate, 5e-12);
+  if (g_serving) rate = 0;
+  if (const char *e = getenv("MHX_ALLOC_S_PER_GB")) rate = atof(e) * 1e-9;
+  const double t_scan = 6.5e-12 * (double)mhx_num_bases(c);
+  if (!(rate > 0 && t_scan > 0)) return 0;
+  const int p = (int)std::min(16.0, std::floor(std::sqrt(working_set * rate / t_scan) + 0.5));
+  if (p < 2) return 0;
+  info("Memory plan by time: hipMalloc ran at %.1f ms per GB so far; %d passes of ~%.1f GB each instead of one working set of %.1f GB", rate * 1e12, p,
+       working_set / p / 1e9, working_set / 1e9);
+  return p;
+}
+// Stage 2 from a count of the (k+1)-mers whose one run does not fit: its count in passes over the count's OWN lv1 bucket ranges (include/mhx.h:
+// s2_count_pass_items, mhx_s2_from_count_bytes) — the largest pass whose figure, with the allocator's headroom, fits `avail`, fewer records
+// where the plan by time says so.  At the 40 M-read shard under a budget that fails the once-fit by one per cent: 558 ms of kernels in 4 count
+// passes against 890 ms for the per-occurrence lv1 passes (profiles/r18_s2_count_passes.json).  MHX_S2_COUNT_PASSES=0 switches it off.
+// -> the passes planned, with the options set and s2_agg_from_count = 3 (a give-up fails the call); 0: not planned, nothing set
+struct S2CountPlan {
+  bool allowed = true;  // in: false once the route gave this job up
+  size_t passes = 0;    // out: the count passes planned, 0: the lv1 plan stands
+};
+size_t plan_s2_count_passes(mhx_ctx *c, uint32_t k, uint32_t m, double est_items, double avail) {
+  const char *sw = getenv("MHX_S2_COUNT_PASSES");
+  if (sw && atoi(sw) == 0) return 0;
+  const double headroom = 17.0 / 16.0;
+  const uint64_t est = (uint64_t)est_items;
+  if (!mhx_s2_from_count_bytes(c, k, m, est, 1) || (double)mhx_s2_from_count_bytes(c, k, m, est, 1) * headroom > avail) return 0;
+  std::vector<uint64_t> hist(MHX_NUM_BUCKETS);
+  CK(mhx_set_bucket_filter(c, nullptr, 0, plan_batch_bytes(), 0));  // (no filter: the batch size alone, for a histogram taken over batches)
+  CK(mhx_bucket_histogram(c, MHX_STAGE_COUNT, k, m, hist.data()));
+  uint64_t records = 0;
+  for (uint64_t v : hist) records += v;
+  if (!records) return 0;
+  uint64_t lo = 1, hi = records;  // the largest pass that fits (the figure grows with the pass)
+  while (lo < hi) {
+    const uint64_t mid = lo + (hi - lo + 1) / 2;
+    if ((double)mhx_s2_from_count_bytes(c, k, m, est, mid) * headroom <= avail) lo = mid;
+    else hi = mid - 1;
+  }
+  uint64_t pass = lo;
+  const double working_set = (double)mhx_s2_from_count_bytes(c, k, m, est, records) - (double)mhx_s2_from_count_bytes(c, k, m, est, 1);
+  if (const int p = plan_passes_by_time(c, working_set)) pass = std::min<uint64_t>(pass, (uint64_t)((double)records / p * 1.02));
+  pass = std::max<uint64_t>(pass, 1);
+  size_t n_passes = 1;  // as the library cuts them (s2.hip s2_count_ranges)
+  uint64_t acc = 0;
+  for (uint64_t v : hist) {
+    if (acc && acc + v > pass) {
+      ++n_passes;
+      acc = 0;
+    }
+    acc += v;
+  }
+  if (n_passes < 2 || n_passes > 64) return 0;  // (more than the library's cap: it would decline)
+  CK(mhx_set_option(c, "s2_count_pass_items", (long long)pass));
+  CK(mhx_set_option(c, "s2_count_budget_mb", (long long)std::max(1.0, std::floor(avail / 1048576.0))));
+  CK(mhx_set_option(c, "s2_agg_from_count", 3));
+  info("Memory plan: stage 2 from a count in %zu passes over its own bucket ranges (at most %llu records each)", n_passes, (unsigned long long)pass);
+  return n_passes;
+}
 // fixed_bytes: device state of the stage that does not shrink with the bucket range (stage 1: the 1 B/base mark map, the
 // bitmap and the aggregated stage-2 items; count: first_0_out / last_0_in; all: sort status words ~ items / 3)
 std::vector<BucketRange> plan_ranges(mhx_ctx *c, int stage, uint32_t k, uint32_t m, size_t item_bytes, double items_upper_bound,
-                                     double fixed_bytes = 0) {
+                                     double fixed_bytes = 0, S2CountPlan *s2_count = nullptr) {
   uint64_t max_items = 0;
   double free_bytes = (double)mhx_device_free_bytes(c);
   if (const char *e = getenv("MHX_FREE_BYTES")) free_bytes = atof(e);  // tests: make the automatic plan fire on a small input
@@ -472,6 +543,11 @@ std::vector<BucketRange> plan_ranges(mhx_ctx *c, int stage, uint32_t k, uint32_t
     // filter, which switches such a route off, so its ranges are sized with the figure of a filtered pass below.
     const uint64_t once_bytes = mhx_stage_once_bytes(c, stage, k, m, (uint64_t)items_upper_bound);
     if (once_bytes && (double)once_bytes * headroom <= avail) return {{0, MHX_NUM_BUCKETS, 0}};
+    // ... unless that route cuts its own count into passes: then the single unfiltered range again
+    if (once_bytes && stage == MHX_STAGE_S2 && s2_count && s2_count->allowed) {
+      s2_count->passes = plan_s2_count_passes(c, k, m, items_upper_bound, avail);
+      if (s2_count->passes) return {{0, MHX_NUM_BUCKETS, 0}};
+    }
     // 2 sort buffers + filtered copy (+ status words); the library knows better where a stage has a leaner path
     const uint64_t probe = 1ull << 30, lib_bytes = mhx_stage_pass_bytes(c, stage, k, m, probe);
     const double per_item = headroom * (lib_bytes ? ((double)lib_bytes - lib_fixed) / (double)probe : 3.0 * (double)item_bytes + 1.0);
@@ -482,30 +558,8 @@ std::vector<BucketRange> plan_ranges(mhx_ctx *c, int stage, uint32_t k, uint32_t
     // 100 M reads) where the stage has that lean form (lib_bytes: the library says so).  The rate this very process has seen so far —
     // the read store it has just allocated — decides: P passes minimise P * t_scan + bytes(P) * rate.  MHX_PLAN_BY_TIME=0 switches it off.
     double time_cap = 0;
-    if (lib_bytes && (stage == MHX_STAGE_S1 || stage == MHX_STAGE_COUNT) && !(getenv("MHX_PLAN_BY_TIME") && atoi(getenv("MHX_PLAN_BY_TIME")) == 0)) {
-      double malloc_s = 0;
-      uint64_t abytes = 0;
-      mhx_alloc_stats(&malloc_s, nullptr, &abytes, nullptr);
-      // (seconds per byte.  The first few GB of a process come fast whatever the box — at 100 M reads the 4.6 GB of the read store
-      //  took 0.1 s, the 239 GB behind them 6.1 s — so what has been seen so far is only a lower bound: a working set of more than
-      //  64 GB is planned with at least 5 ms per GB — the boxes of this pool showed 0.03 (one box), 2-4, 17 and 25 ms per GB for the
-      //  same 239 GB: a plan for 5 costs a fast box 0.25 s of extra read scans and saves a slow one 2-3 s.  A resident server keeps
-      //  its buffers between requests: nothing to plan for there.)
-      double rate = abytes >= (1ull << 30) ? malloc_s / (double)abytes : 0.0;
-      if (per_item * items_upper_bound > 64e9 && !g_serving) rate = std::max(rate, 5e-12);
-      if (g_serving) rate = 0;
-      if (const char *e = getenv("MHX_ALLOC_S_PER_GB")) rate = atof(e) * 1e-9;  // tests
-      const double t_scan = 6.5e-12 * (double)mhx_num_bases(c);
-      if (rate > 0 && t_scan > 0) {
-        const double p_opt = std::sqrt(per_item * items_upper_bound * rate / t_scan);
-        const int p = (int)std::min(16.0, std::floor(p_opt + 0.5));
-        if (p >= 2) {
-          time_cap = items_upper_bound / p * 1.02;
-          info("Memory plan by time: hipMalloc ran at %.1f ms per GB so far; %d passes of ~%.1f GB each instead of one working set of %.1f GB", rate * 1e12,
-               p, per_item * items_upper_bound / p / 1e9, per_item * items_upper_bound / 1e9);
-        }
-      }
-    }
+    if (lib_bytes && (stage == MHX_STAGE_S1 || stage == MHX_STAGE_COUNT))
+      if (const int p = plan_passes_by_time(c, per_item * items_upper_bound)) time_cap = items_upper_bound / p * 1.02;
     if (items_upper_bound <= fit && time_cap == 0) return {{0, MHX_NUM_BUCKETS, 0}};
     max_items = (uint64_t)(time_cap > 0 ? std::min(fit, time_cap) : fit);
   }
@@ -890,9 +944,30 @@ int main_read2sdbg(int argc, char **argv) {
   }
   const size_t s2_item_bytes = (size_t)(((2 * k + 4 + 31) / 32 + 1) / 2 * 2) * 4;
   // per-occurrence path: up to 2 + 4/(solid run) items per base position; the aggregated path (k <= 22) is far smaller
-  const auto ranges2 = plan_ranges(c, MHX_STAGE_S2, k, m, s2_item_bytes, (m > 1 && k <= 22 ? 0.5 : 2.2) * (double)mhx_num_bases(c));
+  const double s2_items_bound = (m > 1 && k <= 22 ? 0.5 : 2.2) * (double)mhx_num_bases(c);
+  S2CountPlan s2_count;
+  const long long from_count_before = mhx_get_option(c, "s2_agg_from_count", 1);
+  auto ranges2 = plan_ranges(c, MHX_STAGE_S2, k, m, s2_item_bytes, s2_items_bound, 0, &s2_count);
   SdbgAcc acc;
-  for (size_t i = 0; i < ranges2.size(); ++i) {
+  bool s2_done = false;
+  if (s2_count.passes) {
+    // Stage 2 from a count in passes over its own bucket ranges (plan_s2_count_passes): one unfiltered call.  A job the route gives up on — an
+    // edge region overflowed, the items exceed the budget — fails the call with that message and nothing published: the lv1 bucket plan
+    // with the per-occurrence figure takes over.  Any other failure is an error.
+    mhx_sdbg_result pr;
+    s2_done = mhx_read2sdbg_s2(c, k, m, &pr) == 0;
+    mhx_set_option(c, "s2_count_pass_items", 0);
+    mhx_set_option(c, "s2_count_budget_mb", 0);
+    mhx_set_option(c, "s2_agg_from_count", from_count_before);
+    if (s2_done) acc.add(c, pr);
+    else {
+      const std::string why = mhx_last_error();
+      if (why.find("stage 2 from a count given up") == std::string::npos) fatal("%s", why.c_str());
+      info("%s; planning lv1 bucket ranges instead", why.c_str());
+      ranges2 = plan_ranges(c, MHX_STAGE_S2, k, m, s2_item_bytes, s2_items_bound);  // (without the route)
+    }
+  }
+  for (size_t i = 0; i < ranges2.size() && !s2_done; ++i) {
     set_range(c, ranges2, i, false);
     mhx_sdbg_result pr;
     CK(mhx_read2sdbg_s2(c, k, m, &pr));

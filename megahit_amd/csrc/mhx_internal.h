@@ -355,6 +355,15 @@ int run_count(mhx_ctx *c, uint32_t k, uint32_t m, mhx_count_result *out);
 // count on the bucket streaming of stage 1 (s1.hip: CountGenT, k_s1_stream<COUNT>)
 int s2_agg_compact_bits(uint32_t k);
 bool s2_agg_from_count_applies(const mhx_ctx *c, uint32_t k, uint32_t m);  // s2.hip: stage 2's solid items from a count of the (k+1)-mers  // count bits of a compact aggregated stage-2 item (k = 23..28), 0: none
+// ... with the count in passes over its own lv1 bucket ranges (s2_count_pass_items): at most kS2CountMaxPasses of them; s2_count_records: the
+// records of the whole count; s2_from_count_need: the device bytes the route holds beyond the stage's fixed state with passes of pass_records
+// records and n_items aggregated + '$' items (mhx_s2_from_count_bytes, and the route's own check against s2_count_budget_mb).
+// kS2CountItemBytes per item: two 8-byte buffers, the first grown by a quarter of headroom with old and new held during the copy (20),
+// the emission's 4-byte word per item, and a byte for the sort's status words and the SdBG records
+constexpr int kS2CountMaxPasses = 64;
+constexpr uint64_t kS2CountItemBytes = 25;
+uint64_t s2_count_records(const mhx_ctx *c, uint32_t k);
+uint64_t s2_from_count_need(const mhx_ctx *c, uint32_t m, uint64_t pass_records, uint64_t n_items);
 struct CountStreamOut {
   unsigned grid;      // workgroups = edge regions
   uint32_t cap;       // 8-byte edges a region holds

@@ -1129,7 +1129,10 @@ bool count_stream_groups(mhx_ctx *c, uint32_t k, uint32_t m, uint32_t *first_0_o
   } else {
     uint32_t *buf_a = nullptr, *buf_b = nullptr;
     SortPrep prep;
-    if (!count_stream_front(c, k, plan, edges_only, &buf_a, &buf_b, &n_items, &prep)) return false;  // (no read holds an edge: the general path knows what to publish)
+    if (!count_stream_front(c, k, plan, edges_only, &buf_a, &buf_b, &n_items, &prep)) {
+      o->n_items = 0;  // (no read holds an edge, or none in the kept buckets: the general path knows what to publish; a caller in passes sees an empty one)
+      return false;
+    }
     sorted = radix_sort(c, buf_a, buf_b, n_items, 3, KWv, plan.passes, &prep);
     spare = sorted == buf_a ? buf_b : buf_a;
   }
@@ -1142,7 +1145,9 @@ bool count_stream_groups(mhx_ctx *c, uint32_t k, uint32_t m, uint32_t *first_0_o
   // workgroups, so that a region holds at least ~6000 edges — with one workgroup, every record's (a region that overflows is
   // found only after the whole pass ran, and the tile path then repeats the work)
   const unsigned grid = (unsigned)std::min<uint64_t>(std::min<uint64_t>(n_buckets, cus), std::max<uint64_t>(n_items / 4096, 1));
-  const uint32_t region = (uint32_t)std::min<uint64_t>(n_items * 12 / 8 / grid, 0xFFFFFFF0u) & ~1u;  // (even: 16-byte entries at k >= 24)
+  // (pre-sorted sources bring a spare buffer of 12 bytes per record, s1_shared.h S1Sources)
+  const uint64_t room = pre ? 12 : count_record_room(n_items, edges_only);
+  const uint32_t region = (uint32_t)std::min<uint64_t>(n_items * room / 8 / grid, 0xFFFFFFF0u) & ~1u;  // (even: 16-byte entries at k >= 24)
   uint32_t *counts = c->ws("cs_edge_counts", (size_t)grid * 4).as<uint32_t>();
   unsigned long long *ctr = c->ws("s1_counters", 64).as<unsigned long long>();
   uint32_t *seg_err = c->ws("s1_seg_err", 64).as<uint32_t>();

@@ -1271,8 +1271,9 @@ bool count_stream_front(mhx_ctx *c, uint32_t k, const S1Plan &plan, bool edges_o
     if (keep && n_items > c->filter_expected) throw Error("bucket filter: more items in the kept buckets than announced");
     if (n_items == 0) return false;  // (no read holds an edge / no edge in the kept buckets: the general path knows what to publish)
   }
-  uint32_t *buf_a = c->ws("items_a", n_items * 12 + 64).as<uint32_t>();
-  uint32_t *buf_b = c->ws("items_b", n_items * 12 + 64).as<uint32_t>();
+  const uint64_t room = count_record_room(n_items, edges_only);
+  uint32_t *buf_a = c->ws("items_a", n_items * room + 64).as<uint32_t>();
+  uint32_t *buf_b = c->ws("items_b", n_items * room + 64).as<uint32_t>();
   *buf_a_out = buf_a;
   *buf_b_out = buf_b;
   *n_items_out = n_items;

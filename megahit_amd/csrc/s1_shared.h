@@ -173,5 +173,9 @@ void s1_classic_launch(mhx_ctx *c, int S, bool compact, bool agg, const uint32_t
 bool count_shape_is_fast(const mhx_ctx *c, uint32_t k, bool edges_only);  // the shapes CountGenT / CountGenVarT serve
 bool count_bucket_histogram_fast(mhx_ctx *c, uint32_t k, unsigned long long *hist);  // lv1 histogram of count's items from the packed reads
 bool count_stream_front(mhx_ctx *c, uint32_t k, const S1Plan &plan, bool edges_only, uint32_t **buf_a, uint32_t **buf_b, uint64_t *n_items, SortPrep *prep);
+// Bytes per record of the two record buffers.  The spare one holds the workgroups' edge regions: 12 bytes per record are room for three 16-byte
+// entries per four records, which counts on keys that repeat.  Edges only (stage 2 from a count), up to 65 536 records — a tiny library, or
+// a small pass of a count in passes, where every key may be new: 16 bytes, an entry per record (256 KiB more at the most)
+inline uint64_t count_record_room(uint64_t n_items, bool edges_only) { return edges_only && n_items <= 65536 ? 16 : 12; }
 
 }  // namespace mhx

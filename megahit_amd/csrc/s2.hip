@@ -1603,8 +1603,199 @@ bool s2_agg_from_count_applies(const mhx_ctx *c, uint32_t k, uint32_t m) {
   if (m > 1 && (k <= 22 || !c->s1.bitmap_is_s1s(k, m))) return false;  // (k <= 22: stage 1 made the aggregated items itself)
   return count_stream_applies(c, k, m, true);
 }
+// ---- the count in PASSES over its own lv1 bucket ranges (s2_count_pass_items > 0) ----
+// The 24.5 bytes per record of the count are what a large job cannot hold at once; the aggregated items are few (0.45 per record at the
+// metagenome shard).  So the count runs range by range under the bucket filter — over the lv1 bucket of the CANONICAL (k+1)-mer, so no key
+// is split between two passes — and every pass appends its items to one array, which is sorted and emitted once.
+uint64_t s2_count_records(const mhx_ctx *c, uint32_t k) {
+  const SeqSet &s = c->seqs;
+  if (s.fixed_len) return s.fixed_len > k ? s.n_seqs * (uint64_t)(s.fixed_len - k) : 0;
+  return s.n_bases > s.n_seqs * (uint64_t)k ? s.n_bases - s.n_seqs * (uint64_t)k : 0;
+}
+uint64_t s2_from_count_need(const mhx_ctx *c, uint32_t m, uint64_t pass_records, uint64_t n_items) {
+  const SeqSet &s = c->seqs;
+  // the count's lean figure for a pass (capi.hip mhx_stage_pass_bytes(MHX_STAGE_COUNT) without the solid-edge outputs): two 12-byte record
+  // buffers, status words, the giant buckets' partial sums and listed keys
+  const uint64_t count = pass_records * 24 + pass_records / 2 + s.n_bases / 3 + std::max<uint64_t>(2u << 20, pass_records / 64) * 16 + (32ull << 20);
+  // + first / last (8 bytes per read, nobody reads them), at min count 1 the bitmap of the (k+1)-mer starts, and kS2CountItemBytes per item
+  return count + s.n_seqs * 8 + (m == 1 ? s.n_bases / 8 + 16 : 0) + n_items * kS2CountItemBytes;
+}
+struct S2CountRange {
+  uint32_t lo, hi;
+  uint64_t n;
+};
+// contiguous ranges of lv1 buckets of at most `cap` records each (a bucket above the cap: a pass of its own, as the CLI's plan_ranges does)
+static std::vector<S2CountRange> s2_count_ranges(mhx_ctx *c, uint32_t k, uint32_t m, uint64_t cap) {
+  std::vector<uint64_t> hist(MHX_NUM_BUCKETS);
+  bucket_histogram(c, MHX_STAGE_COUNT, k, m, hist.data());  // (from the packed reads where count_bucket_histogram_fast applies, else over batches)
+  std::vector<S2CountRange> out;
+  uint32_t lo = 0;
+  uint64_t acc = 0;
+  for (uint32_t b = 0; b < MHX_NUM_BUCKETS; ++b) {
+    if (acc && acc + hist[b] > cap) {
+      out.push_back({lo, b, acc});
+      lo = b;
+      acc = 0;
+    }
+    acc += hist[b];
+  }
+  out.push_back({lo, (uint32_t)MHX_NUM_BUCKETS, acc});
+  return out;
+}
+// the handle's bucket filter while the route sets its own: what the caller left comes back, also behind an exception
+struct S2FilterGuard {
+  mhx_ctx *c;
+  bool on;
+  uint64_t expected;
+  uint32_t kept;
+  explicit S2FilterGuard(mhx_ctx *ctx) : c(ctx), on(ctx->filter_on), expected(ctx->filter_expected), kept(ctx->filter_kept) {}
+  ~S2FilterGuard() { off(); }
+  void off() {
+    c->filter_on = on;
+    c->filter_expected = expected;
+    c->filter_kept = kept;
+  }
+  void set(const S2CountRange &r) {
+    std::vector<uint32_t> bits(MHX_NUM_BUCKETS / 32, 0);
+    std::vector<uint8_t> lut(MHX_NUM_BUCKETS, 1);
+    for (uint32_t b = r.lo; b < r.hi; ++b) {
+      bits[b >> 5] |= 1u << (b & 31);
+      lut[b] = 0;
+    }
+    DevBuf &d = c->ws("filter_lut", MHX_NUM_BUCKETS);
+    DevBuf &db = c->ws("filter_bits", MHX_NUM_BUCKETS / 8);
+    MHX_HIP(hipMemcpyAsync(d.p, lut.data(), MHX_NUM_BUCKETS, hipMemcpyHostToDevice, c->stream));
+    MHX_HIP(hipMemcpyAsync(db.p, bits.data(), MHX_NUM_BUCKETS / 8, hipMemcpyHostToDevice, c->stream));
+    MHX_HIP(hipStreamSynchronize(c->stream));  // (the host vectors go out of scope)
+    c->filter_on = true;
+    c->filter_expected = r.n;
+    c->filter_kept = r.hi - r.lo;
+  }
+};
+// the knobs the route sets for its count unless the caller set them: gone again when the route is left, however
+struct S2KnobGuard {
+  mhx_ctx *c;
+  std::vector<std::string> set;
+  void put(const char *name, long long v) {
+    std::string env = std::string("MHX_") + name;
+    for (char &ch : env) ch = (char)toupper((unsigned char)ch);
+    if (c->options.count(name) || getenv(env.c_str())) return;
+    c->options[name] = v;
+    set.push_back(name);
+  }
+  ~S2KnobGuard() {
+    for (const std::string &n : set) c->options.erase(n);
+  }
+};
+// the accumulated item array of a run in passes: released unless the run got as far as the sort
+struct S2AccGuard {
+  mhx_ctx *c;
+  bool keep = false;
+  ~S2AccGuard() {
+    if (keep) return;
+    auto it = c->work.find("s2c_items_acc");
+    if (it == c->work.end()) return;
+    it->second.release();
+    c->work.erase(it);
+  }
+};
+// the exact need of the route against s2_count_budget_mb (0: no check), with the allocator's headroom: -> false when it is exceeded
+static bool s2_count_in_budget(const mhx_ctx *c, uint32_t m, uint64_t pass_records, uint64_t n_items) {
+  const long long mb = c->opt("s2_count_budget_mb", 0);
+  if (mb <= 0) return true;
+  const uint64_t need = s2_from_count_need(c, m, pass_records, n_items);
+  return need + need / 16 <= (uint64_t)mb << 20;
+}
+// The route with its count in passes.  -> false: a pass gave up (an edge region overflowed, the bucket streaming does not serve a range,
+// the exact need exceeds the budget): nothing published, the accumulated items released, the caller's filter back.
+static bool s2_agg_from_count_passes(mhx_ctx *c, uint32_t k, uint32_t m, mhx_sdbg_result *out, const std::vector<S2CountRange> &ranges, uint32_t *first,
+                                     uint32_t *last, unsigned long long *hist, std::string *why) {
+  SeqSet &s = c->seqs;
+  hipStream_t st = c->stream;
+  const int cb = s2_agg_compact_bits(k);
+  const int cbits = cb ? cb : 16;
+  const int fsh = cbits + 3, bsh = cbits, csh = 0;
+  const uint32_t cmax = cb ? (1u << cb) - 1u : (uint32_t)MHX_MAX_MUL;
+  S2AccGuard acc_guard{c};
+  DevBuf &acc = c->work["s2c_items_acc"];
+  unsigned long long *cur = c->ws("s2c_cursor", 64).as<unsigned long long>();  // word 0: the items so far, word 1: k_edges_to_agg's error flag
+  MHX_HIP(hipMemsetAsync(cur, 0, 64, st));
+  uint64_t n_agg = 0, n_records = 0, largest = 0;
+  int n_run = 0;
+  std::string plan;
+  {
+    S2FilterGuard filter(c);
+    for (const S2CountRange &r : ranges) {
+      if (!r.n) continue;  // (a range without a record is an empty pass)
+      filter.set(r);
+      if (!count_stream_applies(c, k, m, true)) {
+        *why = "the bucket streaming does not serve the range of lv1 buckets " + std::to_string(r.lo) + ".." + std::to_string(r.hi);
+        return false;
+      }
+      CountStreamOut o;
+      o.n_items = 1;
+      if (!count_stream_groups(c, k, m, first, last, hist, &o, nullptr, true)) {
+        if (o.n_items == 0) continue;  // (no record in the kept buckets after all)
+        *why = "an edge region overflowed in pass " + std::to_string(n_run + 1);
+        return false;
+      }
+      std::vector<uint32_t> h_counts(o.grid);
+      MHX_HIP(hipMemcpyAsync(h_counts.data(), o.counts, (size_t)o.grid * 4, hipMemcpyDeviceToHost, st));
+      MHX_HIP(hipStreamSynchronize(st));
+      uint64_t n_edges = 0;
+      for (uint32_t v : h_counts) n_edges += v;
+      largest = std::max(largest, o.n_items);
+      n_records += o.n_items;
+      if (n_run++ == 0) plan = o.plan;
+      // this pass's items at their exact bound, behind those of the passes before it
+      const uint64_t items_cap = n_agg + 2 * (n_edges + o.n_items / cmax + 1);
+      if (!s2_count_in_budget(c, m, largest, items_cap)) {
+        *why = std::to_string(items_cap) + " items behind pass " + std::to_string(n_run) + " exceed s2_count_budget_mb";
+        return false;
+      }
+      uint2 *items = grow_preserving(c, acc, items_cap * 8 + 64, n_agg * 8).as<uint2>();
+      if (n_edges)
+        MHX_LAUNCH(c, "s2_edges_to_items", (double)n_edges * 16,
+                   hipLaunchKernelGGL(k_edges_to_agg, dim3(o.grid, 8), dim3(256), 0, st, reinterpret_cast<const uint4 *>(o.spare), o.cap / 2, o.counts, (int)k, fsh, bsh,
+                                      csh, cmax, items, cur, (unsigned long long)items_cap, reinterpret_cast<uint32_t *>(cur + 1)));
+      unsigned long long h_cur[2] = {0, 0};
+      MHX_HIP(hipMemcpyAsync(h_cur, cur, 16, hipMemcpyDeviceToHost, st));
+      MHX_HIP(hipStreamSynchronize(st));
+      if ((h_cur[1] & 0xFFFFFFFFull) || h_cur[0] > items_cap || h_cur[0] < n_agg) throw Error("read2sdbg_s2: more aggregated items than their bound");
+      n_agg = h_cur[0];
+    }
+  }
+  if (!n_run) {  // (the general path knows what to publish)
+    *why = "no read holds an edge";
+    return false;
+  }
+  // the bitmap the '$' items come from, the '$' items once behind the accumulated ones, one sort, one emission
+  unsigned long long *valid = nullptr;
+  if (m == 1) {
+    const uint64_t n_words = div_ceil(s.n_bases, 64);
+    valid = c->ws("s2c_valid", (n_words + 1) * 8).as<unsigned long long>();
+    if (n_words)
+      MHX_LAUNCH(c, "s2_valid_starts", (double)n_words * 8,
+                 hipLaunchKernelGGL(k_valid_starts, dim3((unsigned)div_ceil(n_words, 256)), dim3(256), 0, st, valid, n_words, s.start.as<uint64_t>(), s.n_seqs, s.fixed_len, (int)k));
+  }
+  const S2dFront f = s2d_open(c, k, m, valid, MHX_BUF_IS_SOLID, m > 1);
+  if (!s2_count_in_budget(c, m, largest, n_agg + f.bound)) {
+    *why = std::to_string(n_agg + f.bound) + " items with the '$' items exceed s2_count_budget_mb";
+    return false;
+  }
+  uint32_t *buf_a = grow_preserving(c, acc, (n_agg + f.bound) * 8 + 64, n_agg * 8).as<uint32_t>();
+  const uint64_t n_items = n_agg + s2d_emit_items(c, k, f, buf_a, n_agg, fsh, bsh, csh);
+  uint32_t *buf_b = c->ws("s2c_items_b", n_items * 8 + 64).as<uint32_t>();
+  acc_guard.keep = true;
+  uint32_t *sorted = sort_whole_key(c, buf_a, buf_b, n_items, 2, 2, s2_agg_sort_passes(k, cbits));
+  emit_sdbg(c, sorted, n_items, 2, 2, k, 2, out, cb);
+  c->last_s1_plan = "stage 2 from a count of the (k+1)-mers in " + std::to_string(n_run) + " passes over its own lv1 bucket ranges (" + std::to_string(n_records) +
+                    " records, at most " + std::to_string(largest) + " a pass): " + plan;
+  return true;
+}
+
 // -> false: the count gave up (nothing published: the per-occurrence path runs)
-static bool s2_agg_from_count(mhx_ctx *c, uint32_t k, uint32_t m, mhx_sdbg_result *out) {
+static bool s2_agg_from_count(mhx_ctx *c, uint32_t k, uint32_t m, mhx_sdbg_result *out, std::string *why) {
   SeqSet &s = c->seqs;
   hipStream_t st = c->stream;
   const uint64_t ns = s.n_seqs;
@@ -1612,6 +1803,17 @@ static bool s2_agg_from_count(mhx_ctx *c, uint32_t k, uint32_t m, mhx_sdbg_resul
   const int cbits = cb ? cb : 16;
   const int fsh = cbits + 3, bsh = cbits, csh = 0;  // chars | flag | W | count, as the aggregated items of k <= 22 with their 16 count bits
   const uint32_t cmax = cb ? (1u << cb) - 1u : (uint32_t)MHX_MAX_MUL;
+  // s2_count_pass_items > 0: the count in passes of at most that many records.  More than kS2CountMaxPasses of them: declined before
+  // anything was done
+  const uint64_t pass_cap = (uint64_t)std::max<long long>(c->opt("s2_count_pass_items", 0), 0);
+  std::vector<S2CountRange> ranges;
+  if (pass_cap) {
+    ranges = s2_count_ranges(c, k, m, pass_cap);
+    if ((int)ranges.size() > kS2CountMaxPasses) {
+      *why = std::to_string(ranges.size()) + " passes, more than " + std::to_string(kS2CountMaxPasses);
+      return false;
+    }
+  }
   // 1. the solid (k+1)-mers and their multiplicities: the workgroups' edge regions of the count (scratch first/last/histogram: nobody reads them)
   uint32_t *first = c->ws("s2c_first", (ns ? ns : 1) * 4).as<uint32_t>(), *last = c->ws("s2c_last", (ns ? ns : 1) * 4).as<uint32_t>();
   unsigned long long *hist = c->ws("s2c_hist", (MHX_MAX_MUL + 1) * 8).as<unsigned long long>();
@@ -1621,25 +1823,20 @@ static bool s2_agg_from_count(mhx_ctx *c, uint32_t k, uint32_t m, mhx_sdbg_resul
   // at the configs[4] shard against a twentieth at 60 x coverage).  Sub-rounds — a second read of every bucket instead of a third sort pass —
   // then still overflow the table and split again (count_groups 198 ms at 40 M reads), a third pass over a finer prefix does not
   // (36 ms + 27 for the pass): the plan is made with s1_stream_sub_max = 0 and 12 000 records per bucket unless the caller set those knobs.
-  struct KnobGuard {
-    mhx_ctx *c;
-    std::vector<std::string> set;
-    void put(const char *name, long long v) {
-      std::string env = std::string("MHX_") + name;
-      for (char &ch : env) ch = (char)toupper((unsigned char)ch);
-      if (c->options.count(name) || getenv(env.c_str())) return;
-      c->options[name] = v;
-      set.push_back(name);
-    }
-    ~KnobGuard() {
-      for (const std::string &n : set) c->options.erase(n);
-    }
-  } knobs{c, {}};
+  S2KnobGuard knobs{c, {}};
   if (m == 1) {
     knobs.put("s1_stream_sub_max", 0);
     knobs.put("s1_stream_max3", 12000);
   }
-  if (!count_stream_groups(c, k, m, first, last, hist, &o, nullptr, true)) return false;
+  if (pass_cap) {
+    if (s2_agg_from_count_passes(c, k, m, out, ranges, first, last, hist, why)) return true;
+    c->last_s1_plan = "stage 2 from a count in passes given up (" + *why + ")";  // (not what an earlier call ran as)
+    return false;
+  }
+  if (!count_stream_groups(c, k, m, first, last, hist, &o, nullptr, true)) {
+    *why = "an edge region overflowed, or no read holds an edge";
+    return false;
+  }
   std::vector<uint32_t> h_counts(o.grid);
   MHX_HIP(hipMemcpyAsync(h_counts.data(), o.counts, (size_t)o.grid * 4, hipMemcpyDeviceToHost, st));
   MHX_HIP(hipStreamSynchronize(st));
@@ -1718,7 +1915,13 @@ int run_s2(mhx_ctx *c, uint32_t k, uint32_t m, mhx_sdbg_result *out) {
   if (c->global_bases) throw Error("read2sdbg_s2: a global layout is set; use the mhx_dist_* entry points");
   if (!c->filter_on && !c->accumulate && c->n_parts <= 1 && s2_use_aggregated(c, k, m) && c->opt("s2_agg_in_place", 1))
     return s2_agg_in_place(c, k, out);
-  if (s2_agg_from_count_applies(c, k, m) && s2_agg_from_count(c, k, m, out)) return 0;
+  if (s2_agg_from_count_applies(c, k, m)) {
+    std::string why;
+    if (s2_agg_from_count(c, k, m, out, &why)) return 0;
+    // s2_agg_from_count = 3: a caller that left the memory plan to this route (s2_count_pass_items) hears that it did not serve — the
+    // per-occurrence items of a whole job that was never cut into lv1 bucket ranges may not fit
+    if (c->opt("s2_agg_from_count", 1) == 3) throw Error("read2sdbg_s2: stage 2 from a count given up (" + why + ")");
+  }
   const StageItems it = extract_stage(c, MHX_STAGE_S2, k, m);
   uint32_t *buf_a = c->work["items_a"].as<uint32_t>();
   uint32_t *buf_b = c->ws("items_b", it.n * (size_t)it.S * 4 + 64).as<uint32_t>();

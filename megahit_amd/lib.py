@@ -192,6 +192,7 @@ SYMBOLS = {
     "mhx_set_bucket_filter": (C.c_int, [_P, _P, C.c_uint64, C.c_uint64, C.c_int]),
     "mhx_stage_pass_bytes": (C.c_uint64, [_P, C.c_int, C.c_uint32, C.c_uint32, C.c_uint64]),
     "mhx_stage_once_bytes": (C.c_uint64, [_P, C.c_int, C.c_uint32, C.c_uint32, C.c_uint64]),
+    "mhx_s2_from_count_bytes": (C.c_uint64, [_P, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint64]),
     "mhx_alloc_stats": (None, [_P, _P, _P, _P]),
     "mhx_alloc_peak": (None, [_P, _P, C.c_int]),
     "mhx_comm_init_hosted": (_P, [_P, C.c_int, C.c_int, _P]),
@@ -453,6 +454,11 @@ class Engine:
         """device bytes the memory plan assumes for one unfiltered run of `stage` where that has a leaner route; 0: none
         (mhx_stage_once_bytes)"""
         return int(self.lib.mhx_stage_once_bytes(self.h, stage, k, m, int(n_items)))
+
+    def s2_from_count_bytes(self, k, m, est_items, pass_records=0):
+        """device bytes stage 2 from a count of the (k+1)-mers holds with its count in passes of at most pass_records records (0: everything
+        at once); 0: the route does not apply (mhx_s2_from_count_bytes)"""
+        return int(self.lib.mhx_s2_from_count_bytes(self.h, k, m, int(est_items), int(pass_records)))
 
     def fastx_to_records(self, text1, text2=None):
         """FASTA/FASTQ text -> read-library records on the GPU; returns (FastxResult, uint32 records or None)."""
