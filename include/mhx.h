@@ -307,7 +307,9 @@ enum mhx_buffer {
   /* `local`, first half (mhx_local_map / mhx_local_collect, below) */
   MHX_BUF_LOCAL_REC = 46,     /* mhx_local_record[n_reads] */
   MHX_BUF_LOCAL_ITEMS = 47,   /* uint64[n_items]: the collector's encoded reads, grouped by contig, then end, ascending inside a group */
-  MHX_BUF_LOCAL_OFFSETS = 48  /* uint64[2 * n_contigs + 1]: the items of (contig c, end e) are [offsets[2c + e], offsets[2c + e + 1]) */
+  MHX_BUF_LOCAL_OFFSETS = 48, /* uint64[2 * n_contigs + 1]: the items of (contig c, end e) are [offsets[2c + e], offsets[2c + e + 1]) */
+  /* mhx_sdbg_mul_histogram (below) */
+  MHX_BUF_SDBG_MUL_HIST = 49  /* uint64[65536]: bin v = valid edges (bit clear in MHX_BUF_SDBG_INVALID) with MHX_BUF_SDBG_MUL == v */
 };
 /* bytes currently held in a result buffer (0 if absent) */
 uint64_t mhx_buffer_bytes(const mhx_ctx *, int which);
@@ -401,6 +403,29 @@ int mhx_sdbg_build_index(mhx_ctx *, uint32_t k, mhx_sdbg_index_info *out);
  * mhx_sdbg_build_index left in HBM.  Updates MHX_BUF_SDBG_INVALID in place; *n_removed = tips removed (the number the
  * reference logs).  `assemble` calls it with max_tip_len = 2k by default (main_assemble.cpp:143-156). */
 int mhx_sdbg_remove_tips(mhx_ctx *, const mhx_sdbg_index_info *info, int max_tip_len, uint64_t *n_removed);
+/* The minimum depth `assemble` infers when none is given: sdbg_pruning::InferMinDepth (assembly/sdbg_pruning.cpp:36-59).
+ *   mhx_sdbg_mul_histogram  the histogram of EdgeMultiplicity over the edges that are valid NOW into MHX_BUF_SDBG_MUL_HIST
+ *       (uint64[65536]); *n_valid (may be NULL) = the sum of the bins.  It reads MHX_BUF_SDBG_MUL and the current bits of
+ *       MHX_BUF_SDBG_INVALID, so it is valid whenever the index is — straight after mhx_sdbg_build_index (what the reference
+ *       looks at: the graph as loaded), after mhx_sdbg_remove_tips, after cleaning calls; without an index of info->n_items
+ *       items in the handle it is an error.  One kernel (csrc/sdbg_index.hip k_sdbg_mul_hist): values below 8192 are counted
+ *       in LDS per workgroup, flushed after at most 2^30 items (knob sdbg_hist_flush_tiles: tiles of 16384 items between two
+ *       flushes, 1..65536, for the tests), the others with one global atomic each.
+ *   mhx_infer_min_depth  the fixed point of InferMinDepth on such a histogram, over the behaviour of Histgram<uint16_t>
+ *       (utils/histgram.h).  Pure host code without a device call: works on a machine without a GPU.  Only non-zero bins exist
+ *       and bin 0 is a value like any other.  cov = FirstLocalMinimum (the running minimum moves on `<=`, four larger bins in
+ *       a row end the search, 0 when the minimum found is the largest value present); then at most 100 rounds of: TrimLow
+ *       ((uint16_t)roundf((float)cov): cumulative), median = the first value whose running sum exceeds (size_t)(size * 0.5)
+ *       (0: none), cov1 = sqrt(median); |cov - cov1| < 1e-2 returns cov (the OLD value) with *converged = 1.  After 100
+ *       rounds *converged = 0 and *min_depth = 1 (the reference warns "Cannot detect min depth: unconverged").  converged may
+ *       be NULL.  An all-zero histogram is the error "no valid edge" (the reference's behaviour is undefined there).
+ *   mhx_sdbg_infer_min_depth  both: the histogram, its 512 KB fetched, the host function.
+ * `mhx_core assemble` calls it after mhx_sdbg_build_index and before mhx_sdbg_remove_tips when the prune level is >= 1 and no
+ * --min_depth > 0 was given, logs "min depth set to %.3f" and uses the full double.  Such a command line takes the GPU route
+ * only at the second level of the route's opt-in variable (MHX_ASSEMBLE_PRUNE=2 / MHX_ASSEMBLE_BUBBLE=2, below). */
+int mhx_sdbg_mul_histogram(mhx_ctx *, const mhx_sdbg_index_info *info, uint64_t *n_valid);
+int mhx_infer_min_depth(const uint64_t hist[65536], double *min_depth, int *converged);
+int mhx_sdbg_infer_min_depth(mhx_ctx *, const mhx_sdbg_index_info *info, double *min_depth, int *converged);
 /* The unitig graph: UnitigGraph::UnitigGraph (assembly/unitig_graph.cpp:13-138) on the buffers mhx_sdbg_build_index
  * (+ mhx_sdbg_remove_tips) left in HBM, and the contig text OutputContigs writes (contig_output.cpp:62-119 over
  * VertexToDNAString, unitig_graph.cpp:357-394).  Vertices in the order the reference builds them on one thread (chains
@@ -454,8 +479,9 @@ int mhx_sdbg_unitigs(mhx_ctx *, const mhx_sdbg_index_info *info, mhx_unitig_resu
  *       MHX_BUF_UNITIG_OFFSET for the vertex table as it is now.  total_depth is no longer a sum of multiplicities once a
  *       vertex was trimmed (lround(average * new length), unitig_graph.cpp:191-193).
  * The CLI (`mhx_core assemble`) runs the cleaning rounds only when MHX_ASSEMBLE_CLEAN=1 or MHX_ASSEMBLE_PRUNE=1 is in its
- * environment and only at --bubble_level 0; --prune_level 1 and 2 (with an explicit --min_depth > 0) run here only with
- * MHX_ASSEMBLE_PRUNE=1, which implies the cleaning rounds.  Otherwise such command lines are forwarded to MHX_REF_CORE.
+ * environment and only at --bubble_level 0; --prune_level 1 and 2 run here only with MHX_ASSEMBLE_PRUNE=1 (--min_depth > 0
+ * given) or MHX_ASSEMBLE_PRUNE=2 (given, or inferred: mhx_sdbg_infer_min_depth above), which imply the cleaning rounds.
+ * Otherwise such command lines are forwarded to MHX_REF_CORE.
  * MHX_ASSEMBLE_BUBBLE=1 (further below) implies both and adds the bubble levels 1 and 2 and prune level 3.
  * MHX_ASSEMBLE_REF=1 wins. */
 int mhx_unitig_disconnect_weak_links(mhx_ctx *, const mhx_sdbg_index_info *info, double ratio, uint64_t *n_flagged);
@@ -466,8 +492,8 @@ int mhx_unitig_iterate_local_low_depth(mhx_ctx *, const mhx_sdbg_index_info *inf
                                        double local_ratio, int mark_changed, uint64_t *n_removed);
 int mhx_unitig_finish(mhx_ctx *, const mhx_sdbg_index_info *info, mhx_unitig_result *out);
 /* Bubble popping and prune level 3 on the same unitig graph (same validity rules and stale-state errors as the calls above):
- * with them the cleaning calls cover `assemble --bubble_level 0..2 --prune_level 0..3` (main_assemble.cpp:182-301) but for
- * InferMinDepth.  The result is the reference's at any -t: a search reads only what the pass never writes and sets only
+ * with them the cleaning calls cover `assemble --bubble_level 0..2 --prune_level 0..3` (main_assemble.cpp:182-301; its
+ * InferMinDepth is mhx_sdbg_infer_min_depth above).  The result is the reference's at any -t: a search reads only what the pass never writes and sets only
  * to-delete flags, so the deleted set is a union and the count the number of distinct vertices in it.
  *   mhx_unitig_pop_bubbles  BaseBubbleRemover::PopBubbles (assembly/bubble_remover.cpp:58-152), one thread per (vertex, strand)
  *       node: a node with d >= 2 out-neighbours ("middles"), none longer than max_len, each with in-degree 1 and one
@@ -499,7 +525,7 @@ int mhx_unitig_finish(mhx_ctx *, const mhx_sdbg_index_info *info, mhx_unitig_res
  *       boundary conditions, in IEEE double.  Needs no graph.  Strings longer than MHX_SIM_MAX_LEN or a max_indel above
  *       MHX_SIM_MAX_INDEL are an error (two band rows of 4-byte cells are kept in 32 KB of LDS).
  * The CLI runs these only with MHX_ASSEMBLE_BUBBLE=1 in its environment (which implies MHX_ASSEMBLE_PRUNE and _CLEAN):
- * --bubble_level 0..2, --prune_level 0..3 (levels 1..3 with an explicit --min_depth > 0), --careful_bubble or not, and
+ * --bubble_level 0..2, --prune_level 0..3 (levels 1..3 with --min_depth > 0 given, or with MHX_ASSEMBLE_BUBBLE=2 inferred), --careful_bubble or not, and
  * --merge_len / --merge_similar within the cap at k = MHX_MAX_K.  Everything else is forwarded as before. */
 #define MHX_SIM_MAX_LEN 16384
 #define MHX_SIM_MAX_INDEL 2047

@@ -919,6 +919,28 @@ int mhx_sdbg_remove_tips(mhx_ctx *c, const mhx_sdbg_index_info *info, int max_ti
     mhx::sdbg_remove_tips(c, info, max_tip_len, n_removed);
   })
 }
+int mhx_sdbg_mul_histogram(mhx_ctx *c, const mhx_sdbg_index_info *info, uint64_t *n_valid) {
+  MHX_TRY({
+    MHX_HIP(hipSetDevice(c->device));
+    if (!info) throw mhx::Error("sdbg_mul_histogram: no index info");
+    mhx::sdbg_mul_histogram(c, info, n_valid);
+  })
+}
+int mhx_infer_min_depth(const uint64_t hist[65536], double *min_depth, int *converged) {
+  MHX_TRY({
+    if (!hist || !min_depth) throw mhx::Error("infer_min_depth: bad arguments");
+    mhx::infer_min_depth(hist, min_depth, converged);
+  })
+}
+int mhx_sdbg_infer_min_depth(mhx_ctx *c, const mhx_sdbg_index_info *info, double *min_depth, int *converged) {
+  MHX_TRY({
+    MHX_HIP(hipSetDevice(c->device));
+    if (!info || !min_depth) throw mhx::Error("sdbg_infer_min_depth: bad arguments");
+    std::vector<uint64_t> h;
+    mhx::sdbg_mul_histogram(c, info, nullptr, &h);
+    mhx::infer_min_depth(h.data(), min_depth, converged);
+  })
+}
 int mhx_sdbg_unitigs(mhx_ctx *c, const mhx_sdbg_index_info *info, mhx_unitig_result *out) {
   MHX_TRY({
     MHX_HIP(hipSetDevice(c->device));

@@ -1346,7 +1346,7 @@ int main_iterate(int argc, char **argv) {
 // contig output: --bubble_level 0 --prune_level 0 --cleaning_rounds 0 — and, with MHX_ASSEMBLE_CLEAN=1 in the environment,
 // with --cleaning_rounds N >= 1 as well: the rounds of RemoveTips and DisconnectWeakLinks on the unitig graph
 // (main_assemble.cpp:182-249 at bubble level 0 and prune level 0) — and, with MHX_ASSEMBLE_PRUNE=1, at --prune_level 1 or 2
-// with an explicit --min_depth > 0 (InferMinDepth is not built): RemoveLocalLowDepth inside the rounds (level 2), the
+// (the --min_depth given and > 0, or — with the variable at 2 — inferred on the device: mhx_sdbg_infer_min_depth): RemoveLocalLowDepth inside the rounds (level 2), the
 // IterateLocalLowDepth after them and the .addi.fa of the changed contigs (main_assemble.cpp:238-301) — and, with
 // MHX_ASSEMBLE_BUBBLE=1 (which implies the other two), at --bubble_level 0..2 and --prune_level 0..3: the naive and complex
 // PopBubbles of the rounds, RemoveLowDepth and its pops at prune level 3, the final complex pop after the iteration and the
@@ -1376,6 +1376,9 @@ void add_assemble_options(Options &o) {  // main_assemble.cpp:66-101
 // ComplexBubbleRemover::PopBubbles' max_len (bubble_remover.cpp:155-157): unsigned product, double quotient
 uint32_t complex_max_len(int merge_len, uint32_t k, double sim) { return (uint32_t)lround((uint32_t)merge_len * k / sim); }
 // decided from argv alone, before anything touches HIP (forwarding is an execv)
+// value of an opt-in variable: 0 off, 1 the route, 2 the route and, at a prune level >= 1 without a --min_depth > 0, InferMinDepth on
+// the device (at 1 such a command line is forwarded, as it always was)
+int opt_in_level(const char *name) { return getenv(name) ? atoi(getenv(name)) : 0; }
 bool assemble_on_gpu(int argc, char **argv) {
   if (getenv("MHX_ASSEMBLE_REF") && atoi(getenv("MHX_ASSEMBLE_REF")) != 0) return false;
   Options o;
@@ -1391,7 +1394,7 @@ bool assemble_on_gpu(int argc, char **argv) {
     const int bubble_level = atoi(o.get("bubble_level").c_str()), merge_len = atoi(o.get("merge_len").c_str());
     const double sim = atof(o.get("merge_similar").c_str());
     if (bubble_level < 0 || bubble_level > 2 || prune_level < 0 || prune_level > 3 || rounds < 0) return false;
-    if (prune_level >= 1 && !(atof(o.get("min_depth").c_str()) > 0)) return false;  // InferMinDepth is the reference's
+    if (prune_level >= 1 && !(atof(o.get("min_depth").c_str()) > 0) && opt_in_level("MHX_ASSEMBLE_BUBBLE") < 2) return false;  // no depth: inferred only at 2
     if (bubble_level >= 2) {
       // the similarity kernel's cap, at the largest k there is: k is not known before the graph is read
       if (merge_len < 0 || !(sim > 0 && sim <= 1)) return false;
@@ -1402,8 +1405,8 @@ bool assemble_on_gpu(int argc, char **argv) {
   }
   if (atoi(o.get("bubble_level").c_str()) != 0) return false;
   const bool prune = getenv("MHX_ASSEMBLE_PRUNE") && atoi(getenv("MHX_ASSEMBLE_PRUNE")) != 0;  // low-depth pruning on the GPU: opt-in
-  if (prune_level != 0)  // levels 1 and 2 with a given minimum depth; the variable implies the cleaning rounds
-    return prune && (prune_level == 1 || prune_level == 2) && atof(o.get("min_depth").c_str()) > 0 && rounds >= 0;
+  if (prune_level != 0)  // levels 1 and 2 with a given minimum depth (at 2: or an inferred one); the variable implies the cleaning rounds
+    return prune && (prune_level == 1 || prune_level == 2) && (atof(o.get("min_depth").c_str()) > 0 || opt_in_level("MHX_ASSEMBLE_PRUNE") >= 2) && rounds >= 0;
   if (rounds <= 0) return rounds == 0;
   return prune || (getenv("MHX_ASSEMBLE_CLEAN") && atoi(getenv("MHX_ASSEMBLE_CLEAN")) != 0);  // the cleaning rounds on the GPU: opt-in
 }
@@ -1454,6 +1457,15 @@ int main_assemble(int argc, char **argv) {
   info("Number of CPU threads: %d", n_threads);
   int max_tip_len = atoi(o.get("max_tip_len").c_str());
   if (max_tip_len == -1) max_tip_len = (int)f.k * 2;
+  // InferMinDepth on the graph as loaded (main_assemble.cpp:146-150; assemble_on_gpu lets such a command line in only at opt-in
+  // level 2).  Prune level 0 never reads the value: nothing is inferred or logged there
+  double min_depth = atof(o.get("min_depth").c_str());
+  if (atoi(o.get("prune_level").c_str()) >= 1 && !(min_depth > 0)) {
+    int converged = 1;
+    CK(mhx_sdbg_infer_min_depth(c, &ix, &min_depth, &converged));
+    if (!converged) fprintf(stderr, "WARN  Cannot detect min depth: unconverged\n");
+    info("min depth set to %.3f", min_depth);
+  }
   if (max_tip_len > 0) {
     uint64_t n_tips = 0;
     CK(mhx_sdbg_remove_tips(c, &ix, max_tip_len, &n_tips));
@@ -1491,7 +1503,7 @@ int main_assemble(int argc, char **argv) {
   const int cleaning_rounds = atoi(o.get("cleaning_rounds").c_str()), prune_level = atoi(o.get("prune_level").c_str());
   const int bubble_level = atoi(o.get("bubble_level").c_str()), merge_len = atoi(o.get("merge_len").c_str());
   const bool is_final_round = o.get("is_final_round") == "1", careful_bubble = o.get("careful_bubble") == "1";
-  const double min_depth = atof(o.get("min_depth").c_str()), low_local_ratio = atof(o.get("low_local_ratio").c_str());
+  const double low_local_ratio = atof(o.get("low_local_ratio").c_str());
   const double merge_similar = atof(o.get("merge_similar").c_str());
   const uint32_t local_width = 1000;  // AssemblerOptions::local_width: no command-line option sets it
   // the --careful_bubble records of every pass, in call order: ContigWriter records with id 0, flag 0 and the average depth

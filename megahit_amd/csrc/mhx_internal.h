@@ -324,6 +324,8 @@ void mercy_adopt_routed(mhx_ctx *c, const long long *recv, uint64_t n);
 void s1_apply_marks(mhx_ctx *c, const unsigned long long *recv, uint64_t n);
 int sdbg_build_index(mhx_ctx *c, uint32_t k, mhx_sdbg_index_info *out);
 int sdbg_remove_tips(mhx_ctx *c, const mhx_sdbg_index_info *info, int max_tip_len, uint64_t *n_removed);
+int sdbg_mul_histogram(mhx_ctx *c, const mhx_sdbg_index_info *info, uint64_t *n_valid, std::vector<uint64_t> *host = nullptr);
+int infer_min_depth(const uint64_t *hist, double *min_depth, int *converged);
 int sdbg_unitigs(mhx_ctx *c, const mhx_sdbg_index_info *info, mhx_unitig_result *out);
 int sdbg_unitig_text(mhx_ctx *c, const mhx_sdbg_index_info *info, uint64_t nv, uint64_t n_loop, mhx_unitig_result *out);
 int unitig_disconnect_weak_links(mhx_ctx *c, const mhx_sdbg_index_info *info, double ratio, uint64_t *n_flagged);

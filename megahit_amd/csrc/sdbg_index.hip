@@ -16,6 +16,7 @@
 //   prefix table, f, rank_f                                                             (sdbg.h:38-55)
 // Bit-exact against the reference's own loader (oracle/ref_sdbg_dump.cpp, tests/test_gpu_sdbg_index.py).
 #include <algorithm>
+#include <cmath>
 
 #include "dev_prims.h"
 #include "mhx_internal.h"
@@ -338,6 +339,156 @@ int sdbg_build_index(mhx_ctx *c, uint32_t k, mhx_sdbg_index_info *out) {
     out->rank_f[0] = 0;
     for (int i = 1; i < 6; ++i) out->rank_f[i] = (long long)h_rank[i - 1];
   }
+  return 0;
+}
+
+// Histogram of EdgeMultiplicity over the edges that are valid now (what sdbg_pruning::InferMinDepth collects,
+// assembly/sdbg_pruning.cpp:36-45): bin v of hist[65536] += items i < n with bit i of `invalid` clear and mul[i] == v.
+// A workgroup (4 wavefronts) takes tiles of kHistTile items, tile t to workgroup t % gridDim.x; a wavefront's quarter is 64
+// validity words, one per lane in one coalesced load, and 8 rounds of one 16-byte load of mul per lane (8 items; the
+// lanes' loads are consecutive), the lane's validity byte taken from the lane that holds its word.  Values below
+// kHistLds are counted in 32-bit LDS bins of the workgroup, the others (rare: real graphs put most edges on a handful of
+// low values) go to the 64-bit global bins directly.  The LDS bins are flushed — one global atomic per non-zero bin —
+// after every flush_tiles tiles and at the end: flush_tiles * kHistTile < 2^32, so no bin can wrap at any n.
+constexpr int kHistLds = 8192;                  // values with an LDS bin: 32 KB per workgroup
+constexpr uint64_t kHistTile = 4 * 64 * 64;     // items per workgroup tile
+constexpr uint32_t kHistMaxFlushTiles = 65536;  // * kHistTile = 2^30 items between flushes at most
+__global__ __launch_bounds__(256) void k_sdbg_mul_hist(const uint16_t *__restrict__ mul, const unsigned long long *__restrict__ invalid, uint64_t n,
+                                                       uint32_t flush_tiles, unsigned long long *__restrict__ hist) {
+  __shared__ uint32_t bins[kHistLds];
+  const int lane = lane_id(), wave = threadIdx.x / kWave;
+  const uint64_t n_tiles = (n + kHistTile - 1) / kHistTile, n_words = (n + 63) / 64;
+  for (int b = threadIdx.x; b < kHistLds; b += 256) bins[b] = 0;
+  __syncthreads();
+  auto flush = [&]() {  // (every thread of the workgroup comes here together)
+    __syncthreads();
+    for (int b = threadIdx.x; b < kHistLds; b += 256) {
+      const uint32_t v = bins[b];
+      if (v) {
+        atomicAdd(&hist[b], (unsigned long long)v);
+        bins[b] = 0;
+      }
+    }
+    __syncthreads();
+  };
+  auto count = [&](unsigned v) {
+    if (v < (unsigned)kHistLds) atomicAdd(&bins[v], 1u);
+    else atomicAdd(&hist[v], 1ull);
+  };
+  uint32_t since_flush = 0;
+  for (uint64_t t = blockIdx.x; t < n_tiles; t += gridDim.x) {
+    const uint64_t w0 = t * (kHistTile / 64) + (uint64_t)wave * 64;  // the wavefront's first validity word
+    const uint64_t w = w0 + (uint64_t)lane;
+    unsigned long long inv = w < n_words ? invalid[w] : ~0ull;
+    if (w * 64 + 64 > n) inv |= w * 64 >= n ? ~0ull : ~0ull << (n & 63);  // the padding of the last word counts as invalid, whatever it holds
+    unsigned bad8[8];  // my validity byte of every round, fetched while all lanes are still together
+#pragma unroll
+    for (int r = 0; r < 8; ++r) {
+      const int src = r * 8 + (lane >> 3);  // the lane that holds the word of my 8 items of round r
+      const unsigned lo = (unsigned)__shfl((int)(unsigned)inv, src, kWave), hi = (unsigned)__shfl((int)(unsigned)(inv >> 32), src, kWave);
+      bad8[r] = (((lane & 4) ? hi : lo) >> (8 * (lane & 3))) & 255u;
+    }
+#pragma unroll
+    for (int r = 0; r < 8; ++r) {
+      const unsigned bad = bad8[r];
+      const uint64_t i0 = (w0 + (uint64_t)(r * 8)) * 64 + 8 * (uint64_t)lane;
+      if (bad == 255u || i0 >= n) continue;
+      if (i0 + 8 <= n) {
+        const uint4 q = *reinterpret_cast<const uint4 *>(mul + i0);
+        const unsigned x[4] = {q.x, q.y, q.z, q.w};
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          if (!((bad >> (2 * j)) & 1u)) count(x[j] & 65535u);
+          if (!((bad >> (2 * j + 1)) & 1u)) count(x[j] >> 16);
+        }
+      } else {  // the last items of the array: a 16-byte load would reach behind it
+        for (int j = 0; j < 8 && i0 + j < n; ++j)
+          if (!((bad >> j) & 1u)) count(mul[i0 + j]);
+      }
+    }
+    if (++since_flush == flush_tiles) {
+      flush();
+      since_flush = 0;
+    }
+  }
+  if (since_flush) flush();
+}
+
+int sdbg_mul_histogram(mhx_ctx *c, const mhx_sdbg_index_info *info, uint64_t *n_valid, std::vector<uint64_t> *host) {
+  hipStream_t st = c->stream;
+  const uint64_t n = info->n_items, nw64 = div_ceil(n, 64);
+  auto need = [&](int which, uint64_t bytes) -> DevBuf & {
+    auto it = c->results.find(which);
+    if (it == c->results.end() || !it->second.p || it->second.used < bytes) throw Error("sdbg_mul_histogram: run mhx_sdbg_build_index first");
+    return it->second;
+  };
+  const uint16_t *mul = need(MHX_BUF_SDBG_MUL, n * 2).as<uint16_t>();
+  const unsigned long long *inv = need(MHX_BUF_SDBG_INVALID, nw64 * 8).as<unsigned long long>();
+  unsigned long long *hist = c->result(MHX_BUF_SDBG_MUL_HIST, (size_t)(MHX_MAX_MUL + 1) * 8).as<unsigned long long>();
+  MHX_HIP(hipMemsetAsync(hist, 0, (size_t)(MHX_MAX_MUL + 1) * 8, st));
+  if (n) {
+    // sized from the device, not from n: 4 workgroups per compute unit (32 KB of LDS each), fewer when there are fewer tiles
+    const uint64_t n_tiles = div_ceil(n, kHistTile);
+    const unsigned grid = (unsigned)std::min<uint64_t>(n_tiles, 4ull * (uint64_t)(c->n_cus > 0 ? c->n_cus : 256));
+    const uint32_t flush_tiles = (uint32_t)std::min<long long>(kHistMaxFlushTiles, std::max<long long>(1, c->opt("sdbg_hist_flush_tiles", kHistMaxFlushTiles)));
+    MHX_LAUNCH(c, "sdbg_mul_hist", (double)n * 2 + (double)nw64 * 8,
+               hipLaunchKernelGGL(k_sdbg_mul_hist, dim3(grid), dim3(256), 0, st, mul, inv, n, flush_tiles, hist));
+  }
+  if (n_valid || host) {  // the one copy of the 512 KB to the host: for the sum, and for a caller that wants the bins
+    std::vector<uint64_t> own;
+    std::vector<uint64_t> &h = host ? *host : own;
+    h.resize(MHX_MAX_MUL + 1);
+    MHX_HIP(hipMemcpyAsync(h.data(), hist, h.size() * 8, hipMemcpyDeviceToHost, st));
+    MHX_HIP(hipStreamSynchronize(st));
+    if (n_valid) {
+      uint64_t sum = 0;
+      for (uint64_t v : h) sum += v;
+      *n_valid = sum;
+    }
+  }
+  return 0;
+}
+
+// sdbg_pruning::InferMinDepth (assembly/sdbg_pruning.cpp:46-58) on a histogram, over the behaviour of Histgram<uint16_t>
+// (utils/histgram.h): host code, no device call.  Only non-zero bins exist (a std::map's entries); `lo` is the first value
+// TrimLow has not removed, `size` the count of what is left.
+int infer_min_depth(const uint64_t *hist, double *min_depth, int *converged) {
+  constexpr int kBins = MHX_MAX_MUL + 1, kSmoothing = 4, kMaxRounds = 100;
+  uint64_t left = 0;  // edges not trimmed yet
+  int first = -1, largest = -1;
+  for (int v = 0; v < kBins; ++v)
+    if (hist[v]) {
+      left += hist[v];
+      if (first < 0) first = v;
+      largest = v;
+    }
+  if (first < 0) throw Error("infer_min_depth: no valid edge (the histogram is empty)");
+  // FirstLocalMinimum: the lowest bin so far moves on `<=`; kSmoothing larger bins in a row end the search
+  int lowest = first, rising = 0;
+  for (int v = first; v <= largest && rising < kSmoothing; ++v) {
+    if (!hist[v]) continue;
+    if (hist[v] <= hist[lowest]) lowest = v, rising = 0;
+    else ++rising;
+  }
+  double depth = lowest == largest ? 0.0 : (double)lowest;
+  int lo = 0;  // first value TrimLow has left
+  bool settled = false;
+  for (int round = 0; round < kMaxRounds && !settled; ++round) {
+    for (const int cut = (uint16_t)roundf((float)depth); lo < cut; ++lo) left -= hist[lo];  // cumulative, never restored
+    const uint64_t half = (uint64_t)((double)left * 0.5);
+    uint64_t seen = 0;
+    int median = 0;  // the first value whose running sum exceeds half; 0: none
+    for (int v = lo; v <= largest; ++v)
+      if ((seen += hist[v]) > half) {
+        median = v;
+        break;
+      }
+    const double next = sqrt((double)median);
+    settled = fabs(depth - next) < 1e-2;  // ... and the OLD value is the answer
+    if (!settled) depth = next;
+  }
+  if (converged) *converged = settled ? 1 : 0;
+  *min_depth = settled ? depth : 1.0;
   return 0;
 }
 

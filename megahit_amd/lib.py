@@ -40,6 +40,7 @@ BUF_UNITIG_BUBBLE_SEQ = 45
 BUF_LOCAL_REC = 46
 BUF_LOCAL_ITEMS = 47
 BUF_LOCAL_OFFSETS = 48
+BUF_SDBG_MUL_HIST = 49
 SIM_MAX_LEN, SIM_MAX_INDEL = 16384, 2047
 # one mhx_local_record (include/mhx.h)
 LOCAL_RECORD_DTYPE = np.dtype([("contig_id", np.uint32), ("contig_from", np.int32), ("contig_to", np.int32), ("query_from", np.int32),
@@ -159,6 +160,9 @@ SYMBOLS = {
     "mhx_sdbg_build_index": (C.c_int, [_P, C.c_uint32, C.POINTER(SdbgIndexInfo)]),
     "mhx_sdbg_load_bytes": (C.c_int, [_P, _P, C.c_uint64, _P, _P, _P, _P]),
     "mhx_sdbg_remove_tips": (C.c_int, [_P, C.POINTER(SdbgIndexInfo), C.c_int, _P]),
+    "mhx_sdbg_mul_histogram": (C.c_int, [_P, C.POINTER(SdbgIndexInfo), C.POINTER(C.c_uint64)]),
+    "mhx_infer_min_depth": (C.c_int, [_P, C.POINTER(C.c_double), C.POINTER(C.c_int)]),
+    "mhx_sdbg_infer_min_depth": (C.c_int, [_P, C.POINTER(SdbgIndexInfo), C.POINTER(C.c_double), C.POINTER(C.c_int)]),
     "mhx_sdbg_unitigs": (C.c_int, [_P, C.POINTER(SdbgIndexInfo), C.POINTER(UnitigResult)]),
     "mhx_unitig_disconnect_weak_links": (C.c_int, [_P, C.POINTER(SdbgIndexInfo), C.c_double, C.POINTER(C.c_uint64)]),
     "mhx_unitig_remove_tips": (C.c_int, [_P, C.POINTER(SdbgIndexInfo), C.c_uint32, C.POINTER(C.c_uint64)]),
@@ -240,6 +244,18 @@ def local_insert_size(rec, read_len, lib_begin, lib_end, max_read_len, paired):
                                C.byref(sd), C.byref(rng)) != 0:
         raise MhxError(L.mhx_last_error().decode())
     return mean.value, sd.value, int(rng.value)
+
+
+def infer_min_depth(hist):
+    """The fixed point of sdbg_pruning::InferMinDepth on a multiplicity histogram (include/mhx.h: mhx_infer_min_depth); host code
+    only, needs no GPU.  hist: uint64[65536].  -> (min_depth, converged); an all-zero histogram raises ("no valid edge")."""
+    L = load()
+    hist = np.ascontiguousarray(hist, dtype=np.uint64)
+    assert hist.shape == (MAX_MUL + 1,)
+    d, conv = C.c_double(0), C.c_int(0)
+    if L.mhx_infer_min_depth(_ptr(hist), C.byref(d), C.byref(conv)) != 0:
+        raise MhxError(L.mhx_last_error().decode())
+    return d.value, bool(conv.value)
 
 
 class Engine:
@@ -506,6 +522,20 @@ class Engine:
         n = C.c_uint64(0)
         self._chk(self.lib.mhx_sdbg_remove_tips(self.h, C.byref(info), int(max_tip_len), C.byref(n)))
         return int(n.value)
+
+    def sdbg_mul_histogram(self, info):
+        """Histogram of EdgeMultiplicity over the edges that are valid now (include/mhx.h: mhx_sdbg_mul_histogram);
+        returns (hist uint64[65536] fetched from BUF_SDBG_MUL_HIST, n_valid)."""
+        self._chk(self.lib.mhx_sdbg_mul_histogram(self.h, C.byref(info), None))  # (no n_valid: the bins come over once, in the fetch)
+        hist = self.fetch(BUF_SDBG_MUL_HIST, np.uint64)
+        return hist, int(hist.sum())
+
+    def sdbg_infer_min_depth(self, info):
+        """sdbg_pruning::InferMinDepth on the device-resident graph as it is now (include/mhx.h: mhx_sdbg_infer_min_depth);
+        returns (min_depth, converged)."""
+        d, conv = C.c_double(0), C.c_int(0)
+        self._chk(self.lib.mhx_sdbg_infer_min_depth(self.h, C.byref(info), C.byref(d), C.byref(conv)))
+        return d.value, bool(conv.value)
 
     def sdbg_unitigs(self, info):
         """The unitig graph of the device-resident graph (include/mhx.h: mhx_sdbg_unitigs); returns a UnitigResult.  The

@@ -11,9 +11,11 @@ and MHX_ASSEMBLE_BUBBLE=1 (what an unmodified `megahit` asks for below k_max; th
 the per-round bubble counts, the mid-run finishes), the digests of .contigs.fa, .addi.fa and .bubble_seq.fa.  --diploid F: a second
 haplotype (an SNP, an SNP pair, a 1-3 base deletion, a 1-3 base insertion in turn, one every 1000 bases of the genome:
 make_unitig_bubble_golden.second_haplotype) sampled by F x as many extra reads, so that the graph holds bubbles of both kinds.
+--infer (with --prune or --bubble): without `--min_depth` and the route's variable at 2, so that the route infers it on the device; "infer_ms" = the kernel groups
+sdbg_mul_hist and sdbg_pack of the profiled run.
 Too slow for the suite.  One JSON line on stdout.
 
-    python tools/unitig_bench.py [--clean | --prune | --bubble] [--diploid 0.5] [--reads 10000000] [--ref oracle/_ref/ref_megahit_core] [--ref-threads 1,16] [--workdir DIR]"""
+    python tools/unitig_bench.py [--clean | --prune | --bubble] [--infer] [--diploid 0.5] [--reads 10000000] [--ref oracle/_ref/ref_megahit_core] [--ref-threads 1,16] [--workdir DIR]"""
 import argparse
 import hashlib
 import json
@@ -52,6 +54,7 @@ def main():
     ap.add_argument("--clean", action="store_true", help="--cleaning_rounds 5 on the GPU route (MHX_ASSEMBLE_CLEAN=1)")
     ap.add_argument("--prune", action="store_true", help="--prune_level 2 --min_depth 2 --cleaning_rounds 5 on the GPU route (MHX_ASSEMBLE_PRUNE=1)")
     ap.add_argument("--bubble", action="store_true", help="bubble level 2, prune level 2, careful, on the GPU route (MHX_ASSEMBLE_BUBBLE=1)")
+    ap.add_argument("--infer", action="store_true", help="with --prune / --bubble: no --min_depth, so the route infers it (kernel group sdbg_mul_hist)")
     ap.add_argument("--diploid", type=float, default=0.0, help="add this fraction of the reads again from a second haplotype (a variant every 1000 bases)")
     a = ap.parse_args()
     qual = QUAL[:-1] + ["5"] if a.clean else QUAL
@@ -60,6 +63,9 @@ def main():
     if a.bubble:
         qual = ["--bubble_level", "2", "--prune_level", "2", "--min_depth", "2", "--merge_len", "20", "--merge_similar", "0.95", "--cleaning_rounds", "5",
                 "--careful_bubble"]
+    if a.infer:
+        at = qual.index("--min_depth")
+        qual = qual[:at] + qual[at + 2:]
     d = a.workdir or tempfile.mkdtemp(prefix="mhx_unitig")
     os.makedirs(d, exist_ok=True)
     res = {"reads": a.reads, "k": a.k, "options": " ".join(qual)}
@@ -75,19 +81,22 @@ def main():
     g = os.path.join(d, "g")
     subprocess.run([MHX_CORE, "read2sdbg", "-k", str(a.k), "-m", "2", "--host_mem", "2e10", "--num_cpu_threads", "16", "--read_lib_file",
                     os.path.join(d, "reads"), "--output_prefix", g], check=True, stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL)
-    env = dict(os.environ, MHX_PROFILE="1", MHX_SERVER="off", MHX_ASSEMBLE_CLEAN="1" if a.clean else "0", MHX_ASSEMBLE_PRUNE="1" if a.prune else "0",
-               MHX_ASSEMBLE_BUBBLE="1" if a.bubble else "0")
+    level = "2" if a.infer else "1"  # 2: a command line without a depth is served
+    env = dict(os.environ, MHX_PROFILE="1", MHX_SERVER="off", MHX_ASSEMBLE_CLEAN="1" if a.clean else "0", MHX_ASSEMBLE_PRUNE=level if a.prune else "0",
+               MHX_ASSEMBLE_BUBBLE=level if a.bubble else "0")
     t0 = time.time()
     p = subprocess.run([MHX_CORE, "assemble", "-s", g, "-o", os.path.join(d, "mine"), "-t", "16"] + qual, env=env, stdout=subprocess.DEVNULL,
                        stderr=subprocess.PIPE, text=True, check=True)
     res["mhx_wall_s"] = round(time.time() - t0, 3)
     res["kernels_ms"] = {m.group(1): float(m.group(2)) for m in re.finditer(r"profile (\S+)\s+\d+ launches\s+([\d.]+) ms", p.stderr)}
-    res["log"] = [l for l in p.stderr.splitlines() if re.search(r"Edges|Tips|unitig graph size|palindrome|Max:|output|disconnected|pruning|low depth|ubble", l)]
+    res["log"] = [l for l in p.stderr.splitlines() if re.search(r"Edges|Tips|unitig graph size|palindrome|Max:|output|disconnected|pruning|low depth|ubble|min depth", l)]
     res["mhx_digest"] = md5(os.path.join(d, "mine.contigs.fa"))
     if a.prune:
         m = re.search(r"profile clean_low_depth\s+(\d+) launches", p.stderr)
         res["low_depth_passes"] = int(m.group(1)) if m else None
         res["mhx_addi_digest"] = md5(os.path.join(d, "mine.addi.fa"))
+    if a.infer:  # the histogram kernel beside k_sdbg_pack, which reads the same multiplicities (same profiled run)
+        res["infer_ms"] = {g_: res["kernels_ms"].get(g_) for g_ in ("sdbg_mul_hist", "sdbg_pack")}
     if a.bubble:
         res["mhx_addi_digest"] = md5(os.path.join(d, "mine.addi.fa"))
         res["mhx_bubble_seq_digest"] = md5(os.path.join(d, "mine.bubble_seq.fa"))
