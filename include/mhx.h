@@ -85,7 +85,8 @@ int mhx_set_option(mhx_ctx *, const char *name, long long value);
 /* The value a knob has for this handle: an explicit mhx_set_option, else the environment variable MHX_<NAME>, else the
  * installation's tuned default — a `name = value` line of mhx_tuning.conf beside libmhx.so (MHX_TUNING_FILE names another
  * file, MHX_NO_TUNING=1 ignores it; written by tools/ab_options.py --write-tuning from an A/B on the box; read once, at
- * mhx_create) — else `dflt`.  Knobs only ever choose between code paths with identical results.  Round 3:
+ * mhx_create) — else `dflt`.  Knobs only ever choose between code paths with identical results.  (The library's own reads
+ * take the default in parentheses below, declared once in megahit_amd/csrc/mhx_options.h.)  Round 3:
  *   sort_unit_runs (1)     0: the chained-scan pass ranks, stages and writes its unit tile by tile (k_radix_onesweep) instead of
  *                          unit-wide runs (k_radix_onesweep_u)
  *   sort_rank_uniform (1)  0: every loading pass ranks with the match-any ballots.  1: a pass whose plan declares the bits

@@ -317,7 +317,7 @@ void upload_edges(mhx_ctx *c, const uint32_t *raw, uint64_t n_edges, uint32_t k,
   const uint64_t bases = n_edges * (uint64_t)len, n_out = div_ceil(bases, 16);
   // room for the mercy edges that may be appended behind them (SeqToSdbg::Initialize, seq_to_sdbg.cpp:370-378: 25 % by default,
   // MEGAHIT_NUM_MERCY_FACTOR otherwise — the CLI passes it on as edges_reserve_permille): the store does not have to grow then
-  const uint64_t permille = (uint64_t)std::min<long long>(std::max<long long>(c->opt("edges_reserve_permille", 1000), 1000), 100000);
+  const uint64_t permille = (uint64_t)std::min<long long>(std::max<long long>(c->opt<Opt::edges_reserve_permille>(), 1000), 100000);
   const uint64_t n_res = n_edges * permille / 1000;
   s.words.reserve((div_ceil(n_res * (uint64_t)len, 16) + kSeqPadWords) * 4);
   s.start.reserve((n_res + 2) * 8);
@@ -652,17 +652,6 @@ int mhx_synchronize(mhx_ctx *c) { MHX_TRY(MHX_HIP(hipStreamSynchronize(c->stream
 
 extern "C" const char *mhx_last_s1_plan(const mhx_ctx *c) { return c ? c->last_s1_plan.c_str() : ""; }
 
-long long mhx_ctx::opt(const char *name, long long dflt) const {
-  auto it = options.find(name);
-  if (it != options.end()) return it->second;
-  std::string env = "MHX_";
-  for (const char *p = name; *p; ++p) env += (char)toupper((unsigned char)*p);
-  const char *e = getenv(env.c_str());
-  if (e && *e) return atoll(e);
-  auto tu = tuned.find(name);
-  return tu != tuned.end() ? tu->second : dflt;
-}
-
 // mhx_tuning.conf beside libmhx.so: the knob settings measured best on this installation (tools/ab_options.py writes it from
 // an A/B on the box); `name = value` or `name value` per line, '#' starts a comment.  Every knob only chooses between
 // code paths that produce identical results.
@@ -785,7 +774,7 @@ int mhx_fetch(mhx_ctx *c, int which, void *dst, uint64_t offset, uint64_t bytes)
     auto it = c->results.find(which);
     if (it == c->results.end() || !it->second.p) throw mhx::Error("fetch: buffer not present");
     if (offset + bytes > it->second.used) throw mhx::Error("fetch: range exceeds buffer");
-    if (bytes >= (16u << 20) && c->opt("fetch_pinned", 1)) {
+    if (bytes >= (16u << 20) && c->opt<Opt::fetch_pinned>()) {
       MHX_HIP(hipStreamSynchronize(c->stream));
       download_pinned(c, dst, (const char *)it->second.p + offset, bytes);
     } else if (bytes) {
@@ -1153,7 +1142,7 @@ int mhx_dist_route_records(mhx_ctx *c, int which, uint64_t stride_bases, mhx_dis
       // and ONE pass over them (a two-field digit when it straddles the 32-bit words of the little-endian uint64; no copy,
       // no word swaps) replaces the full sort of the positions (5 passes + 3 copies of ~10^8 marks per rank and step).
       const int j = hi_bit > 8 ? hi_bit - 8 : 0;
-      if (c->opt("dist_marks_one_pass", 1) && n && j > 0 && j + 8 <= 64 && stride_bases % (1ull << j) == 0) {
+      if (c->opt<Opt::dist_marks_one_pass>() && n && j > 0 && j + 8 <= 64 && stride_bases % (1ull << j) == 0) {
         mhx::SortPass ps{0, 0, 0, 0};
         // key words = the two memory words of the record: word 0 (low half) is the "high" key word of the record sort
         if (j >= 32) ps = {j - 32, 8, 0, 0};

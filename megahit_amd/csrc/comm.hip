@@ -337,7 +337,7 @@ static bool dist_s1_presorted(mhx_ctx *c, mhx_comm *cm, uint32_t k, uint32_t m, 
   const int n = cm->n, rank = cm->rank;
   std::vector<uint64_t> v{it.n, it.S == 3 ? 0ull : 1ull};
   cm->all_reduce(v, true);  // the largest local item count decides for everybody; any rank with other records vetoes
-  if (v[1] || !c->opt("dist_presort", 1) || !s1_presort_applies(c, k, v[0])) return false;
+  if (v[1] || !c->opt<Opt::dist_presort>() || !s1_presort_applies(c, k, v[0])) return false;
   hipStream_t st = c->stream;
   uint32_t *a = c->work["items_a"].as<uint32_t>();
   uint32_t *b = c->ws("items_b", it.n * 12 + 64).as<uint32_t>();
@@ -400,11 +400,11 @@ static int skm_agree(mhx_ctx *c, mhx_comm *cm, uint32_t k, bool applies) {
   const uint64_t n_win_local = sq.n_bases > sq.n_seqs * (uint64_t)k ? sq.n_bases - sq.n_seqs * (uint64_t)k : 0;
   std::vector<uint64_t> v{applies ? 0ull : 1ull, n_win_local};
   cm->all_reduce(v, true);
-  const long long knob = c->opt("s1_skm", 1);
-  if (v[0] || (knob < 2 && v[1] * (uint64_t)cm->n < (uint64_t)c->opt("s1_skm_min_windows", 1 << 22))) return 0;
+  const long long knob = c->opt<Opt::s1_skm>();
+  if (v[0] || (knob < 2 && v[1] * (uint64_t)cm->n < (uint64_t)c->opt<Opt::s1_skm_min_windows>())) return 0;
   int bin_bits = 16;
   while (bin_bits < 20 && (double)v[1] * (double)cm->n * 0.29 / (double)(1ull << bin_bits) > 8192.0) ++bin_bits;
-  if (const long long fb = c->opt("s1_skm_bin_bits", 0)) bin_bits = (int)std::min<long long>(20, std::max<long long>(8, fb));
+  if (const long long fb = c->opt<Opt::s1_skm_bin_bits>()) bin_bits = (int)std::min<long long>(20, std::max<long long>(8, fb));
   return bin_bits;
 }
 static bool skm_exchange(mhx_ctx *c, mhx_comm *cm, uint32_t k, int bin_bits, bool for_count, SkmFront *o, std::vector<uint64_t> *hp_sum, std::string *why) {
@@ -636,7 +636,7 @@ static DistPasses plan_dist_passes_of(mhx_ctx *c, mhx_comm *cm, int stage, uint3
   DistPasses dp;
   // bytes per item a pass needs on a rank: the extracted copy + the send copy / sorted copy + receive buffer + its sort twin
   const double per_item = 4.0 * (double)item_bytes + 1.0;
-  uint64_t max_items = (uint64_t)c->opt("dist_max_items", 0);
+  uint64_t max_items = (uint64_t)c->opt<Opt::dist_max_items>();
   if (const char *e = getenv("MHX_MAX_ITEMS")) max_items = strtoull(e, nullptr, 10);
   const uint64_t plan_key = ((uint64_t)stage << 48) | ((uint64_t)k << 16) | (uint64_t)(m & 0xFFFFu);
   if (!max_items && !getenv("MHX_FREE_BYTES")) {
@@ -679,7 +679,7 @@ static DistPasses plan_dist_passes_of(mhx_ctx *c, mhx_comm *cm, int stage, uint3
   cm->all_reduce(w, true);
   const uint64_t P = std::min<uint64_t>(4096, (w[0] + max_items - 1) / max_items);
   if (P <= 1) {
-    if (!c->opt("dist_max_items", 0) && !getenv("MHX_MAX_ITEMS") && !getenv("MHX_FREE_BYTES")) cm->one_pass_ok.push_back(plan_key);
+    if (!c->opt<Opt::dist_max_items>() && !getenv("MHX_MAX_ITEMS") && !getenv("MHX_FREE_BYTES")) cm->one_pass_ok.push_back(plan_key);
     return dp;
   }
   dp.n = (int)P;
@@ -886,7 +886,7 @@ int mhx_dist_setup(mhx_ctx *c, mhx_comm *cm, int balance_stage, uint32_t k, uint
       cm->stride_bases = up(j);
     }
     MHX_CK(mhx_set_global_layout(c, (uint64_t)cm->rank * cm->stride_bases, (uint64_t)n * cm->stride_bases));
-    c->options["dist_sparse_marks"] = 1;
+    mhx::set_option(c->options, Opt::dist_sparse_marks, 1);
     cm->one_pass_ok.clear();
   })
 }
@@ -920,7 +920,7 @@ int mhx_dist_read2sdbg(mhx_ctx *c, mhx_comm *cm, uint32_t k, uint32_t min_count,
         if (!need_mercy && !done) {
           // (the pre-sort's first pass may make the records itself — and drop those of the buckets a pass leaves out: then
           // "items_a" holds nothing yet — s1.hip, S1GenT)
-          mhx::StageItems it = mhx::extract_stage(c, MHX_STAGE_S1, k, min_count, c->opt("dist_presort", 1) != 0);
+          mhx::StageItems it = mhx::extract_stage(c, MHX_STAGE_S1, k, min_count, c->opt<Opt::dist_presort>() != 0);
           done = mhx::dist_s1_presorted(c, cm, k, min_count, it, &rp);
           if (!done) {  // the classic exchange of the items extracted above: owner multisplit, all-to-all, sort at the owner
             // ... which were deferred to a sort that will not happen: make them now
@@ -1001,7 +1001,7 @@ int mhx_dist_count(mhx_ctx *c, mhx_comm *cm, uint32_t k, uint32_t min_count, mhx
       mhx_count_result rp{};
       bool done = false;
       std::string skm_why;
-      if (dp.n == 1 && c->opt("count_skm_dist", 0)) done = mhx::dist_count_skm(c, cm, k, min_count, &rp, &skm_why);  // super-k-mer records, exchanged by bin (opt-in)
+      if (dp.n == 1 && c->opt<Opt::count_skm_dist>()) done = mhx::dist_count_skm(c, cm, k, min_count, &rp, &skm_why);  // super-k-mer records, exchanged by bin (opt-in)
       if (!done && !mhx::dist_count_presorted(c, cm, k, min_count, &rp)) {  // the classic exchange: 16-byte items, owner multisplit, tile path at the owner
         const uint64_t n = mhx::exchange_stage(c, cm, MHX_STAGE_COUNT, k, min_count);
         MHX_CK(mhx_dist_process_count(c, k, min_count, n, &rp));

@@ -718,11 +718,11 @@ static std::vector<SortPass> count_sort_passes(mhx_ctx *c, uint32_t k, uint32_t 
   // Segment group-by (k_count_seg): sort only the top seg_bits of the key (a segment then holds ~100 records), count the
   // equal keys of every segment in LDS, sort the few solid edges afterwards.  16-byte records / 2-word edges (k <= 23).
   int seg_bits = 0;
-  if (c->opt("count_seg", 1) && S == 4 && KWv == 2 && wpe == 2 && m < 4096 && n_items) {
+  if (c->opt<Opt::count_seg>() && S == 4 && KWv == 2 && wpe == 2 && m < 4096 && n_items) {
     const double n_eff = (double)n_items * (double)(c->n_parts > 1 ? c->n_parts : 1);
     seg_bits = 8;
     while (seg_bits < 32 && n_eff / 96.0 > (double)(1ull << seg_bits)) seg_bits += 8;
-    if (c->opt("count_seg_bits", 0)) seg_bits = (int)c->opt("count_seg_bits", 0);
+    if (c->opt<Opt::count_seg_bits>()) seg_bits = (int)c->opt<Opt::count_seg_bits>();
     seg_bits = std::max(1, std::min(seg_bits, 32));
   }
   if (seg_bits_out) *seg_bits_out = seg_bits;
@@ -760,7 +760,7 @@ uint64_t count_extract(mhx_ctx *c, uint32_t k, uint32_t m, SortPrep *prep) {
   *prep = SortPrep{};
   if (n_items) {
     const unsigned grid = 256 * 8;
-    const bool fixed = s.fixed_len >= k + 1 && n_items == (uint64_t)ns * (s.fixed_len - k) && c->opt("count_extract_fixed", 1) != 0;
+    const bool fixed = s.fixed_len >= k + 1 && n_items == (uint64_t)ns * (s.fixed_len - k) && c->opt<Opt::count_extract_fixed>() != 0;
     DigitSpecs specs;
     specs.n = 0;
     unsigned long long *pre_hist = nullptr;
@@ -858,7 +858,7 @@ int count_process(mhx_ctx *c, uint32_t k, uint32_t m, uint32_t *buf_a, uint32_t 
     unsigned long long *ctrs = c->ws("cs_counters", 64).as<unsigned long long>();  // [0] distinct, [1] err
     MHX_HIP(hipMemsetAsync(ctrs, 0, 64, st));
     const uint32_t pfx_mask = seg_bits >= 32 ? 0xFFFFFFFFu : ~(0xFFFFFFFFu >> seg_bits);
-    const int la = (int)std::min<long long>(std::max<long long>(c->opt("count_seg_la", 3), 0), 6);  // 12-bit tile counters
+    const int la = (int)std::min<long long>(std::max<long long>(c->opt<Opt::count_seg_la>(), 0), 6);  // 12-bit tile counters
     CountSegArgs a{m, pfx_mask, s.start.as<uint64_t>(), s.n_seqs, s.fixed_len, first, last, hist, reinterpret_cast<unsigned long long *>(spare),
                    cap, counts, ctrs, events, ev_n, reinterpret_cast<uint32_t *>(ctrs + 1), la};
     // (multi-GPU: the events go to a buffer of their own — the spare sort buffer holds the edge regions here)
@@ -1076,7 +1076,7 @@ static bool count_run_stream(mhx_ctx *c, uint32_t k, uint32_t m, mhx_count_resul
     }
     if (!skm_done) {
       // count_skm = 3: a caller that left the memory plan to this path (mhx_count_self_planned) hears that it did not serve
-      if (c->opt("count_skm", 1) == 3) throw Error("count: super-k-mer records given up (low-complexity reads, or more records than the arrays hold)");
+      if (c->opt<Opt::count_skm>() == 3) throw Error("count: super-k-mer records given up (low-complexity reads, or more records than the arrays hold)");
       skm_edges = 0;
       if (touched) {
         MHX_HIP(hipMemsetAsync(first, 0xFF, (ns ? ns : 1) * 4, st));

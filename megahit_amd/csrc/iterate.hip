@@ -259,7 +259,7 @@ int iterate_edges(mhx_ctx *c, uint32_t k, uint32_t step, const uint32_t *ctg_wor
   uint64_t n_new = 0;
   if (n_reads) {
     uint32_t *pfx = nullptr;
-    if (k + 1 >= 12 && c->opt("iterate_prefix_filter", 1)) {
+    if (k + 1 >= 12 && c->opt<Opt::iterate_prefix_filter>()) {
       pfx = c->ws("it_prefix_bits", (size_t)(1u << kIterPfxBits) / 8).as<uint32_t>();
       MHX_HIP(hipMemsetAsync(pfx, 0, (size_t)(1u << kIterPfxBits) / 8, st));
       if (n_fl) {

@@ -870,7 +870,7 @@ uint32_t *kmsort_exact(mhx_ctx *c, uint32_t *buf_a, uint32_t *buf_b, uint64_t n,
   MHX_LAUNCH(c, "bucket_bounds", (double)MHX_NUM_BUCKETS * 8 * 30,
              hipLaunchKernelGGL(k_bucket_bounds, dim3((MHX_NUM_BUCKETS + 1 + 255) / 256), dim3(256), 0, st, grouped, n, S, bstart, 16));
   // 3. replay kmsort: one wave per bucket on tags + indices, gathered into the spare buffer
-  if (!c->opt("kmsort_emu_legacy", 0)) {
+  if (!c->opt<Opt::kmsort_emu_legacy>()) {
     uint32_t *other = grouped == buf_a ? buf_b : buf_a;
 #define MHX_CASE(SV)                                                   \
   case SV:                                                             \

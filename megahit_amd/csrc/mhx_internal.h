@@ -12,7 +12,10 @@
 #include <vector>
 
 #include "../../include/mhx.h"
+#include "mhx_options.h"
 #include "s1_handoff.h"
+
+using mhx::Opt;
 
 namespace mhx {
 
@@ -109,12 +112,17 @@ struct mhx_ctx {
   bool lm_ready = false, lm_mapped = false;
   uint64_t lm_n_ctg = 0, lm_cap = 0, lm_n_reads = 0;
   uint32_t lm_seed = 0;
-  // tuning knobs (mhx_set_option): explicit value, else environment MHX_<NAME>, else the default
+  // tuning knobs (mhx_set_option): explicit value, else environment MHX_<NAME>, else the default.  mhx_options.h declares every
+  // knob with its default and holds the rule (DESIGN.md "Tuning knobs"; include/mhx.h describes them)
   std::map<std::string, long long> options;
   // tuned defaults of this installation: `name = value` lines of mhx_tuning.conf beside libmhx.so (MHX_TUNING_FILE names
   // another file, MHX_NO_TUNING=1 ignores it), read at mhx_create; consulted after explicit options and the environment
   std::map<std::string, long long> tuned;
-  long long opt(const char *name, long long dflt) const;
+  template <mhx::Opt O>
+  long long opt() const { return mhx::resolve_option<O>(options, tuned); }
+  template <mhx::Opt O>
+  long long opt(long long fallback) const { return mhx::resolve_option<O>(options, tuned, fallback); }  // derived knobs
+  long long opt(const char *name, long long dflt) const { return mhx::resolve_option(options, tuned, name, dflt); }  // mhx_get_option only
   // pinned staging buffers of upload_pinned (capi.hip)
   void *pinned[2] = {nullptr, nullptr};
   hipEvent_t pinned_free[2] = {nullptr, nullptr};

@@ -132,7 +132,7 @@ void bucket_histogram(mhx_ctx *c, int stage, uint32_t k, uint32_t m, uint64_t *h
 // sort's first pass ("items_a" then holds nothing yet)
 StageItems extract_stage(mhx_ctx *c, int stage, uint32_t k, uint32_t m, bool s1_defer_items) {
   if (!c->filter_on) return extract_all(c, stage, k, m, s1_defer_items);
-  if (stage == MHX_STAGE_S2 && !s2_use_aggregated(c, k, m) && c->opt("s2_filter_in_extract", 1)) {
+  if (stage == MHX_STAGE_S2 && !s2_use_aggregated(c, k, m) && c->opt<Opt::s2_filter_in_extract>()) {
     // stage 2 per occurrence: the extraction itself leaves out the items of the dropped buckets (s2.hip s2_kept_mask) — one
     // scan of the reads per pass, no staging batches, no keep/drop split, nothing of the dropped buckets ever written
     StageItems r = extract_all(c, stage, k, m, false, true);

@@ -357,17 +357,17 @@ static std::vector<SortPass> s1_prefix_passes(int pbits) {
   return p;
 }
 S1Plan s1_plan(const mhx_ctx *c, uint32_t k, uint64_t n_items, bool compact, int want_mercy, bool allow_stream) {
-  const int force_bits = (int)c->opt("s1_seg_bits", 0);
+  const int force_bits = (int)c->opt<Opt::s1_seg_bits>();
   const int kmer_bits = (int)(k - 1) * 2;
   S1Plan p{s1_sort_passes(k), 0, false};
-  if (!c->opt("s1_seg", 1) || !compact || want_mercy || s1_kw(k) != 2 || s1_stride(k, compact) != 3 || !n_items) return p;
+  if (!c->opt<Opt::s1_seg>() || !compact || want_mercy || s1_kw(k) != 2 || s1_stride(k, compact) != 3 || !n_items) return p;
   const double per_bucket = s1_density(c, n_items);
   p.per_bucket = per_bucket;
   // (k <= 22: the local key — the (k-1)-mer below a 16-bit prefix + head/tail — fits 32 bits; up to k = 29, the widest (k-1)-mer the
   //  12-byte record holds, the table keys are 64 bits wide: s1_stream_wide, round 6)
-  if (allow_stream && c->opt("s1_stream", 1) && !force_bits && k >= 10 && (k <= 22 || (k <= 29 && c->opt("s1_stream_wide", 1)))) {
-    const double cap = (double)std::max<long long>(1, c->opt("s1_stream_max", 40000));
-    const int sub_max = (int)std::min<long long>(std::max<long long>(c->opt("s1_stream_sub_max", 1), 0), 6);
+  if (allow_stream && c->opt<Opt::s1_stream>() && !force_bits && k >= 10 && (k <= 22 || (k <= 29 && c->opt<Opt::s1_stream_wide>()))) {
+    const double cap = (double)std::max<long long>(1, c->opt<Opt::s1_stream_max>());
+    const int sub_max = (int)std::min<long long>(std::max<long long>(c->opt<Opt::s1_stream_sub_max>(), 0), 6);
     int need = 0;  // the buckets have to be 2^need times finer than the lv1 buckets
     while (need < 30 && per_bucket > cap * (double)(1ull << need)) ++need;
     int pbits = 16, sub0 = 0;
@@ -376,17 +376,17 @@ S1Plan s1_plan(const mhx_ctx *c, uint32_t k, uint64_t n_items, bool compact, int
       // a third pass costs the same for 17 or 24 prefix bits: aim at buckets that fill a third of the table — the inserts of a
       // table at two thirds take twice as long (tools/micro/insert_probe.hip), and the canonical (k-1)-mers make the low lv1
       // buckets twice as full as the average — but not at so many buckets that their fixed cost (a walk over 8192 slots) shows
-      const double cap3 = (double)std::max<long long>(1, c->opt("s1_stream_max3", std::max<long long>(1, (long long)cap / 2)));
+      const double cap3 = (double)std::max<long long>(1, c->opt<Opt::s1_stream_max3>(std::max<long long>(1, (long long)cap / 2)));
       need = 0;
       while (need < 30 && per_bucket > cap3 * (double)(1ull << need)) ++need;
       pbits = std::min(16 + std::max(need, 1), 24);
       sub0 = std::min(16 + need - pbits, 6);  // (past 24 bits: the rest as sub-rounds; the kernel splits further if it has to)
     }
-    if (const long long f = c->opt("s1_stream_bits", 0)) pbits = (int)std::min<long long>(std::max<long long>(f, 9), 24);
+    if (const long long f = c->opt<Opt::s1_stream_bits>()) pbits = (int)std::min<long long>(std::max<long long>(f, 9), 24);
     // several GPUs: the ranks cut each owner's slice of the pre-sorted records at lv1 bucket bounds (comm.hip, k_bucket_bounds
     // over 16 bits), which are monotone in the array only when it is sorted on at least those 16 bits
     if (c->n_parts > 1) pbits = std::max(pbits, 16);
-    const long long fs = c->opt("s1_stream_sub0", -1);
+    const long long fs = c->opt<Opt::s1_stream_sub0>();
     if (fs >= 0) sub0 = (int)std::min<long long>(fs, 6);
     pbits = std::min(pbits, kmer_bits);
     p.seg_bits = pbits;
@@ -418,7 +418,7 @@ std::string s1_plan_text(const mhx_ctx *c, uint32_t k, uint64_t n_items) {
 // (s1_pos_tag: 8 spare bits between the (k-1)-mer and head/tail, i.e. up to 2^(pos_bits + 8) bases: 7 G reads of 150 bp).
 uint32_t s1_pos_bits(const mhx_ctx *c) {
   const bool force = getenv("MHX_S1_FORCE_TAGGED") != nullptr;  // tests: tags at small sizes too
-  const long long f = c->opt("s1_pos_bits", 0);
+  const long long f = c->opt<Opt::s1_pos_bits>();
   if (f > 0) return (uint32_t)std::min<long long>(std::max<long long>(f, 4), 32);
   if (force) {  // the narrowest position word that keeps the tags below 128
     const uint64_t n_bits = c->global_bases ? c->global_bases : c->seqs.n_bases;
@@ -559,7 +559,7 @@ struct S1Stage {
     // multi-GPU with sparse marks (comm.hip): the marks of the non-solid occurrences leave this stage as a list of
     // global positions (ws "s1_marks", c->n_marks) to be routed to the read owners; no bitmap / byte map of the GLOBAL read
     // set exists unless the classic tile kernel has to run (then its byte map is converted to the list)
-    sparse = global && !mark_atomic && c->opt("dist_sparse_marks", 0) != 0;
+    sparse = global && !mark_atomic && c->opt<Opt::dist_sparse_marks>() != 0;
     n_words64 = sparse ? 0 : div_ceil(n_bits, 64);
     is_solid = c->result(MHX_BUF_IS_SOLID, (n_words64 + 1) * 8).as<unsigned long long>();
     c->results[MHX_BUF_IS_SOLID].used = n_words64 * 8;
@@ -594,7 +594,7 @@ struct S1Stage {
     // them take the digit histograms of that sort.  A workspace of their own: the front of a later pass over a range of bins writes
     // "sort_pre_hist" again.  Not when the items continue those of an earlier call (accumulate): the rows would be partial.
     agg_hist = nullptr;
-    if (agg && !global && !c->filter_on && !c->accumulate && agg_prev == 0 && c->opt("s2_pre_hist", 1) != 0) {
+    if (agg && !global && !c->filter_on && !c->accumulate && agg_prev == 0 && c->opt<Opt::s2_pre_hist>() != 0) {
       const std::vector<SortPass> ps = s2_agg_sort_passes(k);
       if (!ps.empty() && ps.size() <= (size_t)kItemHistRows) {
         agg_specs.n = (int)ps.size();
@@ -617,8 +617,8 @@ struct S1Stage {
   // the LDS group-bys on the partially sorted records: k_s1_stream (one bucket of the plan's prefix per workgroup at a time) or
   // k_s1_seg (tiles).  mode = mark_mode (2: statistics on a 1/64 sample)
   void launch_partial(int mode) {
-    const int per = (int)c->opt("s1_seg_per", 8);
-    const int la = (int)std::min<long long>(std::max<long long>(c->opt("s1_seg_la", 3), 0), 200);  // 16-bit tile counters
+    const int per = (int)c->opt<Opt::s1_seg_per>();
+    const int la = (int)std::min<long long>(std::max<long long>(c->opt<Opt::s1_seg_la>(), 0), 200);  // 16-bit tile counters
     const int T = 256 * (per == 4 ? 4 : 8);
     const uint64_t n_tiles = div_ceil(n_items, (uint64_t)T);
     const uint32_t stride = mode == 2 ? 64u : 1u;
@@ -656,9 +656,9 @@ struct S1Stage {
       seg_mcap = mcap;
     }
     // the stream kernel marks the non-solid occurrences from its table when each of them is its key's only record
-    const int direct = plan.stream && mode == 1 && m <= 2 && (mraw || solid_bytes) && c->opt("s1_stream_direct", 1) ? 1 : 0;
+    const int direct = plan.stream && mode == 1 && m <= 2 && (mraw || solid_bytes) && c->opt<Opt::s1_stream_direct>() ? 1 : 0;
     S1SegArgs a{(int)k, m, pfx_mask, eq_mask1, solid_bytes, mode, hist, ctr, raw, seg_cap, counts, mraw, mcap, mcounts, pos_stride, seg_err,
-                plan.stream ? (int)c->opt("s1_stream_probes", 1024) : la, direct};
+                plan.stream ? (int)c->opt<Opt::s1_stream_probes>() : la, direct};
     MHX_HIP(hipMemsetAsync(seg_err, 0, 4, st));
     const char *nm = mode == 2 ? "s1_sample" : "s1_groups";
     const double bytes = plan.stream ? (double)n_items * 12 / stride * (double)(1u << plan.sub0) : (double)n_work * T * 12;
@@ -684,17 +684,17 @@ struct S1Stage {
       const uint32_t *items0 = pre && sorted == nullptr ? pre->ptr[0] : sorted;
       const uint32_t nslot = half ? 4096u : 8192u;
       const S1StreamGeom geo{plan.seg_bits, plan.sub0, (uint32_t)n_buckets,
-                             (uint32_t)std::min<long long>(std::max<long long>(c->opt("s1_stream_fill", nslot * 7 / 8), 1), nslot)};
+                             (uint32_t)std::min<long long>(std::max<long long>(c->opt<Opt::s1_stream_fill>(nslot * 7 / 8), 1), nslot)};
       const bool tags = pos_stride != 0;
       const bool key64 = kmer_bits - plan.seg_bits + 6 > 32;  // the local key: the (k-1)-mer below the prefix + head/tail
       // giant buckets (S1Giant): found, cut into slices and reduced on the device before the streaming launch, finished by a second
       // launch of the streaming kernel over the same grid (direct marks only: a key's first record stands for its slice)
-      const bool giant_on = direct && !half && mode == 1 && c->opt("s1_giant", 1) != 0;
+      const bool giant_on = direct && !half && mode == 1 && c->opt<Opt::s1_giant>() != 0;
       uint32_t *ticket2 = nullptr;
       if (giant_on) {
         S1Giant &g = a.giant;
         g.gcap = 4096;
-        g.min_records = (uint32_t)std::max<long long>(1, c->opt("s1_giant_min", 262144));
+        g.min_records = (uint32_t)std::max<long long>(1, c->opt<Opt::s1_giant_min>());
         g.pcap = std::max<uint64_t>(2u << 20, n_items / 64);
         g.flag = c->ws("s1_giant_flag", n_buckets + 64).as<uint8_t>();
         uint32_t *lists = c->ws("s1_giant_lists", 64 + (size_t)g.gcap * (5 * 4 + 8)).as<uint32_t>();
@@ -939,7 +939,7 @@ struct S1Stage {
     const bool bound_too = n_words64 && !mark_atomic && mark_mode_used == 1 && !global;  // (the kernels that also count stage 2's '$' items)
     if (bound_too) {
       MHX_HIP(hipMemsetAsync(ctr + kCtrRunEnds, 0, 8, st));
-      if (s.fixed_len >= k + 16 && c->opt("s1_pack_fixed", 1))
+      if (s.fixed_len >= k + 16 && c->opt<Opt::s1_pack_fixed>())
         MHX_LAUNCH(c, "pack_solid", (double)n_words64 * 72,
                    hipLaunchKernelGGL(k_pack_solid_inv_fixed, dim3((unsigned)std::min<uint64_t>(div_ceil(n_words64 * 4, 256), 4096)), dim3(256), 0, st, solid_bytes, n_bits,
                                       s.fixed_len, (int)k, is_solid, n_words64, ctr));
@@ -1032,7 +1032,7 @@ void s1_apply_marks(mhx_ctx *c, const unsigned long long *recv, uint64_t n) {
                hipLaunchKernelGGL(k_apply_marks, dim3((unsigned)div_ceil(n, 256)), dim3(256), 0, st, recv, n, c->pos_base, s.n_bases, bytes, bad));
   DevBuf &b = c->result(MHX_BUF_IS_SOLID_LOCAL, (need + 1) * 8);
   b.used = need * 8;
-  if (need && s.fixed_len >= c->s1_acc_k + 16 && c->opt("s1_pack_fixed", 1))
+  if (need && s.fixed_len >= c->s1_acc_k + 16 && c->opt<Opt::s1_pack_fixed>())
     MHX_LAUNCH(c, "pack_solid", (double)need * 72,
                hipLaunchKernelGGL(k_pack_solid_inv_fixed, dim3((unsigned)std::min<uint64_t>(div_ceil(need * 4, 256), 4096)), dim3(256), 0, st, bytes, s.n_bases, s.fixed_len,
                                   (int)c->s1_acc_k, b.as<unsigned long long>(), need, ctr));
@@ -1057,14 +1057,14 @@ static uint64_t count_plan_items(const mhx_ctx *c, uint32_t k) {  // the item co
 // what both forms need: the shape the generators serve, the plan's digits in the first key word, a 32-bit table key
 static bool count_stream_shape(const mhx_ctx *c, uint32_t k, uint32_t m, bool edges_only) {
   const SeqSet &s = c->seqs;
-  if (!c->opt("count_stream", 1)) return false;
-  if (c->filter_on && !c->opt("s1_filter_in_gen", 1)) return false;
+  if (!c->opt<Opt::count_stream>()) return false;
+  if (c->filter_on && !c->opt<Opt::s1_filter_in_gen>()) return false;
   // (a caller that asks for a particular form of the tile path gets the tile path)
-  if (!c->opt("count_seg", 1) || c->opt("count_seg_bits", 0) || !c->opt("count_extract_fixed", 1)) return false;
+  if (!c->opt<Opt::count_seg>() || c->opt<Opt::count_seg_bits>() || !c->opt<Opt::count_extract_fixed>()) return false;
   // (min count 1, 2: seen-once / seen-twice bits per prev / next char in the table slot; 3..15: 4-bit counters that stop at m)
   if (!s.n_seqs || k < 9 || m < 1 || m > 15) return false;  // (k: count_shape_is_fast — up to 22 with a shared window per run, up to 27 with one per item)
   if (!count_shape_is_fast(c, k, edges_only)) return false;  // (reads of several lengths: item slots padded to the longest read's, CountGenVarT)
-  if (!c->opt("s1_fused_first_pass", 1) || !c->opt("sort_unit_runs", 1) || !c->opt("s1_gen_any_order", 1)) return false;
+  if (!c->opt<Opt::s1_fused_first_pass>() || !c->opt<Opt::sort_unit_runs>() || !c->opt<Opt::s1_gen_any_order>()) return false;
   const uint64_t n_bits = edges_only ? 0 : (c->global_bases ? c->global_bases : s.n_bases);  // (edges only: nobody reads the positions)
   if ((n_bits >> s1_pos_bits(c)) >= 256) return false;  // (positions beyond the tags)
   const uint64_t n_items = count_plan_items(c, k);
@@ -1085,7 +1085,7 @@ bool count_stream_applies(const mhx_ctx *c, uint32_t k, uint32_t m, bool edges_o
 }
 // several GPUs: this rank's say (the ranks decide together, comm.hip); the plan follows the density they agreed on (mhx_ctx::s1_density)
 bool count_presort_applies(const mhx_ctx *c, uint32_t k, uint32_t m) {
-  if (!c->global_bases || c->n_parts > kStreamSrcMax || !c->opt("dist_presort", 1)) return false;
+  if (!c->global_bases || c->n_parts > kStreamSrcMax || !c->opt<Opt::dist_presort>()) return false;
   return count_stream_shape(c, k, m, false);
 }
 // the front half on a rank of a multi-GPU run: this rank's records, made by the first sort pass and ordered by the plan's prefix
@@ -1180,7 +1180,7 @@ bool count_stream_groups(mhx_ctx *c, uint32_t k, uint32_t m, uint32_t *first_0_o
   a.agg_counts = counts;
   a.pos_stride = pos_stride;
   a.err = seg_err;
-  a.la_chunks = (int)c->opt("s1_stream_probes", 1024);
+  a.la_chunks = (int)c->opt<Opt::s1_stream_probes>();
   a.c_start = s.start.as<uint64_t>();
   a.c_n_seqs = s.n_seqs;
   a.c_fixed_len = s.fixed_len;
@@ -1193,14 +1193,14 @@ bool count_stream_groups(mhx_ctx *c, uint32_t k, uint32_t m, uint32_t *first_0_o
   if (global) {
     // events (8 bytes each; at most two per record of a solid key without an in- or out-edge: read ends, tips — a few per thousand
     // records) in per-workgroup regions of a buffer of their own: the spare sort buffer holds the edge regions
-    const uint64_t total = std::max<uint64_t>(n_items / (uint64_t)std::max<long long>(c->opt("count_event_share", 4), 1), (uint64_t)grid * 4096);
+    const uint64_t total = std::max<uint64_t>(n_items / (uint64_t)std::max<long long>(c->opt<Opt::count_event_share>(), 1), (uint64_t)grid * 4096);
     ecap = (uint32_t)std::min<uint64_t>(total / grid, 0xFFFFFFF0u);
     a.marks_raw = c->ws("cs_events", (size_t)grid * ecap * 8 + 64).as<unsigned long long>();
     a.marks_cap = ecap;
     a.marks_counts = ecounts = c->ws("cs_event_counts", (size_t)grid * 4).as<uint32_t>();
   }
   const S1StreamGeom geo{plan.seg_bits, plan.sub0, (uint32_t)n_buckets,
-                         (uint32_t)std::min<long long>(std::max<long long>(c->opt("s1_stream_fill", 8192 * 7 / 8), 1), 8192)};
+                         (uint32_t)std::min<long long>(std::max<long long>(c->opt<Opt::s1_stream_fill>(8192 * 7 / 8), 1), 8192)};
   const double bytes = (double)n_items * 12 * (double)(1u << plan.sub0);
   const uint32_t *items0 = pre ? pre->ptr[0] : sorted;
   const bool key64 = 2 * ((int)k + 1) - plan.seg_bits > 31;  // the (k+1)-mer below the prefix: wider than a 32-bit table key
@@ -1208,13 +1208,13 @@ bool count_stream_groups(mhx_ctx *c, uint32_t k, uint32_t m, uint32_t *first_0_o
   // one key into one — is cut into slices that many workgroups reduce into partial entries (a key's count and per-char counters in
   // the slice); the streaming launch skips it, a second launch over the same grid inserts the partial entries and does the per-key
   // work; a solid key without an in- or out-edge in such a bucket sends that launch's workgroup over the bucket's records once
-  const bool giant_on = c->opt("s1_giant", 1) != 0 && c->opt("count_giant", 1) != 0;
+  const bool giant_on = c->opt<Opt::s1_giant>() != 0 && c->opt<Opt::count_giant>() != 0;
   uint32_t *ticket2 = nullptr;
   const uint32_t *giant_ctr = nullptr;
   if (giant_on) {
     S1Giant &g = a.giant;
     g.gcap = 4096;
-    g.min_records = (uint32_t)std::max<long long>(1, c->opt("s1_giant_min", 262144));
+    g.min_records = (uint32_t)std::max<long long>(1, c->opt<Opt::s1_giant_min>());
     g.pcap = std::max<uint64_t>(2u << 20, n_items / 64);
     g.flag = c->ws("s1_giant_flag", n_buckets + 64).as<uint8_t>();
     uint32_t *lists = c->ws("s1_giant_lists", 64 + (size_t)g.gcap * (5 * 4 + 8)).as<uint32_t>();
@@ -1372,7 +1372,7 @@ int run_s1(mhx_ctx *c, uint32_t k, uint32_t m, int want_mercy, mhx_s1_result *ou
     if (s1_skm_try(c, k, m, out, &skm_why)) return 0;
     // s1_skm = 3: a caller that left the memory plan to this path (mhx_s1_self_planned) hears that it did not serve — the prefix plan
     // of a whole job that was never cut into lv1 bucket ranges may not fit
-    if (c->opt("s1_skm", 1) == 3) throw Error("read2sdbg_s1: super-k-mer records given up (" + skm_why + ")");
+    if (c->opt<Opt::s1_skm>() == 3) throw Error("read2sdbg_s1: super-k-mer records given up (" + skm_why + ")");
   }
   // s1_process sorts "items_a" first thing: its first pass may make the records (and apply a bucket filter)
   StageItems it = extract_stage(c, want_mercy ? MHX_STAGE_S1_MERCY : MHX_STAGE_S1, k, m, !want_mercy);

@@ -794,7 +794,7 @@ __global__ __launch_bounds__(1024) void k_s1_bucket_hist_var(const uint32_t *__r
 // -> true when it ran (fixed-length reads, 12-byte compact records); hist: device, 65 536 counters, zeroed by the caller
 bool s1_bucket_histogram_fast(mhx_ctx *c, uint32_t k, unsigned long long *hist) {
   SeqSet &s = c->seqs;
-  if (c->opt("s1_bucket_hist_fast", 1) && s1_shape_is_var_fast(c, k, s1_compact(c, k, 0))) {  // reads of any length: padded item slots
+  if (c->opt<Opt::s1_bucket_hist_fast>() && s1_shape_is_var_fast(c, k, s1_compact(c, k, 0))) {  // reads of any length: padded item slots
     constexpr int ITV = 8;
     const uint32_t per = s.max_len - k + 4;
     const uint64_t n_slots = s.n_seqs * (uint64_t)per;
@@ -807,14 +807,14 @@ bool s1_bucket_histogram_fast(mhx_ctx *c, uint32_t k, unsigned long long *hist) 
                                     per, n_slots, (int)k, hist, (uint32_t)(stride_items / per), (uint32_t)(stride_items % per), half));
     return true;
   }
-  if (!c->opt("s1_bucket_hist_fast", 1) || !s.n_seqs || s.fixed_len < k + 1 || !s1_compact(c, k, 0) || (2 * (k - 1) + 6 + 31) / 32 != 2 || k > 29) return false;  // (two key words)
+  if (!c->opt<Opt::s1_bucket_hist_fast>() || !s.n_seqs || s.fixed_len < k + 1 || !s1_compact(c, k, 0) || (2 * (k - 1) + 6 + 31) / 32 != 2 || k > 29) return false;  // (two key words)
   constexpr int IT = 8;
   const uint32_t per = s.fixed_len - k + 4;
   const uint64_t n_items = s.n_seqs * (uint64_t)per;
   const uint64_t cus = c->n_cus > 0 ? (uint64_t)c->n_cus : 256;
   const unsigned grid = (unsigned)std::min<uint64_t>(div_ceil(n_items, 1024 * IT), cus);
   const uint64_t stride_items = (uint64_t)grid * 1024 * IT;
-  const bool roll = per >= IT && (int)k <= kS1RollMaxK && c->opt("s1_digit_hist_roll", 1) != 0;
+  const bool roll = per >= IT && (int)k <= kS1RollMaxK && c->opt<Opt::s1_digit_hist_roll>() != 0;
   for (uint32_t half = 0; half < 2; ++half) {
     if (roll)
       MHX_LAUNCH(c, "s1_bucket_hist", (double)s.n_bases / 4,
@@ -834,16 +834,16 @@ bool count_shape_is_fast(const mhx_ctx *c, uint32_t k, bool edges_only) {
   const SeqSet &s = c->seqs;
   if (!s.n_seqs || k < 9) return false;
   if ((int)k > kCountStreamMaxK)  // k = 23..27: a window per item (CountGenWideT), reads of one length, no position tags
-    return (int)k <= kCountStreamWideMaxK && c->opt("count_stream_wide", 1) && s.fixed_len >= k + 1 && s.fixed_len - k >= 8 &&
+    return (int)k <= kCountStreamWideMaxK && c->opt<Opt::count_stream_wide>() && s.fixed_len >= k + 1 && s.fixed_len - k >= 8 &&
            (edges_only || ((s.n_bases >> s1_pos_bits(c)) == 0 && (c->global_bases >> s1_pos_bits(c)) == 0));
   if (s.fixed_len) return s.fixed_len >= k + 1 && s.fixed_len - k >= 8;
-  if (!c->opt("s1_var_fast", 1) || s.max_len < k + 1 || s.max_len - k < 8 || s.n_bases <= s.n_seqs * (uint64_t)k) return false;
-  return (double)s.n_bases * 100.0 >= (double)c->opt("s1_var_min_fill", 50) * (double)s.n_seqs * s.max_len;
+  if (!c->opt<Opt::s1_var_fast>() || s.max_len < k + 1 || s.max_len - k < 8 || s.n_bases <= s.n_seqs * (uint64_t)k) return false;
+  return (double)s.n_bases * 100.0 >= (double)c->opt<Opt::s1_var_min_fill>() * (double)s.n_seqs * s.max_len;
 }
 // -> true when it ran; hist: device, 65 536 counters, zeroed by the caller
 bool count_bucket_histogram_fast(mhx_ctx *c, uint32_t k, unsigned long long *hist) {
   SeqSet &s = c->seqs;
-  if (!c->opt("s1_bucket_hist_fast", 1) || !c->opt("count_stream", 1) || !count_shape_is_fast(c, k, false)) return false;
+  if (!c->opt<Opt::s1_bucket_hist_fast>() || !c->opt<Opt::count_stream>() || !count_shape_is_fast(c, k, false)) return false;
   constexpr int IT = 8;
   const bool var = s.fixed_len == 0;
   const uint32_t per = (var ? s.max_len : s.fixed_len) - k;
@@ -938,7 +938,7 @@ __global__ __launch_bounds__(256) void k_s1_extract_fast(const uint32_t *__restr
 // defer_items: the caller sorts "items_a" right away and hands that sort *prep, so (1) may be taken.
 bool s1_shape_is_fast(const mhx_ctx *c, uint32_t k, bool compact) {
   const SeqSet &s = c->seqs;
-  return s.n_seqs && s.fixed_len >= k + 1 && compact && s1_kw(k) == 2 && s1_stride(k, compact) == 3 && k <= 29 && c->opt("s1_extract_fast", 1) != 0;
+  return s.n_seqs && s.fixed_len >= k + 1 && compact && s1_kw(k) == 2 && s1_stride(k, compact) == 3 && k <= 29 && c->opt<Opt::s1_extract_fast>() != 0;
 }
 // The same front for a library whose reads are NOT of one length (S1GenVarT): item slots padded to the longest read's count.  Taken
 // while at least half of the slots are real records (s1_var_min_fill per cent) — beyond that the extraction kernel + loaded passes
@@ -946,17 +946,17 @@ bool s1_shape_is_fast(const mhx_ctx *c, uint32_t k, bool compact) {
 bool s1_shape_is_var_fast(const mhx_ctx *c, uint32_t k, bool compact) {
   const SeqSet &s = c->seqs;
   if (!s.n_seqs || s.fixed_len || s.max_len < k + 1 || s.max_len - k + 4 < 8 || !compact || s1_kw(k) != 2 || s1_stride(k, compact) != 3 || (int)k > kS1RollMaxK) return false;
-  if (!c->opt("s1_extract_fast", 1) || !c->opt("s1_var_fast", 1)) return false;
+  if (!c->opt<Opt::s1_extract_fast>() || !c->opt<Opt::s1_var_fast>()) return false;
   const double fill = (double)s.n_bases / ((double)s.n_seqs * s.max_len);
-  return fill * 100.0 >= (double)c->opt("s1_var_min_fill", 50);
+  return fill * 100.0 >= (double)c->opt<Opt::s1_var_min_fill>();
 }
 // can a bucket filter be applied inside the generating first pass (instead of extraction batches + a keep/drop split)?
 bool s1_filter_in_gen_applies(const mhx_ctx *c, uint32_t k) {
   const bool compact = s1_compact(c, k, 0);
   const bool var = s1_shape_is_var_fast(c, k, compact);
-  if (!c->filter_on || !c->opt("s1_filter_in_gen", 1) || !(s1_shape_is_fast(c, k, compact) || var) || !c->opt("s1_fused_first_pass", 1)) return false;
-  if (!c->opt("s1_digit_hist_blocked", 1) || !c->opt("s1_digit_hist_plain", 1) || !c->opt("s1_gen_any_order", 1) || !c->opt("sort_unit_runs", 1)) return false;
-  if (var && !(c->opt("s1_gen_blocked", 0) && c->opt("s1_gen_roll", 1) && c->opt("s1_digit_hist_roll", 1))) return false;
+  if (!c->filter_on || !c->opt<Opt::s1_filter_in_gen>() || !(s1_shape_is_fast(c, k, compact) || var) || !c->opt<Opt::s1_fused_first_pass>()) return false;
+  if (!c->opt<Opt::s1_digit_hist_blocked>() || !c->opt<Opt::s1_digit_hist_plain>() || !c->opt<Opt::s1_gen_any_order>() || !c->opt<Opt::sort_unit_runs>()) return false;
+  if (var && !(c->opt<Opt::s1_gen_blocked>() && c->opt<Opt::s1_gen_roll>() && c->opt<Opt::s1_digit_hist_roll>())) return false;
   const uint64_t n_slots = (uint64_t)c->seqs.n_seqs * ((var ? c->seqs.max_len : c->seqs.fixed_len) - k + 4);
   const S1Plan plan = s1_plan(c, k, n_slots, compact, 0);
   // (the plans whose digits are bit fields of the first key word: the prefix plans)
@@ -974,9 +974,9 @@ uint64_t s1_extract(mhx_ctx *c, uint32_t k, bool compact, SortPrep *prep, bool d
   uint64_t *item_start = c->ws("seq_item_start", (ns + 2) * 8).as<uint64_t>();
   uint64_t n_items = 0;
   // reads of any length on the generating pass (S1GenVarT): only as deferred items — there is no extraction kernel of that form
-  const bool var_fast = s1_shape_is_var_fast(c, k, compact) && (filter_in_gen || defer_items) && c->opt("s1_fused_first_pass", 1) &&
-                        c->opt("s1_gen_blocked", 0) && c->opt("s1_gen_roll", 1) && c->opt("s1_digit_hist_roll", 1) && c->opt("s1_digit_hist_blocked", 1) &&
-                        c->opt("s1_digit_hist_plain", 1) && c->opt("s1_gen_any_order", 1) && c->opt("sort_unit_runs", 1);
+  const bool var_fast = s1_shape_is_var_fast(c, k, compact) && (filter_in_gen || defer_items) && c->opt<Opt::s1_fused_first_pass>() &&
+                        c->opt<Opt::s1_gen_blocked>() && c->opt<Opt::s1_gen_roll>() && c->opt<Opt::s1_digit_hist_roll>() && c->opt<Opt::s1_digit_hist_blocked>() &&
+                        c->opt<Opt::s1_digit_hist_plain>() && c->opt<Opt::s1_gen_any_order>() && c->opt<Opt::sort_unit_runs>();
   const bool shape_fast = s1_shape_is_fast(c, k, compact) || var_fast;
   if (ns && shape_fast && s.fixed_len >= k + 1) {
     n_items = ns * (uint64_t)(s.fixed_len - k + 4);  // (no per-read table for reads of one length)
@@ -1030,11 +1030,11 @@ uint64_t s1_extract(mhx_ctx *c, uint32_t k, bool compact, SortPrep *prep, bool d
     }
     const bool fast = (fixed || var_ok) && shape_fast && specs.n <= kFastPasses;
     if (fast) {
-      const int it = (int)c->opt("s1_extract_items", 4);
+      const int it = (int)c->opt<Opt::s1_extract_items>();
       const uint32_t per = per_slots;
       // Deferred items: the caller sorts right away (run_s1, the multi-GPU pre-sort), so only the digit histograms are taken
       // here and the first sort pass makes the records itself (S1Gen): "items_a" stays empty until that pass has run.
-      const bool defer = filter_in_gen || var_ok || (defer_items && pre_hist && c->opt("s1_fused_first_pass", 1) &&
+      const bool defer = filter_in_gen || var_ok || (defer_items && pre_hist && c->opt<Opt::s1_fused_first_pass>() &&
                                                       sort_takes_generated_first_pass(c, n_items, 3, plan_passes));
 #define MHX_FAST(ITV, WR, NAME)                                                                                                        \
   do {                                                                                                                                 \
@@ -1048,7 +1048,7 @@ uint64_t s1_extract(mhx_ctx *c, uint32_t k, bool compact, SortPrep *prep, bool d
       for (int p = 0; p < specs.n; ++p) hi_only = hi_only && specs.d[p].wi1 == 0 && (!specs.d[p].mask2 || specs.d[p].wi2 == 0);
       if (defer) {
         const uint32_t *keep = filter_in_gen ? c->work["filter_bits"].as<uint32_t>() : nullptr;
-        bool plain = hi_only && c->opt("s1_digit_hist_blocked", 1) && c->opt("s1_digit_hist_plain", 1) != 0;  // every digit one bit field of the first key word?
+        bool plain = hi_only && c->opt<Opt::s1_digit_hist_blocked>() && c->opt<Opt::s1_digit_hist_plain>() != 0;  // every digit one bit field of the first key word?
         HiDigits hd;
         hd.n = specs.n;
         for (int p = 0; p < specs.n; ++p) {
@@ -1057,7 +1057,7 @@ uint64_t s1_extract(mhx_ctx *c, uint32_t k, bool compact, SortPrep *prep, bool d
           hd.mk[p] = specs.d[p].mask1;
         }
         if (filter_in_gen && !plain) throw Error("s1_extract: the bucket filter was left to a generating pass that does not apply");
-        if (hi_only && c->opt("s1_digit_hist_blocked", 1)) {
+        if (hi_only && c->opt<Opt::s1_digit_hist_blocked>()) {
           constexpr int ITH = 8;
           const unsigned fgrid = (unsigned)std::min<uint64_t>(div_ceil(n_slots, 256 * ITH), 256 * 8);
           const uint64_t stride_items = (uint64_t)fgrid * 256 * ITH;
@@ -1078,7 +1078,7 @@ uint64_t s1_extract(mhx_ctx *c, uint32_t k, bool compact, SortPrep *prep, bool d
                                 n_slots, (int)k, hd, pre_hist, (uint32_t)(stride_items / per), (uint32_t)(stride_items % per), keep,         \
                                 s.start.as<uint64_t>(), ns))
           // s1_digit_hist_roll: one window + one reverse complement per run of a thread's eight items (k <= 23, >= 8 slots per read)
-          const bool hroll = plain && per >= 8 && (int)k <= kS1RollMaxK && c->opt("s1_digit_hist_roll", 1) != 0;
+          const bool hroll = plain && per >= 8 && (int)k <= kS1RollMaxK && c->opt<Opt::s1_digit_hist_roll>() != 0;
           if (var_ok && !(hroll && plain)) throw Error("s1_extract: the variable-length generating pass met a plan it cannot count");
           if (var_ok && specs.n == 1) MHX_ROLL_VAR(1);
           else if (var_ok && specs.n == 2) MHX_ROLL_VAR(2);
@@ -1090,7 +1090,7 @@ uint64_t s1_extract(mhx_ctx *c, uint32_t k, bool compact, SortPrep *prep, bool d
           else if (hroll && specs.n == 3) MHX_ROLL(3);
           else if (hroll && specs.n == 4) MHX_ROLL(4);
 #undef MHX_ROLL
-          else if (plain && specs.n == 2 && per >= 8 && c->opt("s1_digit_hist_preload", 0) != 0) MHX_PLAIN2(2, true);
+          else if (plain && specs.n == 2 && per >= 8 && c->opt<Opt::s1_digit_hist_preload>() != 0) MHX_PLAIN2(2, true);
           else if (plain && specs.n == 1) MHX_PLAIN(1);
           else if (plain && specs.n == 2) MHX_PLAIN(2);
           else if (plain && specs.n == 3) MHX_PLAIN(3);
@@ -1118,9 +1118,9 @@ uint64_t s1_extract(mhx_ctx *c, uint32_t k, bool compact, SortPrep *prep, bool d
         // The consumers of this pass (the LDS group-bys behind the remaining passes; compact records, no mercy) count equal
         // keys: they need the records grouped, not in input order — so the first pass may place the records of a digit in
         // any order (the later passes are stable with respect to whatever order it leaves).
-        const bool any_order = c->opt("s1_gen_any_order", 1) != 0;
+        const bool any_order = c->opt<Opt::s1_gen_any_order>() != 0;
         // s1_gen_blocked: consecutive items per thread (S1GenBlocked) — only where the order inside a digit is free
-        const bool blocked = any_order && per >= 8 && c->opt("s1_gen_blocked", 0) != 0;
+        const bool blocked = any_order && per >= 8 && c->opt<Opt::s1_gen_blocked>() != 0;
         const S1GenT<false> g{s.words.as<uint32_t>(), s.fixed_len, per, (int)k, pos_base, pos_bits, nullptr};
         const S1GenT<true> gf{s.words.as<uint32_t>(), s.fixed_len, per, (int)k, pos_base, pos_bits, keep};
         const S1GenBlockedT<false> gb{s.words.as<uint32_t>(), s.fixed_len, per, (int)k, pos_base, pos_bits, (uint32_t)(kSortThreads * 8) / per,
@@ -1128,7 +1128,7 @@ uint64_t s1_extract(mhx_ctx *c, uint32_t k, bool compact, SortPrep *prep, bool d
         const S1GenBlockedT<true> gbf{s.words.as<uint32_t>(), s.fixed_len, per, (int)k, pos_base, pos_bits, (uint32_t)(kSortThreads * 8) / per,
                                       (uint32_t)(kSortThreads * 8) % per, keep};
         // s1_gen_roll: the blocked generator with one window + one reverse complement per run of a thread's items (k <= 23)
-        const bool roll = blocked && (int)k <= kS1RollMaxK && c->opt("s1_gen_roll", 1) != 0;
+        const bool roll = blocked && (int)k <= kS1RollMaxK && c->opt<Opt::s1_gen_roll>() != 0;
         if (var_ok && !roll) throw Error("s1_extract: the variable-length generating pass needs s1_gen_blocked and s1_gen_roll");
         prep->gen_var = var_ok;
         const S1GenVarT<false> gv{s.words.as<uint32_t>(), s.start.as<uint64_t>(), ns, per, (int)k, pos_base, pos_bits, (uint32_t)(kSortThreads * 8) / per,

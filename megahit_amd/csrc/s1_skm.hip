@@ -1829,30 +1829,30 @@ __global__ __launch_bounds__(kSkmThreads) void k_count_skm(SkmSrcs srcs, CountSk
 // ---- host ----
 // s1_skm_max_m: the largest min count served on super-k-mer records on ONE GPU — 2, or 3 / 4 with the LOOK form of k_s1_skm and the LV 4 form
 // of k_count_skm (values outside 2..4: the nearest)
-uint32_t s1_skm_max_m(const mhx_ctx *c) { return (uint32_t)std::min<long long>(std::max<long long>(c->opt("s1_skm_max_m", 2), 2), 4); }
+uint32_t s1_skm_max_m(const mhx_ctx *c) { return (uint32_t)std::min<long long>(std::max<long long>(c->opt<Opt::s1_skm_max_m>(), 2), 4); }
 
 bool s1_skm_applies(const mhx_ctx *c, uint32_t k, uint32_t m, int want_mercy) {
   const SeqSet &s = c->seqs;
-  const long long knob = c->opt("s1_skm", 1);
+  const long long knob = c->opt<Opt::s1_skm>();
   if (!knob || want_mercy || c->global_bases || c->n_parts > 1 || c->filter_on || c->accumulate || c->pos_base) return false;
   if (k < 19 || k > 22 || m < 1 || m > s1_skm_max_m(c)) return false;
   if (!s.n_seqs || s.max_len < k + 1 || (s.n_bases >> 36)) return false;
   // (reads of several lengths: every read takes the blocks of the longest — while at least s1_var_min_fill per cent of them hold windows)
-  if (!s.fixed_len && (double)s.n_bases * 100.0 < (double)c->opt("s1_var_min_fill", 50) * (double)s.n_seqs * s.max_len) return false;
+  if (!s.fixed_len && (double)s.n_bases * 100.0 < (double)c->opt<Opt::s1_var_min_fill>() * (double)s.n_seqs * s.max_len) return false;
   const char *e = getenv("MHX_S1_MARK");
   if (e && strcmp(e, "nonsolid")) return false;  // (a caller that asks for another polarity of the marks, or atomics into the bitmap)
   const uint64_t n_win = s.n_bases > s.n_seqs * (uint64_t)k ? s.n_bases - s.n_seqs * (uint64_t)k : 0;
-  return knob >= 2 || n_win >= (uint64_t)c->opt("s1_skm_min_windows", 1 << 22);
+  return knob >= 2 || n_win >= (uint64_t)c->opt<Opt::s1_skm_min_windows>();
 }
 
 // several GPUs (comm.hip dist_s1_skm): this rank's say — the same shape with a global layout; at most kSkmSrcMax ranks (one source per sender)
 bool s1_skm_dist_applies(const mhx_ctx *c, uint32_t k, uint32_t m) {
   const SeqSet &s = c->seqs;
-  if (!c->opt("s1_skm", 1) || !c->opt("dist_skm", 1) || !c->global_bases || c->n_parts > kSkmSrcMax || c->filter_on || c->accumulate) return false;
+  if (!c->opt<Opt::s1_skm>() || !c->opt<Opt::dist_skm>() || !c->global_bases || c->n_parts > kSkmSrcMax || c->filter_on || c->accumulate) return false;
   if (k < 19 || k > 22 || m < 1 || m > 2 || (c->global_bases >> 36)) return false;
   if (!s.n_seqs || s.max_len < k + 1) return false;
-  if (!s.fixed_len && (double)s.n_bases * 100.0 < (double)c->opt("s1_var_min_fill", 50) * (double)s.n_seqs * s.max_len) return false;
-  if (getenv("MHX_S1_MARK") || !c->opt("dist_sparse_marks", 1)) return false;
+  if (!s.fixed_len && (double)s.n_bases * 100.0 < (double)c->opt<Opt::s1_var_min_fill>() * (double)s.n_seqs * s.max_len) return false;
+  if (getenv("MHX_S1_MARK") || !c->opt<Opt::dist_sparse_marks>()) return false;
   return s1_skm_passes(c, k) == 1;
 }
 
@@ -1862,10 +1862,10 @@ int s1_skm_passes(const mhx_ctx *c, uint32_t k) {
   // the two record arrays of a pass together take s1_skm_pass_gb (hipMalloc costs per byte on this driver — seconds per 100 GB — while one
   // more pass costs one more scan of the reads by k_skm_make: 28 ms at 100 M reads); s1_skm_passes forces a count (tests)
   const SeqSet &s = c->seqs;
-  if (const long long f = c->opt("s1_skm_passes", 0)) return (int)std::min<long long>(64, std::max<long long>(1, f));
+  if (const long long f = c->opt<Opt::s1_skm_passes>()) return (int)std::min<long long>(64, std::max<long long>(1, f));
   const uint64_t n_win = s.n_bases > s.n_seqs * (uint64_t)k ? s.n_bases - s.n_seqs * (uint64_t)k : 0;
-  const double need = (double)n_win * (double)std::max<long long>(c->opt("s1_skm_cap_pct", 36), 1) / 100.0 * 32.0;
-  const double budget = (double)std::max<long long>(c->opt("s1_skm_pass_gb", 48), 1) * 1e9;
+  const double need = (double)n_win * (double)std::max<long long>(c->opt<Opt::s1_skm_cap_pct>(), 1) / 100.0 * 32.0;
+  const double budget = (double)std::max<long long>(c->opt<Opt::s1_skm_pass_gb>(), 1) * 1e9;
   return (int)std::min(64.0, std::max(1.0, std::ceil(need / budget)));
 }
 
@@ -1878,13 +1878,13 @@ bool s1_skm_front(mhx_ctx *c, uint32_t k, SkmFront *f, int pass, int n_passes, i
   const uint64_t n_win = var ? (s.n_bases > s.n_seqs * (uint64_t)k ? s.n_bases - s.n_seqs * (uint64_t)k : 0) : s.n_seqs * (uint64_t)(L - k);  // (var: an estimate)
   // the array: 0.284 records per window of random sequence at m = k - 8 (fewer in repeats); s1_skm_cap_pct per cent of the windows
   // (a pass of several: its share of the bins, which the hash fills evenly, and 15 % on top)
-  const uint64_t cap_all = n_win * (uint64_t)std::max<long long>(c->opt("s1_skm_cap_pct", 36), 1) / 100;
+  const uint64_t cap_all = n_win * (uint64_t)std::max<long long>(c->opt<Opt::s1_skm_cap_pct>(), 1) / 100;
   const uint64_t cap = std::max<uint64_t>(n_passes > 1 ? cap_all / n_passes + cap_all / n_passes * 15 / 100 : cap_all, 1u << 16);
   // bins: ~5000 records each (20 000 windows: what the table of one workgroup takes in one round) — 2^16 up to 14 M reads of 150 bases,
   // up to 2^20 and a third sort pass beyond
   int bin_bits = kSkmMinBinBits;
   while (bin_bits < kSkmMaxBinBits && (double)n_win * 0.29 / (double)(1ull << bin_bits) > 8192.0) ++bin_bits;
-  if (const long long fb = c->opt("s1_skm_bin_bits", 0)) bin_bits = (int)std::min<long long>(kSkmMaxBinBits, std::max<long long>(8, fb));
+  if (const long long fb = c->opt<Opt::s1_skm_bin_bits>()) bin_bits = (int)std::min<long long>(kSkmMaxBinBits, std::max<long long>(8, fb));
   if (bin_bits_agreed > 0) bin_bits = bin_bits_agreed;  // (several GPUs: the ranks made it from the size of the whole job)
   // (bits 0..7 of the first word are zero in every record: all passes may rank with LDS atomics)
   std::vector<SortPass> passes;
@@ -1893,7 +1893,7 @@ bool s1_skm_front(mhx_ctx *c, uint32_t k, SkmFront *f, int pass, int n_passes, i
   // and the sort starts at the second digit, reading the ranges in order.  Needs a second pass (the group-by cannot read an array with holes);
   // a range that overflows (a skewed input: the ranges hold the even share of hash-uniform bins and the array's slack) makes the records again, unsplit
   const std::vector<SortPass> passes_rest(passes.begin() + (passes.empty() ? 0 : 1), passes.end());
-  bool split = c->opt("s1_skm_split", 1) != 0 && passes.size() >= 2 && sort_takes_split_first_pass(c, passes_rest);
+  bool split = c->opt<Opt::s1_skm_split>() != 0 && passes.size() >= 2 && sort_takes_split_first_pass(c, passes_rest);
   const uint64_t cap_split = std::max<uint64_t>(cap, 1u << 20), range_cap = cap_split / 256 / kSortSplitUnit * kSortSplitUnit;
   const uint64_t cap_alloc = split ? cap_split : cap;
   uint4 *buf_a = c->ws("items_a", cap_alloc * 16 + 64).as<uint4>();
@@ -1902,25 +1902,25 @@ bool s1_skm_front(mhx_ctx *c, uint32_t k, SkmFront *f, int pass, int n_passes, i
   uint32_t *err = reinterpret_cast<uint32_t *>(cursor + 1);
   uint32_t *max_bin = err + 1;
   unsigned long long *split_cur = split ? c->ws("skm_split_cursors", (256 + 257) * 8).as<unsigned long long>() : nullptr;
-  const uint32_t stage_n = (uint32_t)std::min<long long>(std::max<long long>(c->opt("s1_skm_split_stage", kSkmStage), 0), kSkmStage);
+  const uint32_t stage_n = (uint32_t)std::min<long long>(std::max<long long>(c->opt<Opt::s1_skm_split_stage>(kSkmStage), 0), kSkmStage);
   unsigned long long *pre_hist = c->ws("sort_pre_hist", (size_t)kMaxFusedPasses * 256 * 8).as<unsigned long long>();
   constexpr int NT = 512, J = 2;
   const uint64_t cus = c->n_cus > 0 ? (uint64_t)c->n_cus : 256;
   // (s1_skm_make_grid: fewer workgroups, each with several trips over the blocks — tests on libraries of a few trips in all)
-  const long long grid_knob = c->opt("s1_skm_make_grid", 0);
+  const long long grid_knob = c->opt<Opt::s1_skm_make_grid>();
   const unsigned grid = (unsigned)std::min<uint64_t>(div_ceil(n_blocks, (uint64_t)NT * J), grid_knob > 0 ? (uint64_t)grid_knob : cus * 8);
   const uint32_t n_bins = 1u << bin_bits;
   const uint32_t bin_lo = (uint32_t)((uint64_t)n_bins * pass / n_passes), bin_hi = (uint32_t)((uint64_t)n_bins * (pass + 1) / n_passes);
   // homopolymer windows are counted beside the records on one GPU (several GPUs, stage 1: they stay in the records; a job with many gives the
   // path up.  count's tallies carry no position: on several GPUs the ranks add theirs up, comm.hip dist_count_skm)
   unsigned long long *hp = nullptr;
-  if ((!c->global_bases || for_count) && c->opt("s1_skm_hp", 1)) hp = c->ws("skm_hp", 512).as<unsigned long long>();  // [0..3] stage 1: windows per class, a position each; [8 + 16 class + ..] count: windows, bases in front, bases behind
+  if ((!c->global_bases || for_count) && c->opt<Opt::s1_skm_hp>()) hp = c->ws("skm_hp", 512).as<unsigned long long>();  // [0..3] stage 1: windows per class, a position each; [8 + 16 class + ..] count: windows, bases in front, bases behind
   // s1_skm_rep: the windows of period <= 4 join them (k_skm_make<.., REP>) — looked at only where the homopolymer windows are counted aside,
   // on one GPU; the table sits behind the homopolymer counters
-  const bool rep = hp && !c->global_bases && c->n_parts <= 1 && c->opt("s1_skm_rep", 0) != 0;
+  const bool rep = hp && !c->global_bases && c->n_parts <= 1 && c->opt<Opt::s1_skm_rep>() != 0;
   if (rep) hp = c->ws("skm_hp", (size_t)(kSkmRepAt + kSkmRepN * 9) * 8).as<unsigned long long>();
   // (s1_skm_rep_slots: slots of a workgroup's LDS hash in use — tests: few or none, and the entries go to the global table from the registers)
-  const unsigned long long rep_slots = (unsigned long long)std::min<long long>(std::max<long long>(c->opt("s1_skm_rep_slots", 64), 0), 64);
+  const unsigned long long rep_slots = (unsigned long long)std::min<long long>(std::max<long long>(c->opt<Opt::s1_skm_rep_slots>(), 0), 64);
   unsigned long long hp_init[48] = {0};
   hp_init[2] = hp_init[3] = ~0ull;
   unsigned long long h[4] = {0, 0, 0, 0};
@@ -1990,17 +1990,17 @@ bool s1_skm_front(mhx_ctx *c, uint32_t k, SkmFront *f, int pass, int n_passes, i
   const uint64_t n = h[0];
   // s1_skm_giant: a bin over the limit is worked in slices by several workgroups (skm_giant.h) instead of costing the job the path — one GPU
   // (bins_whole: min count 3 and 4 — the forms of the group-by that serve them take a bin whole; one beyond s1_skm_max_bin gives the job up)
-  const bool giant = !bins_whole && !c->global_bases && c->n_parts <= 1 && c->opt("s1_skm_giant", 0) != 0;
+  const bool giant = !bins_whole && !c->global_bases && c->n_parts <= 1 && c->opt<Opt::s1_skm_giant>() != 0;
   SkmGiantKnobs gk;
-  gk.max_records = (uint64_t)std::max<long long>(c->opt("s1_skm_giant_max", 1 << 21), 1);
-  gk.keys = (uint64_t)std::max<long long>(c->opt("s1_skm_giant_keys", 4096), 1);
-  gk.work_pct = (uint64_t)std::max<long long>(c->opt("s1_skm_giant_work_pct", 25), 0);
-  gk.slices = (uint64_t)std::min<long long>(std::max<long long>(c->opt("s1_skm_giant_slices", 0), 0), 1 << kSkmGiantMaxDepth);
+  gk.max_records = (uint64_t)std::max<long long>(c->opt<Opt::s1_skm_giant_max>(), 1);
+  gk.keys = (uint64_t)std::max<long long>(c->opt<Opt::s1_skm_giant_keys>(), 1);
+  gk.work_pct = (uint64_t)std::max<long long>(c->opt<Opt::s1_skm_giant_work_pct>(), 0);
+  gk.slices = (uint64_t)std::min<long long>(std::max<long long>(c->opt<Opt::s1_skm_giant_slices>(), 0), 1 << kSkmGiantMaxDepth);
   {  // a bin far over the limit shows in the digit histograms already — one value of EVERY digit stands out by its records: no need to
      // order the records to find it (low-complexity reads: 1 % of (AC)n reads put 1.7 M records behind one minimizer)
     const uint64_t n_bins_pass = std::max<uint64_t>(1, ((1ull << bin_bits) + n_passes - 1) / n_passes);
     // (s1_skm_giant: a bin over the limit is served — up to s1_skm_giant_max records, which is what must still be found here)
-    const uint64_t limit = giant ? gk.max_records : std::max<uint64_t>((uint64_t)c->opt("s1_skm_max_bin", 1 << 16), 16 * (n / n_bins_pass + 1));
+    const uint64_t limit = giant ? gk.max_records : std::max<uint64_t>((uint64_t)c->opt<Opt::s1_skm_max_bin>(), 16 * (n / n_bins_pass + 1));
     bool all = n > 0;
     uint64_t smallest_excess = ~0ull;
     for (size_t p = 0; p < passes.size() && all; ++p) {
@@ -2041,7 +2041,7 @@ bool s1_skm_front(mhx_ctx *c, uint32_t k, SkmFront *f, int pass, int n_passes, i
   MHX_LAUNCH(c, "s1_skm_bounds", (double)n_bins * 8 * 30,
              hipLaunchKernelGGL(k_skm_bounds, dim3((n_bins + 1 + 255) / 256), dim3(256), 0, st, reinterpret_cast<const uint4 *>(sorted), n, n_bins, bounds, max_bin));
   // a bin of many times the mean is low-complexity sequence (one minimizer for millions of windows): the prefix plan has the giant path
-  const uint64_t limit = std::max<uint64_t>((uint64_t)c->opt("s1_skm_max_bin", 1 << 16), 16 * (n / (bin_hi - bin_lo) + 1));
+  const uint64_t limit = std::max<uint64_t>((uint64_t)c->opt<Opt::s1_skm_max_bin>(), 16 * (n / (bin_hi - bin_lo) + 1));
   constexpr uint32_t kListCap = (uint32_t)kSkmGiantMaxBins + 1;  // (one more than is served: the cursor says how many there were)
   uint2 *giant_list = nullptr;
   if (giant && bin_hi > bin_lo) {  // the bins over the limit, listed behind the bounds (read back only when there is one)
@@ -2107,7 +2107,7 @@ void s1_skm_groups_launch(mhx_ctx *c, bool agg, unsigned grid, const SkmFront &f
   MHX_HIP(hipMemsetAsync(ticket, 0, 4, st));
   const uint32_t nslot = 1u << kSkmLogSlots;
   SkmArgs a{(int)k, m, solid_bytes, hist, agg_raw, agg_cap, agg_counts, err,
-            (uint32_t)std::min<long long>(std::max<long long>(c->opt("s1_stream_fill", nslot * 7 / 8), 1), nslot), (int)std::min<long long>(c->opt("s1_stream_probes", 1024), 1024),
+            (uint32_t)std::min<long long>(std::max<long long>(c->opt<Opt::s1_stream_fill>(nslot * 7 / 8), 1), nslot), (int)std::min<long long>(c->opt<Opt::s1_stream_probes>(), 1024),
             f.bin_lo, f.bin_hi, marks_raw, marks_cap, marks_counts, f.giants, f.n_giant_items, f.giant_limit};
   const bool giant = f.n_giant_items != 0 && f.n_src == 1;  // (the front lists giant bins on one GPU only)
   SkmSrcs srcs{};
@@ -2117,8 +2117,8 @@ void s1_skm_groups_launch(mhx_ctx *c, bool agg, unsigned grid, const SkmFront &f
     srcs.bounds[q] = f.src_bounds[q];
   }
   const uint64_t n_bits = c->global_bases ? c->global_bases : c->seqs.n_bases;
-  const bool tags = (n_bits >> 32) != 0 || c->opt("s1_skm_tags", 0) != 0;
-  const long long deal = std::min<long long>(std::max<long long>(c->opt("s1_skm_deal", 2), 0), 2);  // (a value outside 0..2: the nearest form)
+  const bool tags = (n_bits >> 32) != 0 || c->opt<Opt::s1_skm_tags>() != 0;
+  const long long deal = std::min<long long>(std::max<long long>(c->opt<Opt::s1_skm_deal>(), 0), 2);  // (a value outside 0..2: the nearest form)
 #define MHX_SKM_G(AGGV, TAGV, GV)                                                                                                \
   do {                                                                                                                           \
     if (deal == 2) hipLaunchKernelGGL((k_s1_skm<AGGV, TAGV, 2, GV>), dim3(grid), dim3(kSkmThreads), 0, st, srcs, a, ticket);      \
@@ -2152,13 +2152,13 @@ void s1_skm_groups_launch(mhx_ctx *c, bool agg, unsigned grid, const SkmFront &f
 // ---- `count` on super-k-mer records: one GPU, 19 <= k <= 21 (k + 10 bases and two flags in a record), min count <= 2 (s1_skm_max_m: up to 4), one pass ----
 bool count_skm_applies(const mhx_ctx *c, uint32_t k, uint32_t m) {
   const SeqSet &s = c->seqs;
-  const long long knob = c->opt("count_skm", 1);
-  if (!knob || !c->opt("s1_skm", 1) || c->global_bases || c->n_parts > 1 || c->filter_on || c->accumulate || c->pos_base) return false;
+  const long long knob = c->opt<Opt::count_skm>();
+  if (!knob || !c->opt<Opt::s1_skm>() || c->global_bases || c->n_parts > 1 || c->filter_on || c->accumulate || c->pos_base) return false;
   if (k < 19 || k > 21 || m < 1 || m > s1_skm_max_m(c)) return false;
   if (!s.n_seqs || s.max_len < k + 1 || (s.n_bases >> 36)) return false;
-  if (!s.fixed_len && (double)s.n_bases * 100.0 < (double)c->opt("s1_var_min_fill", 50) * (double)s.n_seqs * s.max_len) return false;
+  if (!s.fixed_len && (double)s.n_bases * 100.0 < (double)c->opt<Opt::s1_var_min_fill>() * (double)s.n_seqs * s.max_len) return false;
   const uint64_t n_win = s.n_bases > s.n_seqs * (uint64_t)k ? s.n_bases - s.n_seqs * (uint64_t)k : 0;
-  return knob >= 2 || c->opt("s1_skm", 1) >= 2 || n_win >= (uint64_t)c->opt("s1_skm_min_windows", 1 << 22);
+  return knob >= 2 || c->opt<Opt::s1_skm>() >= 2 || n_win >= (uint64_t)c->opt<Opt::s1_skm_min_windows>();
 }
 // the group-by's launch over the sources of `f`, edges to `grid` regions of `region` entries in `edges_raw`.  ev_raw: the EVENTS form — the
 // windows of flagged keys leave as events in regions of ev_cap entries (several GPUs) instead of moving first_0_out / last_0_in here.
@@ -2177,7 +2177,7 @@ static uint32_t count_skm_launch(mhx_ctx *c, uint32_t k, uint32_t m, const SkmFr
   if (ev_raw) MHX_HIP(hipMemsetAsync(ev_counts, 0, (size_t)grid * 4, st));
   const uint32_t nslot = 1u << kSkmLogSlots;
   CountSkmArgs a{(int)k, m, hist, ctr, edges_raw, region, counts, seg_err,
-                 (uint32_t)std::min<long long>(std::max<long long>(c->opt("s1_stream_fill", nslot * 7 / 8), 1), nslot), (int)std::min<long long>(c->opt("s1_stream_probes", 1024), 1024),
+                 (uint32_t)std::min<long long>(std::max<long long>(c->opt<Opt::s1_stream_fill>(nslot * 7 / 8), 1), nslot), (int)std::min<long long>(c->opt<Opt::s1_stream_probes>(), 1024),
                  f.bin_lo, f.bin_hi, s.start.as<uint64_t>(), s.n_seqs, s.fixed_len, first_0_out, last_0_in_p1, ev_raw, ev_cap, ev_counts,
                  f.giants, f.n_giant_items, f.giant_limit};
   const bool giant = f.n_giant_items != 0 && f.n_src == 1 && !ev_raw;  // (the front lists giant bins on one GPU only)
@@ -2188,8 +2188,8 @@ static uint32_t count_skm_launch(mhx_ctx *c, uint32_t k, uint32_t m, const SkmFr
     srcs.bounds[q] = f.src_bounds[q];
   }
   const uint64_t n_bits = c->global_bases ? c->global_bases : s.n_bases;
-  const bool tags = (n_bits >> 32) != 0 || c->opt("s1_skm_tags", 0) != 0;
-  const bool g2 = c->opt("count_skm_group", 2) == 2;  // (four chunks per round of compare-and-swaps spill registers here: measured 13.6 against 13.1 ms)
+  const bool tags = (n_bits >> 32) != 0 || c->opt<Opt::s1_skm_tags>() != 0;
+  const bool g2 = c->opt<Opt::count_skm_group>() == 2;  // (four chunks per round of compare-and-swaps spill registers here: measured 13.6 against 13.1 ms)
 #define MHX_CSKM(EV, GV)                                                                                                                 \
   do {                                                                                                                                   \
     if (tags && g2) hipLaunchKernelGGL((k_count_skm<true, 2, EV, GV>), dim3(grid), dim3(kSkmThreads), 0, st, srcs, a, ticket);            \
@@ -2261,11 +2261,11 @@ bool count_skm_groups(mhx_ctx *c, uint32_t k, uint32_t m, uint32_t *first_0_out,
 // source per sender), no memory plan; a rank without a window (no reads, or none of k + 1 bases) takes part: it sends nothing and owns its bins
 bool count_skm_dist_applies(const mhx_ctx *c, uint32_t k, uint32_t m) {
   const SeqSet &s = c->seqs;
-  if (!c->opt("count_skm", 1) || !c->opt("s1_skm", 1) || !c->opt("dist_skm", 1) || !c->opt("count_skm_dist", 0)) return false;
+  if (!c->opt<Opt::count_skm>() || !c->opt<Opt::s1_skm>() || !c->opt<Opt::dist_skm>() || !c->opt<Opt::count_skm_dist>()) return false;
   if (!c->global_bases || c->n_parts > kSkmSrcMax || c->filter_on || c->accumulate || (c->global_bases >> 36)) return false;
   if (k < 19 || k > 21 || m < 1 || m > 2) return false;
   if (s.n_seqs && s.max_len >= k + 1 && !s.fixed_len &&
-      (double)s.n_bases * 100.0 < (double)c->opt("s1_var_min_fill", 50) * (double)s.n_seqs * s.max_len)
+      (double)s.n_bases * 100.0 < (double)c->opt<Opt::s1_var_min_fill>() * (double)s.n_seqs * s.max_len)
     return false;
   return s1_skm_passes(c, k) == 1;
 }
@@ -2289,8 +2289,8 @@ bool count_skm_owner(mhx_ctx *c, uint32_t k, uint32_t m, const SkmFront &f, unsi
   const uint32_t region = (uint32_t)std::min<uint64_t>(have / grid, 0xFFFFFFF0u);
   // event regions: at most two per window of a solid key without an in- or out-edge (read ends, tips: a few per thousand windows);
   // count_skm_ev_cap sets the entries of a region (tests)
-  const long long ev_knob = c->opt("count_skm_ev_cap", 0);
-  const uint64_t ev_total = std::max<uint64_t>(f.n_records / (uint64_t)std::max<long long>(c->opt("count_event_share", 4), 1) * 4, (uint64_t)grid * 4096);
+  const long long ev_knob = c->opt<Opt::count_skm_ev_cap>();
+  const uint64_t ev_total = std::max<uint64_t>(f.n_records / (uint64_t)std::max<long long>(c->opt<Opt::count_event_share>(), 1) * 4, (uint64_t)grid * 4096);
   const uint32_t ev_cap = ev_knob > 0 ? (uint32_t)std::min<long long>(ev_knob, 0xFFFFFFF0ll) : (uint32_t)std::min<uint64_t>(ev_total / grid, 0xFFFFFFF0u);
   unsigned long long *ev_raw = c->ws("cs_events", (size_t)grid * ev_cap * 8 + 64).as<unsigned long long>();
   uint32_t *counts = c->ws("cs_edge_counts", (size_t)grid * 4).as<uint32_t>();

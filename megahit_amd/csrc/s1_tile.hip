@@ -638,7 +638,7 @@ static void s1_groups_launch(mhx_ctx *c, const uint32_t *sorted, uint64_t n_item
   const unsigned grid = tile_grid(n_tiles);
   // mercy candidates in per-workgroup regions of the spare sort buffer (2 entries of 8 bytes per 16-byte record): region b
   // starts at twice the number of records in the tiles of the workgroups before b — 2 * n_items entries in all
-  const bool regions = !COMPACT && want_mercy && n_items && c->opt("s1_mercy_regions", 1);
+  const bool regions = !COMPACT && want_mercy && n_items && c->opt<Opt::s1_mercy_regions>();
   uint32_t *counts = nullptr;
   uint64_t *d_off = nullptr;
   if (regions) {
@@ -677,7 +677,7 @@ static void s1_groups_launch(mhx_ctx *c, const uint32_t *sorted, uint64_t n_item
   std::vector<uint32_t> h_counts(grid + 1);
   MHX_HIP(hipMemcpyAsync(h_counts.data(), counts, (size_t)(grid + 1) * 4, hipMemcpyDeviceToHost, st));
   MHX_HIP(hipStreamSynchronize(st));
-  if (h_counts[grid] || c->opt("s1_mercy_regions", 1) == 2) {  // (2: tests force the way back)
+  if (h_counts[grid] || c->opt<Opt::s1_mercy_regions>() == 2) {  // (2: tests force the way back)
     MHX_HIP(hipMemcpyAsync(hist, hist_save, (MHX_MAX_MUL + 1) * 8, hipMemcpyDeviceToDevice, st));
     MHX_HIP(hipMemsetAsync(ctr, 0, 16, st));
     if (AGG && agg_cursor) MHX_HIP(hipMemcpyAsync(agg_cursor, agg_before, 24, hipMemcpyHostToDevice, st));

@@ -1160,7 +1160,7 @@ static void emit_sdbg_impl(mhx_ctx *c, const uint32_t *sorted, uint64_t n_items,
     // seq2sdbg, one record per distinct (k+1)-mer and strand.  Items per OCCURRENCE (min count 1, k > 22: a run = the occurrences of
     // one edge, ~coverage records) keep the tile kernel, whose work per record does not grow with the run: measured on the configs[4]
     // shard (10 G items, runs of ~15) 79 + 126 ms against 408 + 416 ms for the run-head form.  sdbg_fast = 2 forces it (tests).
-    const long long fast_opt = c->opt("sdbg_fast", 1);
+    const long long fast_opt = c->opt<Opt::sdbg_fast>();
     if ((fast_opt == 2 || (fast_opt == 1 && P.is_seq != 0)) && P.kw >= 1 && P.kw <= 2 && P.aw <= 1) {
       SdbgFastP F;
       F.gmask = kmer_bits >= 64 ? ~0ull : (kmer_bits ? ~0ull << (64 - kmer_bits) : 0ull);
@@ -1174,8 +1174,8 @@ static void emit_sdbg_impl(mhx_ctx *c, const uint32_t *sorted, uint64_t n_items,
       F.wpt = P.wpt;
       F.k = P.k;
       F.ref_kw = P.ref_kw;
-      F.halo = (int)std::min<long long>(kSdbgFastHalo, std::max<long long>(1, c->opt("sdbg_fast_halo", kSdbgFastHalo)));
-      const int ft = (int)c->opt("sdbg_fast_tile", 2048);  // records per workgroup: 1024 | 2048 | 4096
+      F.halo = (int)std::min<long long>(kSdbgFastHalo, std::max<long long>(1, c->opt<Opt::sdbg_fast_halo>(kSdbgFastHalo)));
+      const int ft = (int)c->opt<Opt::sdbg_fast_tile>();  // records per workgroup: 1024 | 2048 | 4096
       const uint64_t ftile = ft == 1024 ? 1024 : (ft == 4096 ? 4096 : 2048);
       const uint64_t n_ft = div_ceil(n_items, ftile);
       uint64_t *ftt = c->ws("tile_tot", (3 * n_ft + 4) * 8).as<uint64_t>();
@@ -1185,7 +1185,7 @@ static void emit_sdbg_impl(mhx_ctx *c, const uint32_t *sorted, uint64_t n_items,
       uint64_t out_bytes = 0;
       // sdbg_fast_keep: the counting launch keeps what its run heads found (4 bytes per record, up to sdbg_fast_keep_max_mb of them)
       // and the emitting launch only scans and writes
-      const bool keep = c->opt("sdbg_fast_keep", 1) != 0 && n_items * 4 <= (uint64_t)c->opt("sdbg_fast_keep_max_mb", 4096) << 20;
+      const bool keep = c->opt<Opt::sdbg_fast_keep>() != 0 && n_items * 4 <= (uint64_t)c->opt<Opt::sdbg_fast_keep_max_mb>() << 20;
       uint32_t *res_g = keep ? c->ws("sdbg_res", n_items * 4 + 64).as<uint32_t>() : nullptr;
 #define MHX_SDBG_FAST(EMITV, NAME, BYTES, TT, TB)                                                                                          \
   do {                                                                                                                                     \
@@ -1461,7 +1461,7 @@ static S2dFront s2d_open(mhx_ctx *c, uint32_t k, uint32_t m, const unsigned long
   f.cur = c->ws("s2d_cursor", 64).as<unsigned long long>();
   MHX_HIP(hipMemsetAsync(f.cur, 0, 64, st));
   if (!f.n_words) return f;
-  const long long mode = c->opt("s2_bound_from_s1", 1);  // (2: both, and they must agree — tests)
+  const long long mode = c->opt<Opt::s2_bound_from_s1>();  // (2: both, and they must agree — tests)
   uint64_t s1_bound = 0;
   const bool cached = from_s1 && mode != 0 && c->s1.bound_for(k, m, &s1_bound);
   f.bound = s1_bound;
@@ -1484,10 +1484,10 @@ static uint64_t s2d_emit_items(mhx_ctx *c, uint32_t k, const S2dFront &f, uint32
   hipStream_t st = c->stream;
   const uint64_t trips = div_ceil(f.n_words, 256 * kS2dWords);
   dim3 grid((unsigned)std::min<uint64_t>(trips, 4096));
-  if (c->opt("s2_dummy_list", 1) != 0) {
+  if (c->opt<Opt::s2_dummy_list>() != 0) {
     // (every workgroup ends with up to 256 global atomics per histogram row: no more of them than the device holds at once, 5 per CU)
     grid.x = (unsigned)std::min<uint64_t>(trips, (uint64_t)(c->n_cus > 0 ? c->n_cus : 256) * 5);
-    const long long cap = c->opt("s2_dummy_list_cap", 0);
+    const long long cap = c->opt<Opt::s2_dummy_list_cap>();
     const uint32_t list_cap = cap > 0 ? (uint32_t)std::min<long long>(cap, kS2dList) : (uint32_t)kS2dList;
     const DigitSpecs none{};
     if (!specs || specs->n > kItemHistRows) hist = nullptr;
@@ -1598,7 +1598,7 @@ __global__ __launch_bounds__(256) void k_valid_starts(unsigned long long *__rest
 }
 
 bool s2_agg_from_count_applies(const mhx_ctx *c, uint32_t k, uint32_t m) {
-  if (!c->opt("s2_agg_from_count", 1) || c->filter_on || c->accumulate || c->n_parts > 1 || c->global_bases) return false;
+  if (!c->opt<Opt::s2_agg_from_count>() || c->filter_on || c->accumulate || c->n_parts > 1 || c->global_bases) return false;
   if (m < 1 || k < 10 || k > 27) return false;
   if (m > 1 && (k <= 22 || !c->s1.bitmap_is_s1s(k, m))) return false;  // (k <= 22: stage 1 made the aggregated items itself)
   return count_stream_applies(c, k, m, true);
@@ -1672,21 +1672,6 @@ struct S2FilterGuard {
     c->filter_kept = r.hi - r.lo;
   }
 };
-// the knobs the route sets for its count unless the caller set them: gone again when the route is left, however
-struct S2KnobGuard {
-  mhx_ctx *c;
-  std::vector<std::string> set;
-  void put(const char *name, long long v) {
-    std::string env = std::string("MHX_") + name;
-    for (char &ch : env) ch = (char)toupper((unsigned char)ch);
-    if (c->options.count(name) || getenv(env.c_str())) return;
-    c->options[name] = v;
-    set.push_back(name);
-  }
-  ~S2KnobGuard() {
-    for (const std::string &n : set) c->options.erase(n);
-  }
-};
 // the accumulated item array of a run in passes: released unless the run got as far as the sort
 struct S2AccGuard {
   mhx_ctx *c;
@@ -1701,7 +1686,7 @@ struct S2AccGuard {
 };
 // the exact need of the route against s2_count_budget_mb (0: no check), with the allocator's headroom: -> false when it is exceeded
 static bool s2_count_in_budget(const mhx_ctx *c, uint32_t m, uint64_t pass_records, uint64_t n_items) {
-  const long long mb = c->opt("s2_count_budget_mb", 0);
+  const long long mb = c->opt<Opt::s2_count_budget_mb>();
   if (mb <= 0) return true;
   const uint64_t need = s2_from_count_need(c, m, pass_records, n_items);
   return need + need / 16 <= (uint64_t)mb << 20;
@@ -1805,7 +1790,7 @@ static bool s2_agg_from_count(mhx_ctx *c, uint32_t k, uint32_t m, mhx_sdbg_resul
   const uint32_t cmax = cb ? (1u << cb) - 1u : (uint32_t)MHX_MAX_MUL;
   // s2_count_pass_items > 0: the count in passes of at most that many records.  More than kS2CountMaxPasses of them: declined before
   // anything was done
-  const uint64_t pass_cap = (uint64_t)std::max<long long>(c->opt("s2_count_pass_items", 0), 0);
+  const uint64_t pass_cap = (uint64_t)std::max<long long>(c->opt<Opt::s2_count_pass_items>(), 0);
   std::vector<S2CountRange> ranges;
   if (pass_cap) {
     ranges = s2_count_ranges(c, k, m, pass_cap);
@@ -1823,10 +1808,11 @@ static bool s2_agg_from_count(mhx_ctx *c, uint32_t k, uint32_t m, mhx_sdbg_resul
   // at the configs[4] shard against a twentieth at 60 x coverage).  Sub-rounds — a second read of every bucket instead of a third sort pass —
   // then still overflow the table and split again (count_groups 198 ms at 40 M reads), a third pass over a finer prefix does not
   // (36 ms + 27 for the pass): the plan is made with s1_stream_sub_max = 0 and 12 000 records per bucket unless the caller set those knobs.
-  S2KnobGuard knobs{c, {}};
+  // (OptScope: gone again when the route is left, however)
+  OptScope knobs(c->options);
   if (m == 1) {
-    knobs.put("s1_stream_sub_max", 0);
-    knobs.put("s1_stream_max3", 12000);
+    knobs.put(Opt::s1_stream_sub_max, 0);
+    knobs.put(Opt::s1_stream_max3, 12000);
   }
   if (pass_cap) {
     if (s2_agg_from_count_passes(c, k, m, out, ranges, first, last, hist, why)) return true;
@@ -1890,7 +1876,7 @@ static int s2_agg_in_place(mhx_ctx *c, uint32_t k, mhx_sdbg_result *out) {
   const std::vector<SortPass> passes = s2_agg_sort_passes(k);
   DigitSpecs specs{};
   unsigned long long *pre_hist = nullptr;
-  if (c->opt("s2_pre_hist", 1) != 0 && c->opt("s2_dummy_list", 1) != 0 && (int)passes.size() <= kItemHistRows &&
+  if (c->opt<Opt::s2_pre_hist>() != 0 && c->opt<Opt::s2_dummy_list>() != 0 && (int)passes.size() <= kItemHistRows &&
       c->s1.hist_for((int)passes.size(), passes_signature(passes)) && c->work.count("s2_pre_hist")) {
     pre_hist = c->work["s2_pre_hist"].as<unsigned long long>();
     specs.n = (int)passes.size();
@@ -1913,14 +1899,14 @@ static int s2_agg_in_place(mhx_ctx *c, uint32_t k, mhx_sdbg_result *out) {
 
 int run_s2(mhx_ctx *c, uint32_t k, uint32_t m, mhx_sdbg_result *out) {
   if (c->global_bases) throw Error("read2sdbg_s2: a global layout is set; use the mhx_dist_* entry points");
-  if (!c->filter_on && !c->accumulate && c->n_parts <= 1 && s2_use_aggregated(c, k, m) && c->opt("s2_agg_in_place", 1))
+  if (!c->filter_on && !c->accumulate && c->n_parts <= 1 && s2_use_aggregated(c, k, m) && c->opt<Opt::s2_agg_in_place>())
     return s2_agg_in_place(c, k, out);
   if (s2_agg_from_count_applies(c, k, m)) {
     std::string why;
     if (s2_agg_from_count(c, k, m, out, &why)) return 0;
     // s2_agg_from_count = 3: a caller that left the memory plan to this route (s2_count_pass_items) hears that it did not serve — the
     // per-occurrence items of a whole job that was never cut into lv1 bucket ranges may not fit
-    if (c->opt("s2_agg_from_count", 1) == 3) throw Error("read2sdbg_s2: stage 2 from a count given up (" + why + ")");
+    if (c->opt<Opt::s2_agg_from_count>() == 3) throw Error("read2sdbg_s2: stage 2 from a count given up (" + why + ")");
   }
   const StageItems it = extract_stage(c, MHX_STAGE_S2, k, m);
   uint32_t *buf_a = c->work["items_a"].as<uint32_t>();

@@ -430,7 +430,7 @@ int sdbg_mul_histogram(mhx_ctx *c, const mhx_sdbg_index_info *info, uint64_t *n_
     // sized from the device, not from n: 4 workgroups per compute unit (32 KB of LDS each), fewer when there are fewer tiles
     const uint64_t n_tiles = div_ceil(n, kHistTile);
     const unsigned grid = (unsigned)std::min<uint64_t>(n_tiles, 4ull * (uint64_t)(c->n_cus > 0 ? c->n_cus : 256));
-    const uint32_t flush_tiles = (uint32_t)std::min<long long>(kHistMaxFlushTiles, std::max<long long>(1, c->opt("sdbg_hist_flush_tiles", kHistMaxFlushTiles)));
+    const uint32_t flush_tiles = (uint32_t)std::min<long long>(kHistMaxFlushTiles, std::max<long long>(1, c->opt<Opt::sdbg_hist_flush_tiles>(kHistMaxFlushTiles)));
     MHX_LAUNCH(c, "sdbg_mul_hist", (double)n * 2 + (double)nw64 * 8,
                hipLaunchKernelGGL(k_sdbg_mul_hist, dim3(grid), dim3(256), 0, st, mul, inv, n, flush_tiles, hist));
   }

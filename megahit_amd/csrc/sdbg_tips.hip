@@ -136,7 +136,7 @@ int sdbg_remove_tips(mhx_ctx *c, const mhx_sdbg_index_info *info, int max_tip_le
   MHX_HIP(hipMemsetAsync(cnt, 0, 8, st));
   const unsigned grid = (unsigned)div_ceil(g.n, 256);
   MHX_LAUNCH(c, "tips_init", (double)g.n * 2, hipLaunchKernelGGL(k_tips_init, dim3(grid), dim3(256), 0, st, g, ignored));
-  const bool listed = c->opt("tips_candidate_list", 1) != 0;
+  const bool listed = c->opt<Opt::tips_candidate_list>() != 0;
   uint32_t *wcnt = listed ? c->ws("tips_word_cnt", (nw + 1) * 4).as<uint32_t>() : nullptr;
   uint64_t *woff = listed ? c->ws("tips_word_off", (nw + 2) * 8).as<uint64_t>() : nullptr;
   auto walk = [&](int len, int dir) {

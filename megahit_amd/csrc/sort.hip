@@ -297,7 +297,7 @@ static uint32_t *radix_sort_onesweep(mhx_ctx *c, uint32_t *a, uint32_t *b, uint6
   // ... or loaded from an array split by an earlier digit (s1_skm.hip): 16-byte records, this unit shape, unit-wide runs
   constexpr bool kCanSplit = S == 4 && NI == 8 && UT == 2;
   static_assert(!kCanSplit || (uint64_t)kSortThreads * NI * UT == kSortSplitUnit, "a unit of the split pass");
-  const bool split = kCanSplit && !prep.gen && prep.split_fill && prep.split_ubase && prep_fits && c->opt("sort_unit_runs", 1) != 0 &&
+  const bool split = kCanSplit && !prep.gen && prep.split_fill && prep.split_ubase && prep_fits && c->opt<Opt::sort_unit_runs>() != 0 &&
                      prep.split_range_cap > 0 && prep.split_range_cap % kSortSplitUnit == 0;
   if (!gen && !split) refuse_unconsumed_generator(prep, "radix sort (chained scan)");
   // (item slots the first pass walks — more than n when the generator drops the items of filtered-out lv1 buckets, or the last unit of a range is not full)
@@ -306,7 +306,7 @@ static uint32_t *radix_sort_onesweep(mhx_ctx *c, uint32_t *a, uint32_t *b, uint6
   // the whole 8-XCD part with a couple of hundred workgroups resident at once (MI355X in SPX mode: 256 CUs x 3-4 workgroups).
   // On a partition (CPX: 32 CUs, one XCD) or an unknown device the single ticket counter is used: its look-back only ever
   // waits for lower tickets, which are running by construction.
-  const int xcd_units = c->opt("sort_xcd_units", 1) != 0 && c->n_cus >= 192;
+  const int xcd_units = c->opt<Opt::sort_xcd_units>() != 0 && c->n_cus >= 192;
   const uint64_t unit = (uint64_t)kSortThreads * NI * UT;
   auto units_of = [&](uint64_t items) { return xcd_units ? (div_ceil(items, unit) + 127) / 128 * 128 : div_ceil(items, unit); };
   const uint64_t n_units = units_of(n), n_units_gen = units_of(gen_slots);
@@ -315,7 +315,7 @@ static uint32_t *radix_sort_onesweep(mhx_ctx *c, uint32_t *a, uint32_t *b, uint6
   // instead of 140, four workgroups per CU instead of three (the SQ counters of round 6 show the waves of these passes parked at
   // waits and barriers for two thirds of their cycles: latency, not issue) — at the price of shorter unit-wide runs
   constexpr bool kCanUt2 = S == 3 && NI == 8 && UT == 3;
-  const bool loaded_ut2 = kCanUt2 && c->opt("sort_loaded_ut2", 0) != 0;
+  const bool loaded_ut2 = kCanUt2 && c->opt<Opt::sort_loaded_ut2>() != 0;
   const uint64_t unit2 = (uint64_t)kSortThreads * NI * 2;
   const uint64_t n_units2 = xcd_units ? (div_ceil(n, unit2) + 127) / 128 * 128 : div_ceil(n, unit2);
   const uint64_t n_status = std::max(n_units_gen, loaded_ut2 ? n_units2 : 0);
@@ -350,11 +350,11 @@ static uint32_t *radix_sort_onesweep(mhx_ctx *c, uint32_t *a, uint32_t *b, uint6
   hipLaunchKernelGGL(k_bin_starts, dim3(P), dim3(256), 0, st, gh, starts);
   // unit-wide runs (k_radix_onesweep_u) for the default unit shape of every width; MHX_SORT_UNIT_RUNS=0: the tile-by-tile kernel
   constexpr bool kHasUnitRuns = (S <= 3 && NI == 8 && (UT == 3 || UT == 2)) || (S == 4 && NI == 8 && UT == 2) || (S > 4 && NI == 4 && UT == 2);
-  const bool unit_runs = kHasUnitRuns && c->opt("sort_unit_runs", 1) != 0;
+  const bool unit_runs = kHasUnitRuns && c->opt<Opt::sort_unit_runs>() != 0;
   // sort_rank_uniform: passes whose plan declares the bits sorted before them (SortPass::prev_lo) rank with one LDS atomic per
   // record wherever all records of a wavefront instruction agree on those bits, with the ballots elsewhere (RANK 2 of
   // k_radix_onesweep_u: correct whatever order the LDS applies the lanes in).  Every other loading pass: the ballots.
-  const bool rank_uniform = unit_runs && c->opt("sort_rank_uniform", 1) != 0;
+  const bool rank_uniform = unit_runs && c->opt<Opt::sort_rank_uniform>() != 0;
   for (int p = 0; p < P; ++p) {
     const int nb = passes[p].bits + passes[p].bits2;
     const int wi = digit_word_of(all[p], nb, 1);
@@ -617,8 +617,8 @@ static bool seg_finish(mhx_ctx *c, const uint32_t *in, uint32_t *out, uint64_t n
 // may order equal keys arbitrarily).
 uint32_t *sort_whole_key(mhx_ctx *c, uint32_t *a, uint32_t *b, uint64_t n, int stride, int key_words, const std::vector<SortPass> &passes,
                          SortPrep *prep) {
-  const int mode = (int)c->opt("sort_hybrid", 1);  // 0: never, 1: when the cost model says so, 2: always (tests)
-  const uint64_t min_n = (uint64_t)c->opt("sort_hybrid_min", 1 << 16);
+  const int mode = (int)c->opt<Opt::sort_hybrid>();  // 0: never, 1: when the cost model says so, 2: always (tests)
+  const uint64_t min_n = (uint64_t)c->opt<Opt::sort_hybrid_min>();
   if (!mode || n < min_n || n >= (1ull << 40)) return radix_sort(c, a, b, n, stride, key_words, passes, prep);
   // Cost model, picoseconds per record on MI355X (measured at 0.8-1.2 x 10^8 records, round 3, profiles/r03_bench_klist.json):
   // an LSD pass moves the record twice, ~3 ps per 32-bit word (0.71 ms for 117 M 8-byte records, 1.9 ms for 82 M 40-byte
@@ -634,7 +634,7 @@ uint32_t *sort_whole_key(mhx_ctx *c, uint32_t *a, uint32_t *b, uint64_t n, int s
   int best_bits = 0;
   double best = (double)passes.size() * pass_ps;
   for (int pbits = 8; pbits <= 32; pbits += 8) {
-    const double t = (pbits / 8) * pass_ps + finish_ps(pbits) + (double)c->opt("sort_hybrid_margin_ps", 6);
+    const double t = (pbits / 8) * pass_ps + finish_ps(pbits) + (double)c->opt<Opt::sort_hybrid_margin_ps>();
     if ((double)n / (double)(1ull << pbits) <= 64.0 && t < best) {  // (segments of hundreds of records: the walk is quadratic)
       best = t;
       best_bits = pbits;
@@ -644,7 +644,7 @@ uint32_t *sort_whole_key(mhx_ctx *c, uint32_t *a, uint32_t *b, uint64_t n, int s
     best_bits = 8;
     while (best_bits < 32 && (double)n / 4.0 > (double)(1ull << best_bits)) best_bits += 8;
   }
-  if (const long long f = c->opt("sort_hybrid_bits", 0)) best_bits = (int)std::min<long long>(32, std::max<long long>(1, f));
+  if (const long long f = c->opt<Opt::sort_hybrid_bits>()) best_bits = (int)std::min<long long>(32, std::max<long long>(1, f));
   if (!best_bits) return radix_sort(c, a, b, n, stride, key_words, passes, prep);
   uint32_t *sorted = radix_sort(c, a, b, n, stride, key_words, make_passes(key_words, key_words * 32 - best_bits, key_words * 32), prep);
   uint32_t *other = sorted == a ? b : a;
@@ -710,7 +710,7 @@ bool sort_takes_generated_first_pass(const mhx_ctx *c, uint64_t n, int stride, c
 
 bool sort_takes_split_first_pass(const mhx_ctx *c, const std::vector<SortPass> &passes) {
   const SortEnv env = sort_env();  // (the same per-call decision radix_sort_impl2 takes for 16-byte records)
-  if (env.classic || c->opt("sort_unit_runs", 1) == 0) return false;
+  if (env.classic || c->opt<Opt::sort_unit_runs>() == 0) return false;
   if ((!env.shape.empty() && env.shape != "8x2") || (env.items && env.items != default_items<4>())) return false;
   return !passes.empty() && passes.size() <= (size_t)kMaxChainedPasses && passes.size() <= (size_t)kMaxFusedPasses;
 }
