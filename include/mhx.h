@@ -136,6 +136,14 @@ int mhx_set_option(mhx_ctx *, const char *name, long long value);
  *                          per-char counters + k_count_giant_look for the keys without an in- or out-edge
  *   count_event_share (4)  several GPUs: the event regions of k_s1_stream<COUNT> hold items / count_event_share events in all
  *   s1_stream_wide (1)     0: stage 1 at k = 23..29 takes the segment group-by (k_s1_seg); 1: the bucket streaming with 64-bit table keys
+ *   s1_agg_wide (0)        1: stage 1 at k = 23..27 with a min count >= 2, no mercy, on the bucket streaming leaves stage 2's aggregated items
+ *                          itself, as it does at k <= 22, in the compact form of stage 2 from a count — chars, flag | W, then the 60 - 2k
+ *                          count bits that are left (14 at k = 23, 6 at k = 27); a larger multiplicity becomes several items, which the
+ *                          emission sums — and stage 2 sorts them where they lie instead of counting the (k+1)-mers a second time; also
+ *                          for reads of several lengths, under a bucket filter and on several GPUs (8-byte items in stage 2's exchange,
+ *                          if every rank has them).  mhx_last_s1_plan then ends in "[aggregated stage-2 items, <cb> count bits]".  Any
+ *                          way back from the bucket streaming (s1_stream_probes = 0, an output region that overflowed, k_s1_seg, the
+ *                          classic kernel) leaves no items and stage 2 runs as with 0.  Same SdBG either way
  *   s2_agg_from_count (1)  0: stage 2 always makes its solid items per occurrence where stage 1 left no aggregated ones; 1: min count 1
  *                          (k <= 27) and min count >= 2 at k = 23..27 take them from a count of the (k+1)-mers (s2.hip s2_agg_from_count)
  *                          3: as 1, and a job the route gives up on fails mhx_read2sdbg_s2 ("... stage 2 from a count given up (why)", nothing
@@ -347,6 +355,11 @@ int mhx_read2sdbg_s1(mhx_ctx *, uint32_t k, uint32_t min_count, int want_mercy, 
  * prefix plan on the whole job) when the input turns out not to be served, low-complexity reads for one, and the caller plans as before
  * with s1_skm = 0.  host/mhx_core.cpp read2sdbg does exactly that. */
 int mhx_s1_self_planned(mhx_ctx *, uint32_t k, uint32_t min_count, int want_mercy);
+/* 1 while the handle holds the aggregated stage-2 items that the last mhx_read2sdbg_s1 left for (k, min_count) — always at k <= 22 with a
+ * min count >= 2, at k = 23..27 where s1_agg_wide had the bucket streaming leave them — that is, until a stage 2 sorts them where they lie
+ * or the reads or the bitmap change.  A caller that plans stage 2's memory asks this (about 0.5 items per base with them, 2.2 per
+ * occurrence without); host/mhx_core.cpp does. */
+int mhx_s1_left_items(mhx_ctx *, uint32_t k, uint32_t min_count);
 /* The same question for mhx_count (count on super-k-mer records: one GPU, 19 <= k <= 21, min count <= 2): on 1 the caller sets option
  * count_skm = 3 and calls mhx_count once without a bucket filter; a job the path gives up on fails that call, and the caller plans lv1
  * bucket ranges as before with count_skm = 0. */
@@ -641,7 +654,10 @@ typedef struct {
   uint64_t n_items;
   uint32_t item_bytes;
 } mhx_dist_items;
-/* extract + partition; counts[p] = items destined to owner p (n_parts entries) */
+/* extract + partition; counts[p] = items destined to owner p (n_parts entries).  MHX_STAGE_S2 behind a stage 1 with a min count >= 2 at
+ * k <= 22 yields the 8-byte aggregated items on every rank (a function of the arguments alone), else per-occurrence items: at k = 23..27
+ * s1_agg_wide does NOT apply to a stage 1 run through these building blocks (mhx_dist_process_s1) — whether a rank's group-by leaves the
+ * compact items follows its data, and only mhx_dist_read2sdbg makes the ranks agree on it before anything is exchanged */
 int mhx_dist_extract(mhx_ctx *, int stage, uint32_t k, uint32_t min_count, mhx_dist_items *out, uint64_t *counts);
 /* library-owned device buffer to receive n_items items into */
 void *mhx_dist_recv_buffer(mhx_ctx *, uint64_t n_items, uint32_t item_bytes);

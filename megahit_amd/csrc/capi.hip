@@ -804,6 +804,7 @@ int mhx_s1_self_planned(mhx_ctx *c, uint32_t k, uint32_t min_count, int want_mer
     return 0;
   }
 }
+int mhx_s1_left_items(mhx_ctx *c, uint32_t k, uint32_t min_count) { return c && mhx::s2_use_aggregated(c, k, min_count) ? 1 : 0; }
 int mhx_count_self_planned(mhx_ctx *c, uint32_t k, uint32_t min_count) {
   if (!c) return 0;
   try {
@@ -1246,10 +1247,13 @@ uint64_t mhx_stage_pass_bytes(mhx_ctx *c, int stage, uint32_t k, uint32_t min_co
       const bool gen = mhx::s1_filter_in_gen_applies(c, k);
       // the generating first pass: two 12-byte record buffers, nothing staged, nothing split; its status words walk ALL item slots
       // + the partial sums of the giant buckets' slices (s1.hip S1Giant: max(2 M, items / 64) entries of 16 bytes) and, k <= 22 with a min
-      // count >= 2, the aggregated stage-2 items of the kept buckets at their bound (two 8-byte items per solid run of >= min_count records)
+      // count >= 2, the aggregated stage-2 items of the kept buckets at their bound (two 8-byte items per solid run of >= min_count records);
+      // k = 23..27 with s1_agg_wide: the same, and two more per strand for every 2^cb - 1 records of a run (the compact form's pieces)
+      const bool wide = k >= 23 && k <= 27 && c->opt<mhx::Opt::s1_agg_wide>() != 0;
       if (gen)
         return n_items * 24 + n_items / 2 + (c->seqs.n_bases + 4 * c->seqs.n_seqs) / 3 + giant_partial_bytes(n_items) +
-               (k <= 22 && min_count >= 2 ? n_items * 16 / min_count : 0);
+               ((k <= 22 || wide) && min_count >= 2 ? n_items * 16 / min_count : 0) +
+               (wide && min_count >= 2 ? n_items * 16 / ((1ull << mhx::s2_agg_compact_bits(k)) - 1) : 0);
       return n_items * (3 * (uint64_t)mhx::s1_stride(k, mhx::s1_compact(c, k, 0)) * 4 + 1);
     }
     if (stage == MHX_STAGE_COUNT && c->seqs.n_seqs) {
@@ -1276,7 +1280,9 @@ uint64_t mhx_stage_once_bytes(mhx_ctx *c, int stage, uint32_t k, uint32_t min_co
   try {
     // stage 2 from a count of the (k+1)-mers (s2.hip s2_agg_from_count): two 12-byte record buffers per edge occurrence — about one per
     // base, where the caller's item estimate (per-occurrence items) is ~2.2 per base — and the few aggregated items behind them
-    if (stage == MHX_STAGE_S2 && c->seqs.n_seqs && !c->filter_on && mhx::s2_agg_from_count_applies(c, k, min_count)) return n_items * 13;
+    // (not where stage 1 left the aggregated items themselves — k = 23..27 with s1_agg_wide: run_s2 takes those first, as at k <= 22)
+    if (stage == MHX_STAGE_S2 && c->seqs.n_seqs && !c->filter_on && !mhx::s2_use_aggregated(c, k, min_count) && mhx::s2_agg_from_count_applies(c, k, min_count))
+      return n_items * 13;
     return 0;
   } catch (...) {
     return 0;
@@ -1284,7 +1290,7 @@ uint64_t mhx_stage_once_bytes(mhx_ctx *c, int stage, uint32_t k, uint32_t min_co
 }
 uint64_t mhx_s2_from_count_bytes(mhx_ctx *c, uint32_t k, uint32_t min_count, uint64_t est_items, uint64_t pass_records) {
   try {
-    if (!c->seqs.n_seqs || c->filter_on || !mhx::s2_agg_from_count_applies(c, k, min_count)) return 0;
+    if (!c->seqs.n_seqs || c->filter_on || mhx::s2_use_aggregated(c, k, min_count) || !mhx::s2_agg_from_count_applies(c, k, min_count)) return 0;
     const uint64_t records = mhx::s2_count_records(c, k);
     // (the items are not known before the count: one per record and four per read, at most the caller's per-occurrence estimate)
     const uint64_t items = std::min<uint64_t>(records + 4 * c->seqs.n_seqs, est_items);

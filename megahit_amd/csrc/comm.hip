@@ -911,6 +911,12 @@ int mhx_dist_read2sdbg(mhx_ctx *c, mhx_comm *cm, uint32_t k, uint32_t min_count,
         c->s1_density = std::max(1.0, (double)mx[0] * (double)cm->n / (double)MHX_NUM_BUCKETS);
       }
       const mhx::ClearDensity clear_density{c};
+      // (the compact aggregated items of k = 23..27: agreed on below, behind the passes; cleared on every way out, an exception included)
+      struct WideAgreed {
+        mhx_ctx *c;
+        explicit WideAgreed(mhx_ctx *ctx) : c(ctx) { c->s1_agg_wide_agreed = true; }
+        ~WideAgreed() { c->s1_agg_wide_agreed = false; }
+      } wide_agreed(c);
       for (int pass = 0; pass < dp.n; ++pass) {
         mhx::set_pass(c, dp, pass, true);
         mhx_s1_result rp{};
@@ -959,9 +965,19 @@ int mhx_dist_read2sdbg(mhx_ctx *c, mhx_comm *cm, uint32_t k, uint32_t min_count,
         if (num_mercy) *num_mercy = nm;
       }
     }
+    // k = 23..27 with s1_agg_wide: an owner's group-by leaves the compact aggregated items only where the bucket streaming did its whole
+    // job, which follows the data — the ranks exchange them only if every rank has them (one all-reduce; else all drop theirs and stage 2
+    // exchanges per-occurrence items as before)
+    bool wide_items = false;
+    if (min_count > 1 && !need_mercy && k >= 23 && k <= 27 && c->opt<mhx::Opt::s1_agg_wide>() != 0) {
+      std::vector<uint64_t> veto{c->s1.items_for(k, min_count) ? 0ull : 1ull};
+      cm->all_reduce(veto, true);
+      wide_items = veto[0] == 0;
+      if (!wide_items) c->s1.consume_items();
+    }
     mhx_sdbg_result r2{};
     {
-      const size_t ib2 = (min_count > 1 && k <= 22) ? 8 : (size_t)mhx::s2_stride(k) * 4;
+      const size_t ib2 = (min_count > 1 && (k <= 22 || wide_items)) ? 8 : (size_t)mhx::s2_stride(k) * 4;
       const mhx::DistPasses dp = mhx::plan_dist_passes(c, cm, MHX_STAGE_S2, k, min_count, ib2);
       for (int pass = 0; pass < dp.n; ++pass) {
         mhx::set_pass(c, dp, pass, false);

@@ -899,7 +899,9 @@ int main_read2sdbg(int argc, char **argv) {
     // selects the faster stable order instead (DESIGN.md "H1")
     const int mercy_mode = !need_mercy ? 0 : (getenv("MHX_STABLE_TIES") ? 1 : 2);
     const size_t s1_item_bytes = 16 + (k > 30 ? (size_t)((2 * (k - 1) + 6 + 31) / 32 - 2 + 1) / 2 * 8 : 0);
-    // fixed: 1 B/base mark map + bitmap + the aggregated stage-2 items kept for stage 2 (k <= 22: <= 8 B per base, typically 1)
+    // fixed: 1 B/base mark map + bitmap + the aggregated stage-2 items kept for stage 2 (k <= 22, and k = 23..27 with s1_agg_wide: <= 8 B
+    // per base, typically 1)
+    const bool s1_items = k <= 22 || (k <= 27 && !need_mercy && mhx_get_option(c, "s1_agg_wide", 0) != 0);
     // Stage 1 on super-k-mer records plans its own passes (include/mhx.h: mhx_s1_self_planned): asked first, unless the environment
     // dictates a plan (MHX_MAX_ITEMS / MHX_FREE_BYTES: tests of the lv1 bucket plan).  If the input turns out not to be served —
     // low-complexity reads — the call fails and the lv1 bucket plan takes over.
@@ -915,7 +917,7 @@ int main_read2sdbg(int argc, char **argv) {
     if (!s1_done) {
       const auto ranges = plan_ranges(c, mercy_mode ? MHX_STAGE_S1_MERCY : MHX_STAGE_S1, k, m, s1_item_bytes,
                                       (double)mhx_num_bases(c) + 4.0 * (double)mhx_num_sequences(c),
-                                      (double)mhx_num_bases(c) * (1.0 + 0.125 + (k <= 22 ? 1.0 : 0.0)));
+                                      (double)mhx_num_bases(c) * (1.0 + 0.125 + (s1_items ? 1.0 : 0.0)));
       uint64_t n1 = 0;
       for (size_t i = 0; i < ranges.size(); ++i) {
         set_range(c, ranges, i, true);
@@ -943,8 +945,10 @@ int main_read2sdbg(int argc, char **argv) {
     }
   }
   const size_t s2_item_bytes = (size_t)(((2 * k + 4 + 31) / 32 + 1) / 2 * 2) * 4;
-  // per-occurrence path: up to 2 + 4/(solid run) items per base position; the aggregated path (k <= 22) is far smaller
-  const double s2_items_bound = (m > 1 && k <= 22 ? 0.5 : 2.2) * (double)mhx_num_bases(c);
+  // per-occurrence path: up to 2 + 4/(solid run) items per base position; the aggregated path (k <= 22, and wherever the handle says
+  // stage 1 left the items) is far smaller
+  const bool s2_items = m > 1 && (k <= 22 || mhx_s1_left_items(c, k, m) == 1);
+  const double s2_items_bound = (s2_items ? 0.5 : 2.2) * (double)mhx_num_bases(c);
   S2CountPlan s2_count;
   const long long from_count_before = mhx_get_option(c, "s2_agg_from_count", 1);
   auto ranges2 = plan_ranges(c, MHX_STAGE_S2, k, m, s2_item_bytes, s2_items_bound, 0, &s2_count);

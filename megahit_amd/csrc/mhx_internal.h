@@ -89,6 +89,10 @@ struct mhx_ctx {
   // stage 1: records per lv1 bucket the ranks of a multi-GPU run agreed on (comm.hip; 0: each call derives it from its own
   // item count, s1.hip s1_density) — every rank must make the same sort plan
   double s1_density = 0;
+  // several GPUs: this stage 1 runs inside mhx_dist_read2sdbg, which makes the ranks agree on whether all of them hold the compact aggregated
+  // items of k = 23..27 (s1_agg_wide) before stage 2 exchanges anything.  A caller that drives the building blocks itself
+  // (mhx_dist_process_s1, mhx_dist_extract, its own exchange, mhx_dist_process_s2) has no such agreement: no such items there
+  bool s1_agg_wide_agreed = false;
   std::string last_s1_plan;           // what the last stage 1 ran as (mhx_last_s1_plan; bench.py prints it)
   // memory-bounded passes (passes.hip): only items of the kept lv1 buckets are materialised
   bool filter_on = false, accumulate = false;
@@ -304,7 +308,7 @@ bool s2_use_aggregated(const mhx_ctx *c, uint32_t k, uint32_t m);
 uint64_t s2_agg_extract(mhx_ctx *c, uint32_t k);
 int s2_agg_process(mhx_ctx *c, uint32_t k, uint32_t *buf_a, uint32_t *buf_b, uint64_t n_items, mhx_sdbg_result *out, SortPrep *prep = nullptr);
 // the sort passes of aggregated stage-2 items: flag | W above the count_bits count bits, then the chars of the k-mer
-std::vector<SortPass> s2_agg_sort_passes(uint32_t k, int count_bits = 16);
+std::vector<SortPass> s2_agg_sort_passes(uint32_t k, int count_bits);  // count_bits: s2_agg_count_bits(k)
 struct StageItems {
   uint64_t n;      // items in ws("items_a")
   int S;           // words per item
@@ -364,6 +368,10 @@ int sdbg_load_bytes(mhx_ctx *c, const uint8_t *bytes, uint64_t n_bytes, const ui
 int run_count(mhx_ctx *c, uint32_t k, uint32_t m, mhx_count_result *out);
 // count on the bucket streaming of stage 1 (s1.hip: CountGenT, k_s1_stream<COUNT>)
 int s2_agg_compact_bits(uint32_t k);
+inline int s2_agg_count_bits(uint32_t k) {  // the count field of an aggregated item of this k: 16 bits up to k = 22, the compact form's beyond
+  const int cb = s2_agg_compact_bits(k);
+  return cb ? cb : 16;
+}
 bool s2_agg_from_count_applies(const mhx_ctx *c, uint32_t k, uint32_t m);  // s2.hip: stage 2's solid items from a count of the (k+1)-mers  // count bits of a compact aggregated stage-2 item (k = 23..28), 0: none
 // ... with the count in passes over its own lv1 bucket ranges (s2_count_pass_items): at most kS2CountMaxPasses of them; s2_count_records: the
 // records of the whole count; s2_from_count_need: the device bytes the route holds beyond the stage's fixed state with passes of pass_records

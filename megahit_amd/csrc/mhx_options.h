@@ -70,6 +70,7 @@
   X(s1_giant, 1)                   \
   X(s1_giant_min, 262144)          \
   X(s1_pack_fixed, 1)              \
+  X(s1_agg_wide, 0)                \
   X(count_stream, 1)               \
   X(count_event_share, 4)          \
   X(count_giant, 1)                \

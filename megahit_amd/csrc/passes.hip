@@ -62,8 +62,10 @@ static StageItems extract_all(mhx_ctx *c, int stage, uint32_t k, uint32_t m, boo
     r.n = seq2sdbg_extract(c, k);
     r.S = seq2sdbg_stride(k);
   } else if (stage == MHX_STAGE_S2) {
-    // every rank / pass must take the same path: the aggregated one needs stage 1 to have run with this (k, m),
-    // which the (k <= 22, m >= 2) rule makes a pure function of the arguments
+    // every rank / pass must take the same path: the aggregated one needs stage 1 to have run with this (k, m), which the
+    // (k <= 22, m >= 2) rule makes a pure function of the arguments.  The compact items of k = 23..27 (s1_agg_wide) follow the data — a
+    // way back from the bucket streaming leaves none — so on several GPUs only mhx_dist_read2sdbg makes them, which lets the ranks agree
+    // (comm.hip: one all-reduce, all or none); under a bucket filter a later pass makes them only behind passes that left theirs
     r.agg = s2_use_aggregated(c, k, m);
     if (r.agg) {
       r.n = s2_agg_extract(c, k);  // stage-1 aggregates + dummies from the bitmap: not a per-read scan

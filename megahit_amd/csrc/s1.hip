@@ -500,6 +500,9 @@ struct S1Stage {
   bool classic_ran = false;
   long long *mercy = nullptr;
   bool agg = false;
+  // k = 23..27 (s1_agg_wide): the items take the compact form (s2_agg_compact_bits), and only the bucket streaming makes them — every way
+  // back from it switches `agg` off again, so that nothing is published
+  bool agg_wide = false;
   uint2 *agg_items = nullptr;
   uint64_t *agg_cursor = nullptr;
   uint64_t agg_prev = 0, agg_bound = 0;
@@ -584,18 +587,26 @@ struct S1Stage {
     // aggregated stage-2 items (k <= 22, m >= 2): at most 2 per solid run, a solid run has >= m records
     const bool agg_off = getenv("MHX_S2_PER_OCCURRENCE") != nullptr;  // (read per call: a resident server answers requests with different environments)
     agg = !agg_off && k <= 22 && m >= 2 && KWv == 2;
+    agg_wide = !agg_off && k >= 23 && k <= 27 && m >= 2 && KWv == 2 && !want_mercy && plan.stream && c->opt<Opt::s1_agg_wide>() != 0;
+    // (whether a rank ends up with these items follows its data: on several GPUs only where the ranks agree on it afterwards)
+    if (global && !c->s1_agg_wide_agreed) agg_wide = false;
     const S1Handoff::Opened opened = c->s1.open_items(k, m, acc);
+    // (a later bucket-range pass: only behind earlier passes that left theirs — one that went a way back left none, and half a job's items
+    //  would be a wrong SdBG)
+    if (agg_wide && acc && !opened.continues) agg_wide = false;
+    agg = agg || agg_wide;
     agg_cursor = c->ws("s2_agg_cursor", 64).as<uint64_t>();
     // (counts of an earlier stage on their way to the device: their copies have long run, but only a synchronisation says so)
     if (!opened.in_flight.empty()) MHX_HIP(hipStreamSynchronize(st));
     agg_prev = opened.continues ? c->s1.agg_n : 0;  // items of the earlier passes stay in front
     agg_bound = (n_items / m + 16) * 2;
+    if (agg_wide) agg_bound += n_items / ((1ull << s2_agg_compact_bits(k)) - 1) * 2;  // the pieces of the multiplicities past the count field
     // Stage 2 sorts exactly these items plus its '$' items when it takes them in place (s2.hip s2_agg_in_place): the kernels that pack
     // them take the digit histograms of that sort.  A workspace of their own: the front of a later pass over a range of bins writes
     // "sort_pre_hist" again.  Not when the items continue those of an earlier call (accumulate): the rows would be partial.
     agg_hist = nullptr;
     if (agg && !global && !c->filter_on && !c->accumulate && agg_prev == 0 && c->opt<Opt::s2_pre_hist>() != 0) {
-      const std::vector<SortPass> ps = s2_agg_sort_passes(k);
+      const std::vector<SortPass> ps = s2_agg_sort_passes(k, s2_agg_count_bits(k));
       if (!ps.empty() && ps.size() <= (size_t)kItemHistRows) {
         agg_specs.n = (int)ps.size();
         for (size_t p = 0; p < ps.size(); ++p) agg_specs.d[p] = spec_of_pass(ps[p], 2);
@@ -606,7 +617,14 @@ struct S1Stage {
     }
     seg_err = c->ws("s1_seg_err", 64).as<uint32_t>();
   }
+  // the bucket streaming did not finish the job: no compact items (k_s1_seg and the classic kernel write the 16-bit layout)
+  void agg_wide_off() {
+    if (!agg_wide) return;
+    agg = agg_wide = false;
+    agg_hist = nullptr;
+  }
   void agg_prepare_classic() {  // k_tile_groups appends to the dense array through a global cursor
+    agg_wide_off();
     agg_hist = nullptr;  // (... and takes no histograms)
     if (!agg) return;
     agg_items = grow_preserving(c, c->work["s2_agg_items"], (agg_prev + agg_bound) * 8, agg_prev * 8).as<uint2>();
@@ -631,7 +649,13 @@ struct S1Stage {
     //  kernel of their own — lost on every box for two rounds and are gone with their code: profiles/r03_ab_*, r05_ab_marks_list.jsonl)
     const bool half = false;
     const uint64_t cus = c->n_cus > 0 ? (uint64_t)c->n_cus : 256;
-    const unsigned grid = (unsigned)std::min<uint64_t>(n_work, plan.stream ? (half ? 2 * cus : cus) : (per == 4 ? 256 * 6 : 256 * 3));
+    unsigned grid = (unsigned)std::min<uint64_t>(n_work, plan.stream ? (half ? 2 * cus : cus) : (per == 4 ? 256 * 6 : 256 * 3));
+    // the compact items: a key at the multiplicity cap leaves 2 * ceil(65535 / cmax) of them (2082 at k = 27) in ONE workgroup's region, and
+    // low-complexity keys share a bucket — a small job gets fewer, larger regions (eight such keys each), a large one has them anyway
+    if (agg_on && agg_wide) {
+      const uint64_t min_region = 16 * ((uint64_t)MHX_MAX_MUL / ((1ull << s2_agg_compact_bits(k)) - 1) + 1);
+      grid = (unsigned)std::min<uint64_t>(grid, std::max<uint64_t>(1, n_items * (uint64_t)S * 4 / 8 / min_region));
+    }
     // per-workgroup output regions in the spare sort buffer (S*4 >= 12 bytes per record, outputs are 8-byte entries)
     const uint32_t region = (uint32_t)std::min<uint64_t>(n_items * (uint64_t)S * 4 / 8 / grid, 0xFFFFFFF0u);
     uint2 *raw = nullptr;
@@ -714,10 +738,12 @@ struct S1Stage {
       }
       S1StreamLaunch sl{agg_on, half, tags, false, false, grid, items0, bounds, a, geo, stride, ticket, srcs, n_src};
       sl.key64 = key64;
+      sl.wide = agg_on && agg_wide;
       s1_stream_launch(c, nm, bytes, sl);
       if (giant_on) {  // the giants' partial entries -> the same per-key work, the same per-workgroup output regions
         S1StreamLaunch gl{agg_on, false, tags, true, false, grid, items0, bounds, a, geo, 1u, ticket2, nullptr, 1};
         gl.key64 = key64;
+        gl.wide = sl.wide;
         s1_stream_launch(c, "s1_giant_groups", 0.0, gl);
       }
       return;
@@ -819,6 +845,7 @@ struct S1Stage {
       MHX_HIP(hipMemcpyAsync(hist, hist_save, (MHX_MAX_MUL + 1) * 8, hipMemcpyDeviceToDevice, st));
       MHX_HIP(hipMemsetAsync(ctr, 0, 64, st));
       seg_marks = 0;
+      agg_wide_off();  // (whatever runs next is not the bucket streaming)
       uint32_t *other;
       if (plan.stream) {
         if (pre && sorted == nullptr) gather_sources();
@@ -917,6 +944,7 @@ struct S1Stage {
       c->s1.agg_n = 0;
       MHX_HIP(hipMemcpyAsync(&c->s1.agg_n, agg_cursor, 8, hipMemcpyDeviceToHost, st));
       c->s1.publish_items(k, m, agg_hist ? agg_specs.n : 0, agg_sig);
+      if (agg_wide) c->last_s1_plan += " [aggregated stage-2 items, " + std::to_string(s2_agg_compact_bits(k)) + " count bits]";
     }
     if (sparse && classic_ran) {  // the classic kernel marked a byte map of the global read set: turn it into the list
       const uint64_t n_bytes = div_ceil(n_bits, 64) * 64;

@@ -3,7 +3,8 @@
 // of the library (tests/host/s1_handoff_check.cpp drives it on the CPU).
 //
 // It speaks for four things, each for one (k, m):
-//   items   ws "s2_agg_items" holds agg_n aggregated 8-byte stage-2 items (k <= 22, m >= 2), until a stage 2 sorts them where they lie
+//   items   ws "s2_agg_items" holds agg_n aggregated 8-byte stage-2 items (k <= 22, m >= 2; k = 23..27 in the compact
+//           form where s1_agg_wide had the bucket streaming leave them), until a stage 2 sorts them where they lie
 //   rows    ws "s2_pre_hist" holds the digit histograms of stage 2's sort passes (s2_agg_sort_passes(k), their count and
 //           passes_signature()) over exactly those agg_n items, taken where stage 1 packed them; stage 2 adds its '$' items
 //   bitmap  the is_solid bitmap is exactly what stage 1 found — no mercy edges added, not set by the caller, not a rank's share of

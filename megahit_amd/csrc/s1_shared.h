@@ -154,6 +154,7 @@ struct S1StreamLaunch {  // one launch of k_s1_stream (s1_stream.hip)
   const uint32_t *const *srcs;
   int n_src;
   bool key64 = false;  // local keys wider than 32 bits (k > 22 at a 16-bit prefix)
+  bool wide = false;   // agg at k = 23..27: the compact items (s1_agg_wide)
 };
 void s1_stream_launch(mhx_ctx *c, const char *name, double bytes, const S1StreamLaunch &l);
 void s1_giant_launch(mhx_ctx *c, const uint32_t *items0, const uint32_t *const *srcs, const uint64_t *bounds, int n_src, uint64_t n_buckets, int pbits, int k,

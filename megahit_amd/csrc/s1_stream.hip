@@ -273,7 +273,10 @@ __global__ __launch_bounds__(256) void k_s1_giant_reduce(const uint32_t *__restr
 // bits (min count <= 2: has_in / has_out need no more), a solid key's packed edge goes to the workgroup's region (AGG's), and the
 // records of solid keys without an in- or out-edge — a few per bucket — are found by a second read of the bucket, which brings
 // first_0_out / last_0_in of their reads up to date.
-template <bool AGG, int UNR, int NT, int LOGS, bool TAGS, bool GIANT = false, bool COUNT = false, bool K64 = false>
+// WIDE (k = 23..27, opt-in s1_agg_wide): the aggregated items in the compact form of stage 2 from a count (s2.hip k_edges_to_agg) — chars,
+// flag | W, then the 60 - 2k count bits that are left; a solid key of a larger multiplicity leaves several items per strand, which the
+// emission sums.  The local key of such a k takes 64 bits at a 16-bit prefix (K64) and 32 under a prefix of 19 bits or more at k = 23.
+template <bool AGG, int UNR, int NT, int LOGS, bool TAGS, bool GIANT = false, bool COUNT = false, bool K64 = false, bool WIDE = false>
 __global__ __launch_bounds__(NT) void k_s1_stream(const uint32_t *__restrict__ items0, const uint64_t *__restrict__ bounds, S1SegArgs a,
                                                   S1StreamGeom geo, uint32_t bucket_stride, uint32_t *__restrict__ ticket,
                                                   const uint32_t *const *__restrict__ srcs, int n_src) {
@@ -284,15 +287,18 @@ __global__ __launch_bounds__(NT) void k_s1_stream(const uint32_t *__restrict__ i
   static_assert(NSLOT % NT == 0 && UNR <= 8, "table walk / pending mask");
   typedef typename StreamKey<K64>::T KeyT;       // K64: local keys wider than 32 bits (k > 22 at a 16-bit prefix): 64-bit compare-and-swap
   constexpr KeyT kEmpty = StreamKey<K64>::kEmpty;
-  static_assert(!K64 || !AGG || COUNT, "aggregated stage-2 items exist up to k = 22: their keys fit 32 bits");
+  static_assert(!K64 || !AGG || COUNT || WIDE, "aggregated stage-2 items with 16 count bits exist up to k = 22: their keys fit 32 bits");
+  static_assert(!WIDE || (AGG && !COUNT), "the compact items are stage 1's");
   __shared__ KeyT keys[NSLOT];
   __shared__ uint32_t cnts[NSLOT];
   __shared__ uint32_t fpos[NSLOT];             // position word of the record that claimed the slot (direct_marks)
   __shared__ uint8_t ftag[TAGS ? NSLOT : 4];   // ... and the position bits above it (s1_pos_tag), when the read set has any
   __shared__ uint32_t lhist[kSegHist];
   __shared__ uint32_t s_bad[2], s_nclaimed[2];  // per round, double-buffered: the next round's are cleared while this round's are read
-  constexpr int NLIST = NSLOT / 4;              // solid keys of a round waiting for their aggregated items (more: worked off in place)
-  __shared__ uint2 slist[AGG && !COUNT ? NLIST : 1];
+  // solid keys of a round waiting for their aggregated items (more: worked off in place).  64-bit keys: an entry is two elements — the key,
+  // then the count — and there are half as many of them (the table's 128 KB leave no room for more)
+  constexpr int NLIST = K64 ? NSLOT / 8 : NSLOT / 4;
+  __shared__ uint2 slist[AGG && !COUNT ? (K64 ? 2 * NLIST : NLIST) : 1];
   __shared__ uint32_t s_list_n[2];
   __shared__ uint32_t s_agg_cur, s_mark_cur;
   __shared__ uint32_t s_flagged;  // COUNT: the round has a solid key without an in- or out-edge
@@ -388,19 +394,29 @@ __global__ __launch_bounds__(NT) void k_s1_stream(const uint32_t *__restrict__ i
     return r;
   };
   // the (k+1)-mer head.S.tail of a table key of bucket bi, chars MSB-first in 64 bits
-  auto edge_of = [&](uint32_t bi, uint32_t lk) -> uint64_t {
+  auto edge_of = [&](uint32_t bi, KeyT lk) -> uint64_t {
     const uint64_t smer = ((uint64_t)bi << (64 - pbits)) | (rem ? (uint64_t)(lk >> 6) << (64 - pbits - rem) : 0ull);
-    return ((uint64_t)((lk >> 3) & 7u) << 62) | (smer >> 2) | ((uint64_t)(lk & 7u) << (62 - 2 * k));
+    return ((uint64_t)(((uint32_t)lk >> 3) & 7u) << 62) | (smer >> 2) | ((uint64_t)((uint32_t)lk & 7u) << (62 - 2 * k));
   };
+  // WIDE: the count field of a compact item (s2.hip s2_agg_compact_bits) and what it holds
+  const int wide_cb = WIDE ? min(16, 60 - 2 * k) : 16;
+  const uint32_t wide_cmax = (1u << wide_cb) - 1u;
   // the aggregated stage-2 items of a solid key (one per strand; one for a palindrome) -> this workgroup's region, from its end.
   // dense: called by whole wavefronts (the place comes from one LDS atomic per wavefront); otherwise by single lanes.
-  auto emit_items = [&](uint32_t bi, uint32_t lk, uint32_t cnt, bool dense, bool valid = true) {
+  // WIDE: per strand ceil(min(cnt, MHX_MAX_MUL) / cmax) of them, every one with at most cmax in its count field.
+  auto emit_items = [&](uint32_t bi, KeyT lk, uint32_t cnt, bool dense, bool valid = true) {
     uint64_t x = 0, xr = 0;
     uint32_t n_out = 0;
+    [[maybe_unused]] uint32_t strands = 0, pieces = 0;
     if (valid) {
       x = edge_of(bi, lk);
       xr = rc64(x, k + 1);
       n_out = x == xr ? 1u : 2u;
+      if constexpr (WIDE) {
+        strands = n_out;
+        pieces = (min(cnt, (uint32_t)MHX_MAX_MUL) + wide_cmax - 1u) / wide_cmax;
+        n_out = strands * pieces;
+      }
     }
     uint32_t at;
     bool ok;
@@ -421,7 +437,25 @@ __global__ __launch_bounds__(NT) void k_s1_stream(const uint32_t *__restrict__ i
       atomicOr(a.err, 1u);
       return;
     }
-    if (n_out) {
+    if constexpr (WIDE) {
+      if (n_out) {  // (the layout of k_edges_to_agg: flag at cb + 3, W at cb, the count at bit 0)
+        const uint64_t mask_k = ~0ull << (64 - 2 * k);
+        const uint64_t f0 = ((x << 2) & mask_k) | (1ull << (wide_cb + 3)) | ((x >> 62) << wide_cb);
+        const uint64_t b0 = ((xr << 2) & mask_k) | (1ull << (wide_cb + 3)) | ((xr >> 62) << wide_cb);
+        uint32_t left = min(cnt, (uint32_t)MHX_MAX_MUL);
+        uint2 *dst = agg_end - 1 - (long)at;
+        for (uint32_t p = 0; p < pieces; ++p) {
+          const uint32_t c = min(left, wide_cmax);
+          left -= c;
+          const uint64_t f = f0 | c;
+          *dst-- = make_uint2((uint32_t)(f >> 32), (uint32_t)f);
+          if (strands == 2) {
+            const uint64_t b = b0 | c;
+            *dst-- = make_uint2((uint32_t)(b >> 32), (uint32_t)b);
+          }
+        }
+      }
+    } else if (n_out) {
       const uint64_t mask_k = ~0ull << (64 - 2 * k);
       const uint64_t mul = cnt > MHX_MAX_MUL ? (uint64_t)MHX_MAX_MUL : cnt;
       const uint64_t f = ((x << 2) & mask_k) | (1ull << 19) | ((x >> 62) << 16) | mul;
@@ -1170,8 +1204,16 @@ __global__ __launch_bounds__(NT) void k_s1_stream(const uint32_t *__restrict__ i
 #pragma unroll
             for (int it = 0; it < W; ++it)
               if ((want_bits >> it) & 1u) {
-                if (at < (uint32_t)NLIST) slist[at] = make_uint2((uint32_t)wk[it], wc[it]);
-                else emit_items(bi, (uint32_t)wk[it], wc[it], false);  // (more solid keys in one round than the list holds: in place)
+                if (at < (uint32_t)NLIST) {
+                  if constexpr (K64) {
+                    slist[2 * at] = make_uint2((uint32_t)wk[it], (uint32_t)((unsigned long long)wk[it] >> 32));
+                    slist[2 * at + 1].x = wc[it];
+                  } else {
+                    slist[at] = make_uint2((uint32_t)wk[it], wc[it]);
+                  }
+                } else {
+                  emit_items(bi, wk[it], wc[it], false);  // (more solid keys in one round than the list holds: in place)
+                }
                 ++at;
               }
           }
@@ -1184,8 +1226,13 @@ __global__ __launch_bounds__(NT) void k_s1_stream(const uint32_t *__restrict__ i
         const uint32_t n_list = min(s_list_n[rp], (uint32_t)NLIST);
         for (uint32_t base = 0; base < n_list; base += NT) {
           const uint32_t i = base + tid;
-          const uint2 e = i < n_list ? slist[i] : make_uint2(0u, 0u);
-          emit_items(bi, e.x, e.y, true, i < n_list);
+          if constexpr (K64) {
+            const uint2 ek = i < n_list ? slist[2 * i] : make_uint2(0u, 0u);
+            emit_items(bi, (KeyT)(((unsigned long long)ek.y << 32) | ek.x), i < n_list ? slist[2 * i + 1].x : 0u, true, i < n_list);
+          } else {
+            const uint2 e = i < n_list ? slist[i] : make_uint2(0u, 0u);
+            emit_items(bi, e.x, e.y, true, i < n_list);
+          }
         }
       }
       rp ^= 1;
@@ -1344,16 +1391,29 @@ void s1_giant_launch(mhx_ctx *c, const uint32_t *items0, const uint32_t *const *
 
 void s1_stream_launch(mhx_ctx *c, const char *name, double bytes, const S1StreamLaunch &l) {
   hipStream_t st = c->stream;
-#define MHX_STREAM_K(AGGV, NTV, LOGV, TAGV, GIANTV, COUNTV, K64V)                                                                                     \
-  MHX_LAUNCH(c, name, bytes, hipLaunchKernelGGL((k_s1_stream<AGGV, 4, NTV, LOGV, TAGV, GIANTV, COUNTV, K64V>), dim3(l.grid), dim3(NTV), 0, st, l.items0, \
+#define MHX_STREAM_KW(AGGV, NTV, LOGV, TAGV, GIANTV, COUNTV, K64V, WIDEV)                                                                                     \
+  MHX_LAUNCH(c, name, bytes, hipLaunchKernelGGL((k_s1_stream<AGGV, 4, NTV, LOGV, TAGV, GIANTV, COUNTV, K64V, WIDEV>), dim3(l.grid), dim3(NTV), 0, st, l.items0, \
                                                 l.bounds, l.a, l.geo, l.stride, l.ticket, l.srcs, l.n_src))
+#define MHX_STREAM_K(AGGV, NTV, LOGV, TAGV, GIANTV, COUNTV, K64V) MHX_STREAM_KW(AGGV, NTV, LOGV, TAGV, GIANTV, COUNTV, K64V, false)
 #define MHX_STREAM(AGGV, NTV, LOGV, TAGV, GIANTV, COUNTV) MHX_STREAM_K(AGGV, NTV, LOGV, TAGV, GIANTV, COUNTV, false)
 #define MHX_STREAM_T(AGGV, NTV, LOGV, GIANTV, COUNTV)             \
   do {                                                            \
     if (l.tags) MHX_STREAM(AGGV, NTV, LOGV, true, GIANTV, COUNTV); \
     else MHX_STREAM(AGGV, NTV, LOGV, false, GIANTV, COUNTV);       \
   } while (0)
-  if (l.key64 && l.count) {  // count at k = 23..27 (or under a forced narrow prefix): no position tags in those records
+  if (l.wide) {  // stage 1 at k = 23..27 with the compact aggregated items (s1_agg_wide): either key width, with or without tags, both launches
+    if (!l.agg || l.half || l.count || l.a.k < 23 || l.a.k > 27) throw Error("s1_stream_launch: the compact aggregated items are stage 1's at k = 23..27 on full tables");
+#define MHX_STREAM_W(TAGV, GIANTV)                                                        \
+  do {                                                                                    \
+    if (l.key64) MHX_STREAM_KW(true, kStreamThreads, 13, TAGV, GIANTV, false, true, true); \
+    else MHX_STREAM_KW(true, kStreamThreads, 13, TAGV, GIANTV, false, false, true);        \
+  } while (0)
+    if (l.giant && l.tags) MHX_STREAM_W(true, true);
+    else if (l.giant) MHX_STREAM_W(false, true);
+    else if (l.tags) MHX_STREAM_W(true, false);
+    else MHX_STREAM_W(false, false);
+#undef MHX_STREAM_W
+  } else if (l.key64 && l.count) {  // count at k = 23..27 (or under a forced narrow prefix): no position tags in those records
     if (!l.agg || l.half || l.tags) throw Error("s1_stream_launch: count with 64-bit local keys runs on full tables, edge regions, no position tags");
     if (l.giant) MHX_STREAM_K(true, kStreamThreads, 13, false, true, true, true);
     else MHX_STREAM_K(true, kStreamThreads, 13, false, false, true, true);
@@ -1380,6 +1440,7 @@ void s1_stream_launch(mhx_ctx *c, const char *name, double bytes, const S1Stream
 #undef MHX_STREAM_T
 #undef MHX_STREAM
 #undef MHX_STREAM_K
+#undef MHX_STREAM_KW
 }
 
 #ifdef MHX_TILE_TIMING

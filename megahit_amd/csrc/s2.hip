@@ -1475,8 +1475,9 @@ static S2dFront s2d_open(mhx_ctx *c, uint32_t k, uint32_t m, const unsigned long
   return f;
 }
 // The '$' items of the front, written behind the n_agg items of `items` (room for n_agg + f.bound); -> their number.
-// hist: the digit histograms of `specs` are added up there (k_s2d_emit's list form only).
-static uint64_t s2d_emit_items(mhx_ctx *c, uint32_t k, const S2dFront &f, uint32_t *items, uint64_t n_agg, int fsh = 19, int bsh = 16, int csh = 0,
+// hist: the digit histograms of `specs` are added up there (k_s2d_emit's list form only).  fsh / bsh / csh: where the flag, W and the count
+// sit in an item of this k — s2_agg_count_bits(k) + 3, s2_agg_count_bits(k), 0 — which every caller states.
+static uint64_t s2d_emit_items(mhx_ctx *c, uint32_t k, const S2dFront &f, uint32_t *items, uint64_t n_agg, int fsh, int bsh, int csh,
                                const DigitSpecs *specs = nullptr, unsigned long long *hist = nullptr) {
   if (!f.bound) return 0;
   uint2 *dst = reinterpret_cast<uint2 *>(items) + n_agg;
@@ -1506,13 +1507,14 @@ static uint64_t s2d_emit_items(mhx_ctx *c, uint32_t k, const S2dFront &f, uint32
   if ((h_cur[4] & 0xFFFFFFFFull) || h_cur[0] > f.bound) throw Error("read2sdbg_s2: more '$' items than their bound");
   return h_cur[0];
 }
-// aggregated stage 2 (k <= 22): solid items from stage 1 + dummy items from the local reads -> ws "items_a"
+// aggregated stage 2 (k <= 22; k = 23..27 in the compact form, s1_agg_wide): solid items from stage 1 + dummy items from the local reads -> ws "items_a"
 uint64_t s2_agg_extract(mhx_ctx *c, uint32_t k) {
+  const int cbits = s2_agg_count_bits(k);
   const uint64_t n_agg = c->s1.agg_n;
   const S2dFront f = s2d_open(c, k, c->s1.items_m(), nullptr, c->global_bases ? MHX_BUF_IS_SOLID_LOCAL : MHX_BUF_IS_SOLID, !c->global_bases);
   uint32_t *buf_a = c->ws("items_a", (n_agg + f.bound) * 8 + 64).as<uint32_t>();
   if (n_agg) MHX_HIP(hipMemcpyAsync(buf_a, c->work["s2_agg_items"].p, n_agg * 8, hipMemcpyDeviceToDevice, c->stream));
-  return n_agg + s2d_emit_items(c, k, f, buf_a, n_agg);
+  return n_agg + s2d_emit_items(c, k, f, buf_a, n_agg, cbits + 3, cbits, 0);
 }
 std::vector<SortPass> s2_agg_sort_passes(uint32_t k, int count_bits) {
   return make_passes_ranges(2, {{count_bits, count_bits + 4}, {64 - 2 * (int)k, 64}});
@@ -1521,8 +1523,8 @@ std::vector<SortPass> s2_agg_sort_passes(uint32_t k, int count_bits) {
 // left for the sort (their digit histograms)
 int s2_agg_process(mhx_ctx *c, uint32_t k, uint32_t *buf_a, uint32_t *buf_b, uint64_t n_items, mhx_sdbg_result *out, SortPrep *prep) {
   // (the whole-key order also orders equal keys by their count bits: the emission sums them, any order does)
-  uint32_t *sorted = sort_whole_key(c, buf_a, buf_b, n_items, 2, 2, s2_agg_sort_passes(k), prep);
-  emit_sdbg(c, sorted, n_items, 2, 2, k, 2, out);
+  uint32_t *sorted = sort_whole_key(c, buf_a, buf_b, n_items, 2, 2, s2_agg_sort_passes(k, s2_agg_count_bits(k)), prep);
+  emit_sdbg(c, sorted, n_items, 2, 2, k, 2, out, s2_agg_compact_bits(k));
   return 0;
 }
 
@@ -1532,8 +1534,9 @@ int s2_agg_process(mhx_ctx *c, uint32_t k, uint32_t *buf_a, uint32_t *buf_b, uin
 // equal items (read_to_sdbg_s2.cpp:398-409, counted again at :579) — so `count` on the bucket streaming (k_s1_stream<COUNT>, edges only:
 // no positions, no first_0_out / last_0_in) gives every solid item with its multiplicity, and only the '$' items at the ends of the
 // solid runs come from the reads.  Serves min count 1 (main_sdbg_build.cpp:139-147: stage 1 skipped, EVERY occurrence is an item: the
-// meta presets — 10^10 items at 40 M reads, k = 27) for k <= 27, and min count >= 2 at k = 23..27, where stage 1 has no aggregated items
-// of its own (they need 2k + 20 <= 64 bits).  k >= 23: the same 8-byte layout — chars, flag | W, count — with a count field of the 60 - 2k
+// meta presets — 10^10 items at 40 M reads, k = 27) for k <= 27, and min count >= 2 at k = 23..27 wherever stage 1 left no aggregated items
+// of its own (with 16 count bits they need 2k + 20 <= 64 bits; with s1_agg_wide stage 1 leaves them in the compact form below, and run_s2
+// takes those first).  k >= 23: the same 8-byte layout — chars, flag | W, count — with a count field of the 60 - 2k
 // bits that are left (an edge with a larger multiplicity becomes several items: the emission sums them).
 // ---------------------------------------------------------------------------------------------------------------
 int s2_agg_compact_bits(uint32_t k) { return k >= 23 && k <= 28 ? std::min(16, 60 - 2 * (int)k) : 0; }
@@ -1873,7 +1876,8 @@ static int s2_agg_in_place(mhx_ctx *c, uint32_t k, mhx_sdbg_result *out) {
   // Stage 1 took the digit histograms of this sort over its n_agg items where it packed them (ws "s2_pre_hist", for exactly this k and
   // this pass plan); k_s2d_emit adds those of the '$' items, and the sort reads no histogram of its own.  Anything that does not match:
   // the sort takes them itself.
-  const std::vector<SortPass> passes = s2_agg_sort_passes(k);
+  const int cbits = s2_agg_count_bits(k);
+  const std::vector<SortPass> passes = s2_agg_sort_passes(k, cbits);
   DigitSpecs specs{};
   unsigned long long *pre_hist = nullptr;
   if (c->opt<Opt::s2_pre_hist>() != 0 && c->opt<Opt::s2_dummy_list>() != 0 && (int)passes.size() <= kItemHistRows &&
@@ -1884,7 +1888,7 @@ static int s2_agg_in_place(mhx_ctx *c, uint32_t k, mhx_sdbg_result *out) {
   }
   // (from here on the items are being consumed, and the rows count '$' items too: a call that fails below leaves nothing that claims otherwise)
   c->s1.consume_items();
-  const uint64_t n_items = n_agg + s2d_emit_items(c, k, f, buf_a, n_agg, 19, 16, 0, &specs, pre_hist);
+  const uint64_t n_items = n_agg + s2d_emit_items(c, k, f, buf_a, n_agg, cbits + 3, cbits, 0, &specs, pre_hist);
   uint32_t *buf_b = c->ws("items_b", n_items * 8 + 64).as<uint32_t>();
   SortPrep prep;
   if (pre_hist) {

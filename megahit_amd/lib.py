@@ -203,6 +203,7 @@ SYMBOLS = {
     "mhx_reset": (C.c_int, [_P]),
     "mhx_last_s1_plan": (C.c_char_p, [_P]),
     "mhx_s1_self_planned": (C.c_int, [_P, C.c_uint32, C.c_uint32, C.c_int]),
+    "mhx_s1_left_items": (C.c_int, [_P, C.c_uint32, C.c_uint32]),
     "mhx_count_self_planned": (C.c_int, [_P, C.c_uint32, C.c_uint32]),
     "mhx_profile_enable": (C.c_int, [_P, C.c_int]),
     "mhx_profile_reset": (C.c_int, [_P]),
@@ -641,6 +642,10 @@ class Engine:
     def count_self_planned(self, k, min_count):
         """count would run on super-k-mer records and cut the job into passes by itself (mhx_count_self_planned)"""
         return bool(self.lib.mhx_count_self_planned(self.h, k, min_count))
+
+    def s1_left_items(self, k, min_count):
+        """the handle holds the aggregated stage-2 items stage 1 left for (k, min_count) (mhx_s1_left_items)"""
+        return bool(self.lib.mhx_s1_left_items(self.h, k, min_count))
 
     def last_s1_plan(self):
         """what the last stage 1 of this handle ran as (mhx_last_s1_plan)"""
