@@ -318,7 +318,9 @@ enum mhx_buffer {
   MHX_BUF_LOCAL_ITEMS = 47,   /* uint64[n_items]: the collector's encoded reads, grouped by contig, then end, ascending inside a group */
   MHX_BUF_LOCAL_OFFSETS = 48, /* uint64[2 * n_contigs + 1]: the items of (contig c, end e) are [offsets[2c + e], offsets[2c + e + 1]) */
   /* mhx_sdbg_mul_histogram (below) */
-  MHX_BUF_SDBG_MUL_HIST = 49  /* uint64[65536]: bin v = valid edges (bit clear in MHX_BUF_SDBG_INVALID) with MHX_BUF_SDBG_MUL == v */
+  MHX_BUF_SDBG_MUL_HIST = 49, /* uint64[65536]: bin v = valid edges (bit clear in MHX_BUF_SDBG_INVALID) with MHX_BUF_SDBG_MUL == v */
+  /* mhx_bgzf_inflate (below) */
+  MHX_BUF_FASTX_TEXT = 50     /* char[n_text]: the inflated text */
 };
 /* bytes currently held in a result buffer (0 if absent) */
 uint64_t mhx_buffer_bytes(const mhx_ctx *, int which);
@@ -573,6 +575,50 @@ typedef struct {
   int status;
 } mhx_fastx_result;
 int mhx_fastx_to_records(mhx_ctx *, const char *text1, uint64_t n1, const char *text2, uint64_t n2, mhx_fastx_result *out);
+
+/* ---- BGZF read files (the blocked gzip of bgzip: a concatenation of gzip members of at most 64 KiB, each an independent DEFLATE
+ * stream whose compressed size stands in its header and whose CRC32 and length stand in its trailer) inflated on the GPU, one block
+ * per wavefront, and parsed where the text lies.  The host only walks the members (O(blocks), nothing inflated).
+ * mhx_bgzf_inflate: gz[0 .. n) -> its text in MHX_BUF_FASTX_TEXT (mhx_fetch), every block checked against its CRC32 and ISIZE.
+ * status 0: inflated.  status 2: the file is not BGZF throughout (reason: one of the scan's, bad_block: the member it is about) or a
+ * block failed (reason: one of the decoder's, bad_block: the first such block); no text is left then.  An empty file and a file of
+ * end-of-file blocks alone are BGZF with an empty text.
+ * mhx_fastx_bgzf_to_records: mhx_fastx_to_records on the texts of one or two BGZF files (gz2 == NULL: unpaired).  status 0 / 1 as
+ * there; status 2: a file was not inflated on the device (mhx_bgzf_inflate tells why) and nothing was produced: inflate on the host.
+ * Device memory per file: the compressed bytes + the text + 64 + 32 bytes per block (+ 1.3 KB of tables), next to what
+ * mhx_fastx_to_records takes for a text of that size less its own copy of the text. ---- */
+enum mhx_bgzf_reason {
+  MHX_BGZF_OK = 0,
+  /* the scan: the file is not BGZF throughout */
+  MHX_BGZF_NOT_GZIP = 1,     /* a member does not begin 1f 8b 08 */
+  MHX_BGZF_FLG = 2,          /* FLG is not exactly 4 (plain gzip, or a name, a comment, a header CRC) */
+  MHX_BGZF_NO_BC = 3,        /* no 'B','C' extra subfield of length 2 */
+  MHX_BGZF_SHORT_BLOCK = 4,  /* a block shorter than 26 bytes, or than its own header, subfields and trailer */
+  MHX_BGZF_PAST_EOF = 5,     /* a block that runs past the end of the file */
+  MHX_BGZF_TRAILING = 6,     /* trailing bytes that are not a whole member (fewer than a member's fixed header) */
+  MHX_BGZF_ISIZE = 7,        /* ISIZE above 65536 */
+  /* the decoder: a block's DEFLATE stream or its trailer */
+  MHX_BGZF_PAYLOAD_END = 8,     /* end of the payload before the final block's end-of-block symbol */
+  MHX_BGZF_BTYPE = 9,           /* BTYPE 3 */
+  MHX_BGZF_STORED_LEN = 10,     /* stored block: LEN != ~NLEN */
+  MHX_BGZF_CODE_OVER = 11,      /* an over-subscribed code */
+  MHX_BGZF_CODE_INCOMPLETE = 12, /* an incomplete code (beyond the single code of length 1 zlib accepts) */
+  MHX_BGZF_BAD_SYMBOL = 13,     /* bits that are no code's, literal/length 286 / 287, distance 30 / 31, a repeat without a length before it
+                                 * or past the counts, no end-of-block code, more than 286 / 30 codes */
+  MHX_BGZF_DIST_FAR = 14,       /* a match that reaches before the block's start */
+  MHX_BGZF_OUT_OVER = 15,       /* output past ISIZE */
+  MHX_BGZF_OUT_SHORT = 16,      /* the stream ends with fewer bytes than ISIZE */
+  MHX_BGZF_CRC = 17             /* the text's CRC32 is not the trailer's */
+};
+typedef struct {
+  int status;
+  uint32_t reason;   /* enum mhx_bgzf_reason */
+  uint64_t bad_block;
+  uint64_t n_blocks; /* members, empty ones included */
+  uint64_t n_text;   /* bytes of text */
+} mhx_bgzf_result;
+int mhx_bgzf_inflate(mhx_ctx *, const void *gz, uint64_t n, mhx_bgzf_result *out);
+int mhx_fastx_bgzf_to_records(mhx_ctx *, const void *gz1, uint64_t n1, const void *gz2, uint64_t n2, mhx_fastx_result *out);
 
 /* ---- `iterate` — the (k+step+1)-mer edges that the loaded reads (FORWARD orientation:
  * mhx_load_bin_records(..., reverse = 0)) support next to the contigs of round k.  Replaces ContigFlankIndex +

@@ -896,6 +896,20 @@ int mhx_fastx_to_records(mhx_ctx *c, const char *text1, uint64_t n1, const char 
     mhx::fastx_to_records(c, text1, n1, text2, n2, out);
   })
 }
+int mhx_bgzf_inflate(mhx_ctx *c, const void *gz, uint64_t n, mhx_bgzf_result *out) {
+  MHX_TRY({
+    MHX_HIP(hipSetDevice(c->device));
+    if (!out || (!gz && n)) throw mhx::Error("bgzf_inflate: bad arguments");
+    mhx::bgzf_inflate(c, gz, n, out);
+  })
+}
+int mhx_fastx_bgzf_to_records(mhx_ctx *c, const void *gz1, uint64_t n1, const void *gz2, uint64_t n2, mhx_fastx_result *out) {
+  MHX_TRY({
+    MHX_HIP(hipSetDevice(c->device));
+    if (!out || !gz1) throw mhx::Error("fastx_bgzf_to_records: bad arguments");
+    mhx::fastx_bgzf_to_records(c, gz1, n1, gz2, n2, out);
+  })
+}
 int mhx_sdbg_build_index(mhx_ctx *c, uint32_t k, mhx_sdbg_index_info *out) {
   MHX_TRY({
     MHX_HIP(hipSetDevice(c->device));

@@ -172,22 +172,22 @@ struct ParsedFastx {
   int status = 0;
 };
 
-static ParsedFastx parse_one(mhx_ctx *c, const char *h_text, uint64_t n, const std::string &tag, unsigned long long *totals) {
+// what the host has to see of a text: its first byte, its last and the one before it (0 where the text has none)
+struct TextEdge {
+  char first = 0, last = 0, last2 = 0;
+};
+// the shapes that are declined before anything is parsed
+static bool declined_by_edge(const TextEdge &e, uint64_t n) {
+  if (e.first != '>' && e.first != '@') return true;  // kseq skips junk up to the first header: rare, sequential parser
+  return e.first == '>' && e.last == '>' && (n == 1 || e.last2 == '\n');  // kseq: end of file, no record (see the top)
+}
+
+// t: the text on the device, n > 0 bytes and 64 more that may be read (not declined_by_edge)
+static ParsedFastx parse_device(mhx_ctx *c, const char *t, uint64_t n, const TextEdge &edge, const std::string &tag, unsigned long long *totals) {
   hipStream_t st = c->stream;
   ParsedFastx p;
   auto W = [&](const char *name, size_t bytes) -> DevBuf & { return c->ws((tag + name).c_str(), bytes); };
-  if (n == 0) return p;
-  if (h_text[0] != '>' && h_text[0] != '@') {  // kseq skips junk up to the first header: rare, sequential parser
-    p.status = 1;
-    return p;
-  }
-  const bool fastq = h_text[0] == '@';
-  if (!fastq && h_text[n - 1] == '>' && (n == 1 || h_text[n - 2] == '\n')) {  // kseq: end of file, no record (see the top)
-    p.status = 1;
-    return p;
-  }
-  char *t = W("text", n + 64).as<char>();
-  upload_pinned(c, t, h_text, n);
+  const bool fastq = edge.first == '@';
   const uint64_t n_chunks = div_ceil(n, (uint64_t)kTextChunk);
   uint32_t *cnt = W("nl_cnt", (n_chunks + 1) * 4).as<uint32_t>();
   uint64_t *coff = W("nl_off", (n_chunks + 2) * 8).as<uint64_t>();
@@ -205,7 +205,7 @@ static ParsedFastx parse_one(mhx_ctx *c, const char *h_text, uint64_t n, const s
     p.status = 1;
     return p;
   }
-  const uint64_t n_lines = n_nl + (h_text[n - 1] == '\n' ? 0 : 1);
+  const uint64_t n_lines = n_nl + (edge.last == '\n' ? 0 : 1);
   uint64_t *ls = W("line_start", (n_nl + 2) * 8).as<uint64_t>();
   MHX_LAUNCH(c, "fastx_line_starts", (double)n,
              hipLaunchKernelGGL(k_line_starts, dim3((unsigned)div_ceil(n_chunks, 256)), dim3(256), 0, st, t, n, coff, ls));
@@ -263,6 +263,39 @@ static ParsedFastx parse_one(mhx_ctx *c, const char *h_text, uint64_t n, const s
   return p;
 }
 
+// a text on the host: uploaded to the workspace tag + "text", then parsed there
+static ParsedFastx parse_one(mhx_ctx *c, const char *h_text, uint64_t n, const std::string &tag, unsigned long long *totals) {
+  ParsedFastx p;
+  if (n == 0) return p;
+  TextEdge e;
+  e.first = h_text[0];
+  e.last = h_text[n - 1];
+  e.last2 = n > 1 ? h_text[n - 2] : 0;
+  if (declined_by_edge(e, n)) {
+    p.status = 1;
+    return p;
+  }
+  char *t = c->ws((tag + "text").c_str(), n + 64).as<char>();
+  upload_pinned(c, t, h_text, n);
+  return parse_device(c, t, n, e, tag, totals);
+}
+// a text that is on the device already (inflate.hip): parsed where it lies
+static ParsedFastx parse_resident(mhx_ctx *c, const char *d_text, uint64_t n, const char edge[3], const std::string &tag, unsigned long long *totals) {
+  ParsedFastx p;
+  if (n == 0) return p;
+  TextEdge e;
+  e.first = edge[0];
+  e.last = edge[1];
+  e.last2 = n > 1 ? edge[2] : 0;
+  if (declined_by_edge(e, n)) {
+    p.status = 1;
+    return p;
+  }
+  return parse_device(c, d_text, n, e, tag, totals);
+}
+
+static int records_of(mhx_ctx *c, const ParsedFastx &a, const ParsedFastx &b, bool paired, unsigned long long *totals, mhx_fastx_result *out);
+
 int fastx_to_records(mhx_ctx *c, const char *text1, uint64_t n1, const char *text2, uint64_t n2, mhx_fastx_result *out) {
   hipStream_t st = c->stream;
   memset(out, 0, sizeof *out);
@@ -272,6 +305,24 @@ int fastx_to_records(mhx_ctx *c, const char *text1, uint64_t n1, const char *tex
   ParsedFastx a = parse_one(c, text1, n1, "fx1_", totals);
   ParsedFastx b;
   if (paired) b = parse_one(c, text2, n2, "fx2_", totals);
+  return records_of(c, a, b, paired, totals, out);
+}
+
+int fastx_device_to_records(mhx_ctx *c, const char *d_text1, uint64_t n1, const char edge1[3], const char *d_text2, uint64_t n2, const char edge2[3],
+                            bool paired, mhx_fastx_result *out) {
+  hipStream_t st = c->stream;
+  memset(out, 0, sizeof *out);
+  unsigned long long *totals = c->ws("fx_totals", 64).as<unsigned long long>();
+  MHX_HIP(hipMemsetAsync(totals, 0, 64, st));
+  ParsedFastx a = parse_resident(c, d_text1, n1, edge1, "fx1_", totals);
+  ParsedFastx b;
+  if (paired) b = parse_resident(c, d_text2, n2, edge2, "fx2_", totals);
+  return records_of(c, a, b, paired, totals, out);
+}
+
+// the parsed file (or the two mates' files) -> MHX_BUF_LIB_RECORDS
+static int records_of(mhx_ctx *c, const ParsedFastx &a, const ParsedFastx &b, bool paired, unsigned long long *totals, mhx_fastx_result *out) {
+  hipStream_t st = c->stream;
   if (a.status || b.status) {
     out->status = 1;
     return 0;

@@ -192,6 +192,25 @@ TextFile open_text_file(const std::string &path) {
   tf.size = tf.owned.size();
   return tf;
 }
+TextFile map_gzip_file(const std::string &path) {
+  TextFile tf;
+  if (path == "-") return tf;
+  int fd = open(path.c_str(), O_RDONLY);
+  if (fd < 0) return tf;  // (open_text_file reports it)
+  struct stat st;
+  unsigned char magic[2] = {0, 0};
+  if (fstat(fd, &st) == 0 && S_ISREG(st.st_mode) && st.st_size > 0 && pread(fd, magic, 2, 0) == 2 && magic[0] == 0x1f && magic[1] == 0x8b) {
+    void *m = mmap(nullptr, (size_t)st.st_size, PROT_READ, MAP_PRIVATE, fd, 0);
+    if (m != MAP_FAILED) {
+      (void)madvise(m, (size_t)st.st_size, MADV_SEQUENTIAL);
+      tf.map = m;
+      tf.data = static_cast<const char *>(m);
+      tf.size = (size_t)st.st_size;
+    }
+  }
+  ::close(fd);
+  return tf;
+}
 void TextFile::close() {
   if (map) munmap(map, size);
   map = nullptr;

@@ -74,6 +74,8 @@ struct TextFile {
   void close();
 };
 TextFile open_text_file(const std::string &path);
+// A regular file that begins 1f 8b, mapped read-only as it is (nothing inflated); any other path: data == nullptr.
+TextFile map_gzip_file(const std::string &path);
 // Sequential FASTA/FASTQ reader with kseq's semantics (kseq.h:193-247): multi-line records, junk before the first header,
 // '\r' stripped at line ends as ks_getuntil2 does.  next() -> false at the end of the text and at a malformed FASTQ record;
 // after a malformed record a further next() reads on from where that one stopped, as a further kseq_read does.

@@ -32,6 +32,7 @@
 #include <thread>
 #include <vector>
 
+#include "../bgzf_scan.h"
 #include "formats.h"
 #include "mhx.h"
 
@@ -1188,6 +1189,8 @@ int main_seq2sdbg(int argc, char **argv) {
 // buildlib (reference src/main_buildlib.cpp + SequenceLibCollection::Build, sequence_lib.cpp:8-91): read-library
 // description -> <out>.bin + <out>.lib_info.  The texts are parsed and packed on the GPU (mhx_fastx_to_records);
 // a text the GPU parser declines goes through the sequential kseq-compatible parser.  MHX_BUILDLIB_HOST=1 forces that.
+// MHX_BUILDLIB_BGZF=1: a library whose files are BGZF throughout is mapped as it is and inflated on the GPU
+// (mhx_fastx_bgzf_to_records); any other gzip file, and a BGZF file the GPU declines, is inflated by zlib as ever.
 int main_buildlib(int argc, char **argv) {
   if (argc < 3) {
     fprintf(stderr, "Usage %s <read_lib_file> <out_prefix>\n", argv[0]);
@@ -1203,6 +1206,8 @@ int main_buildlib(int argc, char **argv) {
   FILE *bin = fopen((out + ".bin").c_str(), "wb");
   if (!bin) fatal("Cannot open %s.bin", out.c_str());
   const bool host_only = getenv("MHX_BUILDLIB_HOST") != nullptr;
+  const char *bgzf_env = getenv("MHX_BUILDLIB_BGZF");
+  const bool bgzf_route = !host_only && bgzf_env && *bgzf_env && strcmp(bgzf_env, "0") != 0;
   mhx_ctx *c = nullptr;
   struct Lib {
     std::string meta;
@@ -1232,23 +1237,53 @@ int main_buildlib(int argc, char **argv) {
       fprintf(stderr, "Cannot identify read library type %s\n", type);
       fatal("Valid types: pe, se, interleaved");
     }
-    mhxio::TextFile t1 = mhxio::open_text_file(f1), t2;
-    if (ty == "pe") t2 = mhxio::open_text_file(f2);
     const int64_t begin = total_reads;
     unsigned max_len = 0;
     bool done = false;
-    if (!host_only) {
+    auto write_records = [&](const mhx_fastx_result &r) {
+      std::vector<uint32_t> rec(r.n_words);
+      if (r.n_words) CK(mhx_fetch(c, MHX_BUF_LIB_RECORDS, rec.data(), 0, r.n_words * 4));
+      if (r.n_words && fwrite(rec.data(), 4, rec.size(), bin) != rec.size()) fatal("write error on %s.bin", out.c_str());
+      total_reads += (int64_t)r.n_reads;
+      total_bases += (int64_t)r.n_bases;
+      max_len = r.max_len;
+      done = true;
+    };
+    if (bgzf_route) {
+      // the compressed files as they are; both mates must be BGZF throughout, or the whole library is inflated by zlib below
+      mhxio::TextFile g1 = mhxio::map_gzip_file(f1), g2;
+      if (ty == "pe") g2 = mhxio::map_gzip_file(f2);
+      uint64_t n_blocks = 0;
+      bool all = g1.data != nullptr && (ty != "pe" || g2.data != nullptr);
+      for (const mhxio::TextFile *g : {&g1, &g2}) {
+        if (!all || !g->data) continue;
+        const mhx::BgzfScan scan = mhx::bgzf_scan(g->data, g->size);
+        all = scan.reason == mhx::kBgzfOk;
+        n_blocks += scan.blocks.size();
+      }
+      if (all) {
+        if (!c) c = open_gpu();
+        mhx_fastx_result r{};
+        CK(mhx_fastx_bgzf_to_records(c, g1.data, g1.size, ty == "pe" ? g2.data : nullptr, g2.size, &r));
+        if (r.status == 0) {
+          info("%s: BGZF, %llu blocks inflated on the GPU", f1, (unsigned long long)n_blocks);
+          write_records(r);
+        }
+      }
+      g1.close();
+      g2.close();
+    }
+    mhxio::TextFile t1, t2;
+    if (!done) {
+      t1 = mhxio::open_text_file(f1);
+      if (ty == "pe") t2 = mhxio::open_text_file(f2);
+    }
+    if (!done && !host_only) {
       if (!c) c = open_gpu();
       mhx_fastx_result r{};
       CK(mhx_fastx_to_records(c, t1.data, t1.size, ty == "pe" ? t2.data : nullptr, t2.size, &r));
       if (r.status == 0) {
-        std::vector<uint32_t> rec(r.n_words);
-        if (r.n_words) CK(mhx_fetch(c, MHX_BUF_LIB_RECORDS, rec.data(), 0, r.n_words * 4));
-        if (r.n_words && fwrite(rec.data(), 4, rec.size(), bin) != rec.size()) fatal("write error on %s.bin", out.c_str());
-        total_reads += (int64_t)r.n_reads;
-        total_bases += (int64_t)r.n_bases;
-        max_len = r.max_len;
-        done = true;
+        write_records(r);
       } else {
         info("%s: not plain FASTA / four-line FASTQ, using the sequential parser", f1);
       }

@@ -361,6 +361,12 @@ int local_collect(mhx_ctx *c, uint32_t n_libs, const uint64_t *lib_begin, const 
 int local_insert_size(const mhx_local_record *rec, const uint32_t *read_len, uint64_t lib_begin, uint64_t lib_end, uint32_t max_read_len,
                       int paired, double *mean, double *sd, int32_t *local_range);
 int fastx_to_records(mhx_ctx *c, const char *text1, uint64_t n1, const char *text2, uint64_t n2, mhx_fastx_result *out);
+// the same for texts that lie on the device (n bytes and 64 more that may be read); edge: a text's first, last and last but one byte
+int fastx_device_to_records(mhx_ctx *c, const char *d_text1, uint64_t n1, const char edge1[3], const char *d_text2, uint64_t n2, const char edge2[3],
+                            bool paired, mhx_fastx_result *out);
+// ---- inflate.hip ----
+void bgzf_inflate(mhx_ctx *c, const void *gz, uint64_t n, mhx_bgzf_result *out);
+void fastx_bgzf_to_records(mhx_ctx *c, const void *gz1, uint64_t n1, const void *gz2, uint64_t n2, mhx_fastx_result *out);
 int sdbg_load_bytes(mhx_ctx *c, const uint8_t *bytes, uint64_t n_bytes, const uint64_t *off, const uint64_t *items, const uint64_t *tips,
                     const uint64_t *large);
 

@@ -41,6 +41,7 @@ BUF_LOCAL_REC = 46
 BUF_LOCAL_ITEMS = 47
 BUF_LOCAL_OFFSETS = 48
 BUF_SDBG_MUL_HIST = 49
+BUF_FASTX_TEXT = 50
 SIM_MAX_LEN, SIM_MAX_INDEL = 16384, 2047
 # one mhx_local_record (include/mhx.h)
 LOCAL_RECORD_DTYPE = np.dtype([("contig_id", np.uint32), ("contig_from", np.int32), ("contig_to", np.int32), ("query_from", np.int32),
@@ -79,6 +80,10 @@ class KernelStat(C.Structure):
 
 class FastxResult(C.Structure):
     _fields_ = [("n_reads", C.c_uint64), ("n_bases", C.c_uint64), ("n_words", C.c_uint64), ("max_len", C.c_uint32), ("status", C.c_int)]
+
+
+class BgzfResult(C.Structure):
+    _fields_ = [("status", C.c_int), ("reason", C.c_uint32), ("bad_block", C.c_uint64), ("n_blocks", C.c_uint64), ("n_text", C.c_uint64)]
 
 
 class IterateResult(C.Structure):
@@ -157,6 +162,8 @@ SYMBOLS = {
                                         C.POINTER(C.c_int32)]),
     "mhx_local_collect": (C.c_int, [_P, C.c_uint32, _P, _P, _P, _P, _P, _P]),
     "mhx_fastx_to_records": (C.c_int, [_P, C.c_char_p, C.c_uint64, C.c_char_p, C.c_uint64, C.POINTER(FastxResult)]),
+    "mhx_bgzf_inflate": (C.c_int, [_P, C.c_char_p, C.c_uint64, C.POINTER(BgzfResult)]),
+    "mhx_fastx_bgzf_to_records": (C.c_int, [_P, C.c_char_p, C.c_uint64, C.c_char_p, C.c_uint64, C.POINTER(FastxResult)]),
     "mhx_sdbg_build_index": (C.c_int, [_P, C.c_uint32, C.POINTER(SdbgIndexInfo)]),
     "mhx_sdbg_load_bytes": (C.c_int, [_P, _P, C.c_uint64, _P, _P, _P, _P]),
     "mhx_sdbg_remove_tips": (C.c_int, [_P, C.POINTER(SdbgIndexInfo), C.c_int, _P]),
@@ -481,6 +488,20 @@ class Engine:
         """FASTA/FASTQ text -> read-library records on the GPU; returns (FastxResult, uint32 records or None)."""
         r = FastxResult()
         self._chk(self.lib.mhx_fastx_to_records(self.h, text1, len(text1), text2, len(text2) if text2 is not None else 0, C.byref(r)))
+        return r, (self.fetch(BUF_LIB_RECORDS, np.uint32) if r.status == 0 else None)
+
+    def bgzf_inflate(self, gz):
+        """A BGZF file's bytes inflated on the GPU, one block per wavefront, every block checked against its CRC32 and ISIZE
+        (include/mhx.h: mhx_bgzf_inflate); returns (BgzfResult, the text as bytes, or None when status != 0)."""
+        r = BgzfResult()
+        self._chk(self.lib.mhx_bgzf_inflate(self.h, gz, len(gz), C.byref(r)))
+        return r, (self.fetch(BUF_FASTX_TEXT, np.uint8).tobytes() if r.status == 0 else None)
+
+    def fastx_bgzf_to_records(self, gz1, gz2=None):
+        """fastx_to_records on the texts of one or two BGZF files, inflated on the GPU and parsed where they lie; status 2: a file was
+        not inflated there.  Returns (FastxResult, uint32 records or None)."""
+        r = FastxResult()
+        self._chk(self.lib.mhx_fastx_bgzf_to_records(self.h, gz1, len(gz1), gz2, len(gz2) if gz2 is not None else 0, C.byref(r)))
         return r, (self.fetch(BUF_LIB_RECORDS, np.uint32) if r.status == 0 else None)
 
     # ---- `local`, first half (include/mhx.h: mhx_local_*)
